@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the VLM-FO1 hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: re-executes itself under torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: runs itself under torch.distributed.run, a child process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = ONE packed pass of `--batch` (default 25) different images through every hot-path stage the engine implements
 (listed in config.stages: both towers, FPN, HFRE, connectors, splice, 36-layer LLM prefill, first greedy token), inputs already
 resident in HBM; `--inflight` (default 2) passes are in flight on their own HIP streams.  value = images / second.  N>1: images
 shard across ranks with no data-path collective (weak scaling); value = images all ranks processed / max-over-ranks time.
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, live dispatch timestamps), `cpu_baseline` (the oracle at full depth
-on this box's host cores, N = 1 only) and side measurements (one pass / one image at a time, decode loops, preprocessing;
-`--main-only` skips them).  `--fp8` is a secondary, opt-in measurement (e4m3 linears); the default line is bf16.
+A plain run sets up, warms up, times `--steps` steps and prints ONE JSON line on rank 0 (`value`, `ms_per_step`, ...).
+`--full` then goes on with everything else: `roofline` (dominant kernel, live dispatch timestamps), `cpu_baseline` (the oracle at full
+depth on the host cores, N = 1 only), the multi-rank `scale` block and side measurements (one pass / one image at a time, decode
+loops, end to end, driver level, hires, dataset, preprocessing; `--main-only` skips the side measurements).  `--dump-outputs DIR`
+writes what the last timed step returned as DIR/<name>.npy.  `--fp8` is a secondary, opt-in measurement (e4m3 linears); the
+default line is bf16.
 """
 import argparse
 import json
@@ -956,6 +959,42 @@ def compact_line(full: dict) -> dict:
     return line
 
 
+DUMP_NAMES = ("image_tokens", "region_tokens", "last_hidden", "logits", "next_token")
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(outs, out_dir: str) -> dict:
+    """What one step returned to its caller, rows of all requests concatenated: DIR/<name>.npy for every name of DUMP_NAMES, float64
+    for the token ids, float32 otherwise, DUMP_BYTES in all.  Smallest array first, each gets an equal share of what the arrays before
+    it left; one larger than its share (image_tokens at the default pass) is written as a fixed, seeded sample of its rows in
+    ascending order, their indices in DIR/<name>_rows.npy."""
+    import numpy as np
+    if isinstance(outs, dict):          # prefill() of one request
+        outs = [outs]
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for name in DUMP_NAMES:
+        parts = [o[name] for o in outs if o.get(name) is not None]
+        if parts:
+            t = torch.cat(parts, 0)
+            arrays[name] = (t.double() if name == "next_token" else t.float()).cpu().numpy()
+    left, written = DUMP_BYTES, {}
+    for k, name in enumerate(sorted(arrays, key=lambda n: arrays[n].nbytes)):
+        a = arrays[name]
+        share = left // (len(arrays) - k)
+        files = [os.path.join(out_dir, name + ".npy")]
+        if a.nbytes + 128 > share:      # sample + its index file within the share (256: the two .npy headers)
+            row_bytes = a.nbytes // max(1, a.shape[0])
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, (share - 256) // (row_bytes + 8)), replace=False))
+            files.append(os.path.join(out_dir, name + "_rows.npy"))
+            np.save(files[1], rows.astype(np.float64))
+            a = a[rows]
+        np.save(files[0], a)
+        left -= sum(os.path.getsize(f) for f in files)
+        written[name] = list(a.shape)
+    return written
+
+
 def emit(full: dict, json_out: str) -> None:
     """Full record -> json_out (per-kernel tables, notes, loop descriptions); compact contract line -> stdout (ONE line, last)."""
     if json_out:
@@ -1021,10 +1060,22 @@ def main():
                     "verbatim, or COCO-like sizes x 100 boxes); `none` skips it")
     ap.add_argument("--dataset-items", type=int, default=150, help="items of the dataset to run (0 = all)")
     ap.add_argument("--dataset-aux", default="dynamic", choices=["dynamic", "squash"], help="aux image sizing (config aux_image_aspect_ratio)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, everything else this benchmark measures: side measurements, "
+                    "the profiled roofline pass, the multi-rank `scale` block and the CPU baseline (implied by --e2e-only and --profile-shapes); "
+                    "without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned (image / region tokens, "
+                    "last hidden rows, logits, next tokens of every request) as DIR/<name>.npy, float32 / float64, <= 64 MB in all; an "
+                    "array over its share is a fixed, seeded sample of its rows (DIR/<name>_rows.npy)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    args.full = args.full or args.e2e_only or args.profile_shapes
+    if not args.full:         # the headline only: no side measurements, no CPU leg, no scale block, no roofline pass (below)
+        args.main_only = args.no_cpu_baseline = True
+        args.scale_items = 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # `python bench.py --gpus N` without a launcher: become the launcher — one rank per GPU under torch.distributed.run on the
+        # `python bench.py --gpus N` without a launcher: start one as a child process — one rank per GPU under torch.distributed.run on the
         # loopback address (the container hostname may not resolve), same arguments.  rank 0's JSON line is the only stdout line.
         import socket
         with socket.socket() as sk:
@@ -1035,7 +1086,9 @@ def main():
         if os.environ.get("FO1_BENCH_SPAWN_DRYRUN") == "1":      # tests/test_bench_cli.py (no GPU): show the launch instead of doing it
             print(json.dumps(cmd))
             return
-        os.execv(sys.executable, cmd)
+        import subprocess
+        rc = subprocess.call(cmd)
+        sys.exit(128 - rc if rc < 0 else rc)      # killed by signal N: 128 + N, as a shell reports it
 
     # Host tensors on the GPU path (index plans, rope tables) are a few hundred KB: one intra-op thread.  torch's default — one per core,
     # 256 on the GPU box — turns every small torch.cat / clone of the submitting threads into an OpenMP region on an oversubscribed pool
@@ -1113,7 +1166,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        pipe.step(use_graph, k % R)
+        last = pipe.step(use_graph, k % R)
     torch.cuda.synchronize()
     barrier()
     torch.cuda.synchronize()
@@ -1123,6 +1176,9 @@ def main():
         t = torch.tensor([el], device="cpu" if one_dev else dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         el = float(t.item())
+    # before anything else runs on the engines: the last step's outputs live in its replica's graph buffers
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last, args.dump_outputs)
 
     # ---- multi-rank runs: the sharded evaluation loop across the ranks (LPT shard -> prefetch -> pool -> one all_gather); every rank takes
     # part, right after the timed region (the other ranks then leave; rank 0 goes on with its side measurements).  Never `value`. ----
@@ -1304,7 +1360,7 @@ def main():
 
     # ---- roofline of the dominant kernel: separate profiled pass (hipEvents per launch) ----
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         if args.profile_shapes:      # per-shape profile rows: an instrument of include/fo1_ab.h (FO1_AB=1 runs only)
             if not L.ab_build():
                 raise SystemExit("--profile-shapes needs the test / bench build: run with FO1_AB=1")

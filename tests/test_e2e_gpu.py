@@ -104,7 +104,7 @@ def test_graph_replay_is_bit_identical_to_eager():
 
 
 def test_bench_two_ranks_control_flow(tmp_path):
-    """`python bench.py --gpus 2` WITHOUT a launcher (the form the driver uses): bench.py re-executes itself under
+    """`python bench.py --gpus 2` WITHOUT a launcher (the form the driver uses): bench.py runs itself, as a child process, under
     torch.distributed.run with 2 ranks (both on cuda:0 over gloo — a 1-GPU box cannot host two RCCL ranks): the barrier /
     max-over-ranks / rank-0-prints-one-line contract and hipGraph capture with a live process group."""
     import json
@@ -115,7 +115,7 @@ def test_bench_two_ranks_control_flow(tmp_path):
     env = dict(os.environ, FO1_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--main-only", "--scale-items", "64"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--main-only", "--scale-items", "64"]
     p = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -133,6 +133,32 @@ def test_bench_two_ranks_control_flow(tmp_path):
     assert sc["images_per_sec"] > 0 and sc["predictions_file_written"] and sc["host_threads_for_this_run"] == 2 * sc["host_threads_per_gpu"]
     assert sc["items_failed"] == 0, sc
     assert sc["sample_ids_equal_to_one_rank_alone"] is True, sc.get("sample_difference")
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR`: what the LAST timed step returned (step 2 of 2: the second engine replica's graph replay), written
+    before anything else runs on the engines, equals one eager pass over the same seeded inputs in this process, array for array."""
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B = 2
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", str(B), "--json-out", "",
+           "--dump-outputs", str(tmp_path)]
+    p = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    sys.path.insert(0, root)
+    import bench
+    dev = torch.device("cuda", 0)
+    cases = [bench.build_workload(dev, seed=1234 + i) for i in range(B)]
+    outs = bench.Pipeline(cases[0], dev, inflight=1, batch=B, cases=cases).step(graph=False)
+    torch.cuda.synchronize()
+    assert sorted(os.listdir(tmp_path)) == sorted(n + ".npy" for n in bench.DUMP_NAMES), "nothing sampled at this size"
+    for name in bench.DUMP_NAMES:
+        want = torch.cat([o[name] for o in outs], 0)
+        want = (want.double() if name == "next_token" else want.float()).cpu().numpy()
+        assert np.array_equal(np.load(tmp_path / f"{name}.npy"), want), name
 
 
 def test_replicas_in_flight_match_sequential():
