@@ -373,7 +373,8 @@ def test_pool_service_from_replica_threads_equals_direct_pool_runs(product_libra
 def test_pool_attention_one_chunk_writes_rows_without_combine(ab_library):
     """More than 32 sequences whose contexts fit ONE 1024-key chunk (the pool's default): the split kernel writes the normalised rows itself
     (no combine launch).  Against torch fp32 (P rounded to bf16 like the kernel), and against the 512-key split + combine form of the same
-    kernel (other merge order: equal within a bf16 ulp); finished slots keep their previous rows."""
+    kernel (other merge order: equal within a bf16 ulp); a finished slot's row is written as exact zeros (it must stay finite: it flows into
+    the frozen K / V^T rows of later layers)."""
     from vlm_fo1_amd import lib as L, ops
     lib = L.load()
     B, H, KV, HD, slot = 40, 16, 2, 128, 1024
@@ -403,6 +404,8 @@ def test_pool_attention_one_chunk_writes_rows_without_combine(ab_library):
         torch.cuda.synchronize()
     finally:
         lib.fo1_attention_decode_set_impl(0)
+    for c in (1024, 512, "ws"):
+        assert out[c][5].abs().max().item() == 0.0, f"{c}: finished slot 5 has a nonzero (or unwritten) row"
     grp = H // KV
     for b in range(B):
         if b == 5:

@@ -965,6 +965,11 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_wg_kernel(const AttnDecPa
     int kv0 = 0, kv_len;
     if (p.seq_state) {
         const int* st = p.seq_state + b * 8;
+        if (st[3]) {                                 // finished / empty slot: a zero row (several splits: the combine kernel writes it)
+            if (p.n_splits == 1)
+                for (int t = tid; t < p.group * HD; t += NW * 64) p.O[(long long)b * p.o_seq_stride + (long long)kvh * p.group * HD + t] = 0;
+            return;
+        }
         kv0 = st[2];
         kv_len = st[0] + 1;
     } else {
@@ -1133,7 +1138,10 @@ __global__ __launch_bounds__(256) void attn_decode_ws_kernel(const AttnDecParams
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ql = lane & 15, g = lane >> 4;
     const int* st = p.seq_state + b * 8;
-    if (st[3]) return;                               // finished / empty slot (workgroup-uniform)
+    if (st[3]) {                                     // finished / empty slot (workgroup-uniform): a zero row, as attn_fwd_kernel writes
+        for (int t = tid; t < p.group * HD; t += 256) p.O[(long long)b * p.o_seq_stride + (long long)kvh * p.group * HD + t] = 0;
+        return;
+    }
     const int kv0 = st[2], kv_len = st[0] + 1;
     uint16_t* sK = reinterpret_cast<uint16_t*>(smem_ws + wave * WAVE_LDS);
     uint16_t* sVT = sK + KB * LDKR;
@@ -1599,7 +1607,9 @@ static int attention_decode_batch_impl(const void* q, long long q_seq_stride, co
         return set_err(FO1_ERR_WORKSPACE, "attention_decode_batch: workspace too small");
     const int group = n_q_heads / n_kv_heads;
 #ifdef FO1_ENABLE_AB
-    if (g_attn_decode_impl == 1) {
+    // the A/B kernels write the output rows (or their own partial layout): the partials-only entry (combine false, out null) keeps the split
+    // kernel below, whose layout fo1_gemv_attn_combine_bf16 reads
+    if (combine && g_attn_decode_impl == 1) {
         AttnDecParams d;
         d.Q = (const uint16_t*)q; d.q_seq_stride = q_seq_stride;
         d.K = (const uint16_t*)kcache; d.k_tok = k_tok_stride; d.k_head = k_head_stride;
@@ -1609,7 +1619,7 @@ static int attention_decode_batch_impl(const void* q, long long q_seq_stride, co
         d.n_kv_heads = n_kv_heads; d.group = group; d.scale = scale;
         return launch_attn_decode_wg(d, max_kv_len, batch, n_q_heads, (hipStream_t)stream);
     }
-    if (g_attn_decode_impl == 2) {
+    if (combine && g_attn_decode_impl == 2) {
         AttnDecParams d;
         d.Q = (const uint16_t*)q; d.q_seq_stride = q_seq_stride;
         d.K = (const uint16_t*)kcache; d.k_tok = k_tok_stride; d.k_head = k_head_stride;
@@ -1629,8 +1639,9 @@ static int attention_decode_batch_impl(const void* q, long long q_seq_stride, co
     const int chunk = decode_batch_chunk(batch);
     // 17..32 sequences: an item walks 2 tiles of 64 keys and writes each tile's partial separately (see AttnParams.part_tiles) — half the
     // workgroups, the next tile's loads under the current tile's arithmetic, the SAME partials as one-tile items (the batch invariance holds)
+    // (not with ONE chunk: that launch writes the normalised rows itself, and the per-tile partial form returns before that store)
     const int n_chunks = cdiv(max_kv_len, chunk);
-    const int ptiles = (batch > 16 && batch <= 32 && chunk == 64 && combine) ? g_attn_tiles_per_item : 1;
+    const int ptiles = (batch > 16 && batch <= 32 && chunk == 64 && combine && n_chunks > 1) ? g_attn_tiles_per_item : 1;
     p.n_items = cdiv(n_chunks, ptiles); p.Hq = n_kv_heads; p.group = 1;
     p.scale = scale; p.causal = 0; p.q_row_base = nullptr;
     p.part = (float*)workspace; p.dyn_kv_len = nullptr; p.kv_chunk = chunk * ptiles;
