@@ -5,11 +5,20 @@ import json
 import os
 import types
 
+import numpy as np
 import pytest
 import torch
 from PIL import Image
 
 pytestmark = pytest.mark.gpu
+
+
+def noise_image(size, sigma, seed):
+    """Grey Gaussian noise around 128 (what Image.effect_noise draws), from its own seeded generator: the pixels do not depend on what
+    ran earlier in the process."""
+    w, h = size
+    g = np.random.default_rng(seed).normal(128.0, sigma, (h, w))
+    return Image.fromarray(np.clip(np.rint(g), 0, 255).astype(np.uint8), "L")
 
 CONFIG = {
     "model_type": "omchat_qwen2_5_vl", "hidden_size": 2048, "num_hidden_layers": 2, "num_attention_heads": 16,
@@ -74,7 +83,7 @@ def test_load_prepare_generate_roundtrip(tmp_path, monkeypatch):
     assert model.config.mm_use_region_index_token is True and model.get_vision_tower().is_loaded
 
     img_path = str(tmp_path / "demo.jpg")
-    Image.effect_noise((500, 399), 64).convert("RGB").save(img_path)
+    noise_image((500, 399), 64, seed=1).convert("RGB").save(img_path)
     boxes = [[161.0, 11.0, 292.0, 127.0], [268.0, 61.0, 428.0, 226.0], [12.0, 100.0, 140.0, 227.0]]
     messages = [{"role": "user", "content": [{"type": "image_url", "image_url": {"url": img_path}},
                                              {"type": "text", "text": OD_template.format("orange")}], "bbox_list": boxes}]
@@ -149,7 +158,9 @@ def test_device_preprocessing_is_bit_identical_to_host_path():
 
 def test_two_requests_in_flight_through_the_dropin_model(tmp_path, monkeypatch):
     """FO1ForCausalLM.replica() + sharded_eval.request_workers: three worker threads, each with its own engine replica and HIP
-    stream, generate for 6 requests; every answer equals the sequential one."""
+    stream, generate for 6 requests; every answer equals the sequential one.  Both runs decode through the same route (the 128-slot
+    pool, switched on before the sequential run): cross-route agreement is tests/test_decode_routes_gpu.py's, with an oracle and a
+    margin."""
     from safetensors.torch import save_file
     from test_dropin_surface import ToyTokenizer
     from vlm_fo1 import mm_utils as MU
@@ -168,11 +179,14 @@ def test_two_requests_in_flight_through_the_dropin_model(tmp_path, monkeypatch):
     monkeypatch.setattr(builder, "_load_tokenizer", lambda p: Tok())
     monkeypatch.setattr(MU, "_IM_START_ID", 8190)
     monkeypatch.setattr(MU, "_IM_END_ID", 8191)
+    monkeypatch.setattr(MU, "print", lambda *a, **k: None, raising=False)      # prepare_inputs prints every prompt (as the reference does)
+    monkeypatch.setenv("FO1_DECODE_POOL", "128")
+    monkeypatch.setenv("FO1_INFLIGHT", "3")
     tokenizer, model, procs = builder.load_pretrained_model(str(model_dir), device="cuda")
     paths = []
     for j, size in enumerate([(500, 399), (420, 280), (500, 399)]):
         p = str(tmp_path / f"img{j}.jpg")
-        Image.effect_noise(size, 32 + 16 * j).convert("RGB").save(p)
+        noise_image(size, 32 + 16 * j, seed=10 + j).convert("RGB").save(p)
         paths.append(p)
     boxes = [[161.0, 11.0, 292.0, 127.0], [268.0, 61.0, 428.0, 226.0], [12.0, 100.0, 140.0, 227.0], [30.0, 30.0, 90.0, 200.0]]
     reqs = [(paths[i % 3], boxes[: 2 + i % 3], ["orange", "apple", "cat"][i % 3]) for i in range(6)]
@@ -189,7 +203,9 @@ def test_two_requests_in_flight_through_the_dropin_model(tmp_path, monkeypatch):
                 return out[0, kw["inputs"].shape[1]:].tolist()
         return generate
 
-    sequential = SE.run_sharded(len(reqs), [1.0] * len(reqs), make_generate(model, torch.cuda.current_stream()))
+    single = SE.request_workers(model, make_generate, n=1)      # switches the pool on: the sequential run decodes through it as well
+    assert len(single) == 1 and model.engine._pool_svc is not None
+    sequential = SE.run_sharded(len(reqs), [1.0] * len(reqs), single[0])
     workers = SE.request_workers(model, make_generate, n=3)
     assert len(workers) == 3
     overlapped = SE.run_sharded(len(reqs), [1.0] * len(reqs), workers)
