@@ -34,6 +34,16 @@ def _rows(t: torch.Tensor, name: str):
     return t.data_ptr(), t.stride(0), t.shape[0], t.shape[1]
 
 
+def _out_rows(out: Optional[torch.Tensor], rows: int, cols: int, device) -> torch.Tensor:
+    """A new [rows, cols] bf16 output, or the caller's `out` checked to be such a row-major view (its row stride may be padded)."""
+    if out is None:
+        return torch.empty(rows, cols, dtype=torch.bfloat16, device=device)
+    _chk(out, "out")
+    if tuple(out.shape) != (rows, cols) or out.stride(1) != 1:
+        raise ValueError(f"out: need a row-major [{rows}, {cols}] view, got shape {tuple(out.shape)} strides {out.stride()}")
+    return out
+
+
 def _stream():
     return _L.current_stream_ptr()
 
@@ -995,15 +1005,15 @@ def single_tile_items(segments: Sequence[Sequence[int]], head_dim: int) -> bool:
 
 
 def attention_windows(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, items: torch.Tensor, n_heads: int, head_dim: int, scale: float,
-                      flops: float = 0.0, qk_head_stride: Optional[int] = None) -> torch.Tensor:
+                      flops: float = 0.0, qk_head_stride: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ops.attention (non-causal, q_block 64) for a work list of single-tile items (items.single_tile, see single_tile_items): the pipelined
-    fo1_attention_windows_bf16, the same bits."""
+    fo1_attention_windows_bf16, the same bits.  out: an optional [L, n_heads*head_dim] row-major view (any row stride) to write into."""
     _chk(q, "q"); _chk(k, "k"); _chk(vt, "vt")
     assert items.dtype == torch.int32 and items.is_contiguous() and items.device == q.device and getattr(items, "single_tile", False)
     pq, ldq, L, _ = _rows(q, "q")
     pk, ldk, _, _ = _rows(k, "k")
     pv, ldv, _, _ = _rows(vt, "vt")
-    out = torch.empty(L, n_heads * head_dim, dtype=torch.bfloat16, device=q.device)
+    out = _out_rows(out, L, n_heads * head_dim, q.device)
     hs = head_dim if qk_head_stride is None else int(qk_head_stride)
     rc = _L.load().fo1_attention_windows_bf16(pq, ldq, hs, pk, ldk, hs, pv, ldv, out.data_ptr(), out.stride(0), head_dim, L, items.data_ptr(), items.shape[0],
                                               n_heads, n_heads, head_dim, float(scale), float(flops), _stream())
@@ -1071,14 +1081,14 @@ def window_reverse_add(yw: torch.Tensor, shortcut: torch.Tensor, H: int, W: int,
 WINDOW_ATTENTION_MAX_TOKENS = 160      # fo1_window_attention_bf16: tokens per window the head-dim-32 kernel is built for
 
 
-def window_attention(qkv: torch.Tensor, C: int, n_heads: int, window_tokens: int, scale: float) -> torch.Tensor:
+def window_attention(qkv: torch.Tensor, C: int, n_heads: int, window_tokens: int, scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """qkv [n_windows * window_tokens, 3C] (the q/k/v GEMM's rows of window-partitioned tokens) -> softmax(q k^T * scale) v per window and
     head, [rows, C] (fo1_window_attention_bf16: head dim 32, DaViT's WindowAttention modeling_davit.py:225-282)."""
     _chk(qkv, "qkv")
     p, ld, n, _ = _rows(qkv, "qkv")
     assert C == n_heads * 32 and n % window_tokens == 0 and window_tokens <= WINDOW_ATTENTION_MAX_TOKENS
-    out = torch.empty(n, C, dtype=torch.bfloat16, device=qkv.device)
-    _L.check(_L.load().fo1_window_attention_bf16(p, ld, C, n_heads, window_tokens, n // window_tokens, out.data_ptr(), C, float(scale), _stream()),
+    out = _out_rows(out, n, C, qkv.device)
+    _L.check(_L.load().fo1_window_attention_bf16(p, ld, C, n_heads, window_tokens, n // window_tokens, out.data_ptr(), out.stride(0), float(scale), _stream()),
              "fo1_window_attention_bf16")
     return out
 
@@ -1086,27 +1096,29 @@ def window_attention(qkv: torch.Tensor, C: int, n_heads: int, window_tokens: int
 WINDOW_ATTENTION_MAP_WINDOW = 12       # fo1_window_attention_map_bf16: the window side its token -> pixel arithmetic is built for
 
 
-def window_attention_map(qkv: torch.Tensor, C: int, n_heads: int, window: int, H: int, W: int, batch: int, pad_row: torch.Tensor, scale: float) -> torch.Tensor:
+def window_attention_map(qkv: torch.Tensor, C: int, n_heads: int, window: int, H: int, W: int, batch: int, pad_row: torch.Tensor, scale: float,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Window attention on UN-partitioned rows: qkv [batch * H * W, 3C] = the q/k/v projection of the images' pixels in raster order; the windows'
     tokens are found by arithmetic, tokens outside the image read `pad_row` (the layer's bf16 q/k/v bias = the projection of the reference's zero
     padding, modeling_davit.py:248-251).  -> [batch * H * W, C] in pixel order (fo1_window_attention_map_bf16)."""
     _chk(qkv, "qkv"); _chk(pad_row, "pad_row")
     p, ld, n, _ = _rows(qkv, "qkv")
     assert C == n_heads * 32 and n == batch * H * W and window == WINDOW_ATTENTION_MAP_WINDOW and pad_row.numel() == 3 * C and pad_row.is_contiguous()
-    out = torch.empty(n, C, dtype=torch.bfloat16, device=qkv.device)
-    _L.check(_L.load().fo1_window_attention_map_bf16(p, ld, C, n_heads, window, H, W, batch, pad_row.data_ptr(), out.data_ptr(), C, float(scale), _stream()),
+    out = _out_rows(out, n, C, qkv.device)
+    _L.check(_L.load().fo1_window_attention_map_bf16(p, ld, C, n_heads, window, H, W, batch, pad_row.data_ptr(), out.data_ptr(), out.stride(0), float(scale), _stream()),
              "fo1_window_attention_map_bf16")
     return out
 
 
-def window_attention_map_var(qkv: torch.Tensor, C: int, n_heads: int, window: int, sg: "ImgSegs", pad_row: torch.Tensor, scale: float) -> torch.Tensor:
+def window_attention_map_var(qkv: torch.Tensor, C: int, n_heads: int, window: int, sg: "ImgSegs", pad_row: torch.Tensor, scale: float,
+                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """window_attention_map for images of different sizes (sg = the window-partition geometry table: pixels row0, H, W, -, windows down / across)."""
     _chk(qkv, "qkv"); _chk(pad_row, "pad_row")
     p, ld, n, _ = _rows(qkv, "qkv")
     assert C == n_heads * 32 and n == sg.total_in and window == WINDOW_ATTENTION_MAP_WINDOW and pad_row.numel() == 3 * C and pad_row.is_contiguous()
-    out = torch.empty(n, C, dtype=torch.bfloat16, device=qkv.device)
+    out = _out_rows(out, n, C, qkv.device)
     _L.check(_L.load().fo1_window_attention_map_var_bf16(p, ld, C, n_heads, window, sg.ptr, sg.n, sg.max_out // (window * window), sg.total_in,
-                                                         pad_row.data_ptr(), out.data_ptr(), C, float(scale), _stream()), "fo1_window_attention_map_var_bf16")
+                                                         pad_row.data_ptr(), out.data_ptr(), out.stride(0), float(scale), _stream()), "fo1_window_attention_map_var_bf16")
     return out
 
 
@@ -1471,7 +1483,7 @@ def gather_rows_f32(table: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
 
 # ---- Swin backbone pieces (swin_ops.hip, attention.hip) ------------------------------------------------------------------------
 def attention_window_bias(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, items: torch.Tensor, n_heads: int, head_dim: int, scale: float,
-                          bias: torch.Tensor, ws: int, shift: int, nwy: int, nwx: int, flops: float = 0.0) -> torch.Tensor:
+                          bias: torch.Tensor, ws: int, shift: int, nwy: int, nwx: int, flops: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Swin W-MSA / SW-MSA over consecutive windows of ws*ws tokens (fo1_attention_window_bias_bf16); bias fp32 [heads, ws*ws, ws*ws]."""
     _chk(q, "q"); _chk(k, "k"); _chk(vt, "vt")
     wlen = ws * ws
@@ -1480,7 +1492,7 @@ def attention_window_bias(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, it
     pq, ldq, L, _ = _rows(q, "q")
     pk, ldk, _, _ = _rows(k, "k")
     pv, ldv, _, _ = _rows(vt, "vt")
-    out = torch.empty(L, n_heads * head_dim, dtype=torch.bfloat16, device=q.device)
+    out = _out_rows(out, L, n_heads * head_dim, q.device)
     rc = _L.load().fo1_attention_window_bias_bf16(pq, ldq, head_dim, pk, ldk, head_dim, pv, ldv, out.data_ptr(), out.stride(0), head_dim, items.data_ptr(),
                                                   items.shape[0], getattr(items, "q_block", 64), n_heads, head_dim, float(scale), bias.data_ptr(), wlen, ws,
                                                   shift, nwy, nwx, float(flops), _stream())
