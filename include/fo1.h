@@ -444,6 +444,8 @@ int fo1_attention_decode_bf16(const void* q, const void* kcache, long long k_tok
  *                                  (n_stop == -1: PER-SEQUENCE stop sets — stop_ids is a table int32 [sets][17] = {count, ids[16]} and state[b][6] the
  *                                  row of sequence b: a decode pool mixing requests with different stop rules, round 5)
  *                                  next step's embedding-gather plan
+ *   fo1_argmax_rows_bf16           greedy pick per logits row and nothing else (first index among ties, like fo1_argmax_bf16): the head of a
+ *                                  packed prefill, one launch pair for all its sequences.  scratch: 2 * 128 * B * 4 bytes
  *   fo1_kv_relocate                packed prefill rows -> per-sequence decode slots, all layers in one launch
  * ---------------------------------------------------------------------- */
 int fo1_gemv_batch_bf16(const void* x, int ldx, const void* W, int ldw, const void* bias, const void* residual, int ldr,
@@ -474,6 +476,8 @@ int fo1_gemv_attn_combine_bf16(const float* part, long long part_seq_stride, con
 int fo1_decode_argmax_accept(const void* logits, long long ld_logits, int n_vocab, int B, const int32_t* first_tokens,
                              int32_t* state, int32_t* plan, int32_t* ids_out, int ids_ld, const int32_t* stop_ids,
                              int n_stop, int32_t* done, void* scratch, void* stream);
+int fo1_argmax_rows_bf16(const void* logits, long long ld_logits, int n_vocab, int B, int32_t* out /* [B] */, void* scratch,
+                         void* stream);
 int fo1_kv_relocate(const void* ksrc, void* kdst, long long ks_layer, long long ks_head, long long kd_layer,
                     long long kd_head, const void* vsrc, void* vdst, long long vs_layer, long long vs_row,
                     long long vd_layer, long long vd_row, const int32_t* seqs, int B, int max_len, int n_kv_heads,
@@ -498,6 +502,12 @@ int fo1_kv_relocate(const void* ksrc, void* kdst, long long ks_layer, long long 
  *                        256 x 256 GEMM kernel (fo1_gemm_takes_big_tile) and pos0 / the cache pitches are multiples of 8 rows, mRoPE, the K
  *                        append and V^T ride in its epilogue (fo1_qkv_proj_rope_bf16), as in the Python mirror; otherwise GEMM + fo1_qkv_post_llm_bf16.
  *                        reference: modeling_qwen2_5_vl.py:1014-1095,1126-1242; omchat_qwen2_5_vl.py:143-155
+ *                        Without hidden_out the LAST layer's o-projection and MLP run on the n_seq last rows only (fo1_llm_prefill_tail): in a
+ *                        causal decoder nothing else reads the other rows of that layer — its K / V^T entries are written before.
+ *   fo1_llm_prefill_tail everything after the last layer's attention for the rows the head reads: gathers the n_seq rows of the residual
+ *                        stream and of the attention output, o-projection + residual, RMSNorm, gate/up + SwiGLU, down + residual at
+ *                        M = n_seq (fo1_gemm_bf16 dispatch), final norm, lm_head, one batched greedy pick (fo1_argmax_rows_bf16).
+ *                        reference: modeling_qwen2_5_vl.py:1066-1095 on the rows omchat_qwen2_5_vl.py:143-155 keeps
  *   fo1_llm_decode_step  one token for `batch` sequences (state / plan / stop rule as in the batched decode block above).
  * ---------------------------------------------------------------------- */
 typedef struct fo1_vit_block {   /* bf16 device pointers; Linear weights [out, in] */
@@ -561,6 +571,13 @@ int fo1_llm_prefill(const fo1_llm_weights_t* w, const fo1_kv_cache_t* kv,
                     void* hidden_out /* optional bf16 [rows, hidden]: final residual stream */,
                     void* last_hidden /* bf16 [n_seq, hidden] after the final norm */, void* logits /* bf16 [n_seq, vocab] */,
                     int32_t* next_ids /* [n_seq] */, void* workspace, size_t workspace_bytes, void* stream);
+size_t fo1_llm_prefill_tail_workspace_bytes(const fo1_llm_weights_t* w, int n_seq);
+int fo1_llm_prefill_tail(const fo1_llm_weights_t* w,
+                         const void* x /* bf16 [rows, ldx]: residual stream entering the last layer's o-projection */, int ldx,
+                         const void* att /* bf16 [rows, ld_att]: the last layer's attention output */, int ld_att,
+                         const int32_t* last_plan /* [n_seq][2] = {0, last row of sequence b} */, int n_seq,
+                         void* last_hidden /* bf16 [n_seq, hidden] after the final norm */, void* logits /* bf16 [n_seq, vocab] */,
+                         int32_t* next_ids /* [n_seq] */, void* workspace, size_t workspace_bytes, void* stream);
 size_t fo1_llm_decode_workspace_bytes(const fo1_llm_weights_t* w, int batch, int slot_rows);
 int fo1_llm_decode_step(const fo1_llm_weights_t* w, const fo1_kv_cache_t* slots, const void* rope_cos, const void* rope_sin,
                         int32_t* state, int32_t* plan, int32_t* ids_out, int ids_ld, const int32_t* stop_ids, int n_stop,

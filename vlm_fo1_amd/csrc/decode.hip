@@ -507,6 +507,28 @@ __global__ __launch_bounds__(128) void argmax_rows_accept_kernel(const float* __
     }
 }
 
+// stage 2 of the argmax alone (one workgroup per row): the head of a packed prefill, which has no decode state to advance yet
+__global__ __launch_bounds__(128) void argmax_rows_final_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int np, int* __restrict__ out) {
+    const int b = blockIdx.x;
+    __shared__ float s_v[2];
+    __shared__ int s_i[2];
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    if ((int)threadIdx.x < np) { best = pv[b * np + threadIdx.x]; bi = pi[b * np + threadIdx.x]; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
+    if ((threadIdx.x & 63) == 0) { s_v[threadIdx.x >> 6] = best; s_i[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_v[1] > best || (s_v[1] == best && s_i[1] < bi)) { best = s_v[1]; bi = s_i[1]; }
+        out[b] = bi;
+    }
+}
+
 // ---- KV relocation: packed prefill rows -> per-sequence decode slots ---------------------------------------------------
 // K:  dst[l][h][dst0 + t][:] = src[l][h][src0 + t][:]        (rows of 128 bf16, 16-B pieces)
 // VT: dst[l][c][dst0 + t]    = src[l][c][src0 + t]           (c = kv_head*128 + d; src0, dst0 multiples of 4 -> 8-B pieces)
@@ -633,6 +655,20 @@ int fo1_decode_argmax_accept(const void* logits, long long ld_logits, int n_voca
     }
     FO1_LAUNCH("argmax_accept", 1024.0 * B, argmax_rows_accept_kernel, dim3(B), dim3(128), 0, st, (const float*)pv, (const int*)pi, 128,
                (const int*)first_tokens, (int*)state, (int*)plan, (int*)ids_out, ids_ld, (const int*)stop_ids, n_stop, (int*)done);
+    return FO1_OK;
+}
+
+// Greedy pick for B logits rows, first index among ties (the ids fo1_argmax_bf16 gives row by row), two launches for all rows.
+// scratch: 2 * 128 * B * 4 bytes.
+int fo1_argmax_rows_bf16(const void* logits, long long ld_logits, int n_vocab, int B, int32_t* out, void* scratch, void* stream) {
+    using namespace fo1;
+    FO1_CHECK_ARG(logits && out && scratch && B >= 1 && B <= 65535 && n_vocab > 0 && ld_logits >= n_vocab, "argmax_rows: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    float* pv = (float*)scratch;
+    int* pi = (int*)(pv + 128 * B);
+    FO1_LAUNCH("argmax_rows", (double)B * n_vocab * 2.0, argmax_rows_partial_kernel, dim3(128, B), dim3(256), 0, st, (const uint16_t*)logits, ld_logits,
+               n_vocab, pv, pi);
+    FO1_LAUNCH("argmax_rows_final", 1024.0 * B, argmax_rows_final_kernel, dim3(B), dim3(128), 0, st, (const float*)pv, (const int*)pi, 128, (int*)out);
     return FO1_OK;
 }
 

@@ -14,6 +14,8 @@
 //   fo1_llm_prefill      Qwen2_5_VLModel.forward over the spliced prompt   modeling_qwen2_5_vl.py:1126-1242 (decoder layer
 //                        :1014-1095, attention :738-802) + last-row lm_head / greedy pick (omchat_qwen2_5_vl.py:143-155,
 //                        modeling_qwen2_5_vl.py:1848-1860)
+//   fo1_llm_prefill_tail the second half of the LAST decoder layer (modeling_qwen2_5_vl.py:1066-1095) + head for the rows the head reads, one per
+//                        sequence: nothing else of that layer is read once its K / V^T entries are in the cache (fo1_llm_prefill without hidden_out)
 //   fo1_llm_decode_step  the 1-token fast path of the same code for B sequences
 #include "common.h"
 
@@ -151,8 +153,22 @@ int fo1_vit_forward(const fo1_vit_weights_t* w, const fo1_vit_plan_t* g, const v
 // ---------------------------------------------------------------------------------------------------------------------
 // LLM prefill
 // ---------------------------------------------------------------------------------------------------------------------
+// Scratch of the last-layer tail (fo1_llm_prefill_tail): the n_seq gathered rows and their way through o-projection and MLP
+struct TailBufs { void *att_rows, *x_rows, *xa, *h, *a, *xb, *argmax_sc; };
+
+static void llm_tail_carve(Carver& c, const fo1_llm_weights_t* w, int n_seq, TailBufs* t) {
+    const int d = w->hidden;
+    t->att_rows = c.take(bf16_rows(n_seq, (long long)w->n_heads * w->head_dim));
+    t->x_rows = c.take(bf16_rows(n_seq, d));
+    t->xa = c.take(bf16_rows(n_seq, d));
+    t->h = c.take(bf16_rows(n_seq, d));
+    t->a = c.take(bf16_rows(n_seq, w->intermediate));
+    t->xb = c.take(bf16_rows(n_seq, d));
+    t->argmax_sc = c.take((size_t)2 * 128 * n_seq * 4);
+}
+
 static size_t llm_prefill_layout(const fo1_llm_weights_t* w, int R, int n_seq, void* ws, size_t ws_bytes, void** xa, void** xb, void** h,
-                                 void** qkv, void** att, void** a, void** last_rows, void** argmax_sc, void** gemm_ws) {
+                                 void** qkv, void** att, void** a, TailBufs* tail, void** gemm_ws) {
     Carver c(ws, ws_bytes);
     const int d = w->hidden, qd = (w->n_heads + 2 * w->n_kv_heads) * w->head_dim;
     *xa = c.take(bf16_rows(R, d));
@@ -161,16 +177,63 @@ static size_t llm_prefill_layout(const fo1_llm_weights_t* w, int R, int n_seq, v
     *qkv = c.take(bf16_rows(R, qd));
     *att = c.take(bf16_rows(R, (long long)w->n_heads * w->head_dim));
     *a = c.take(bf16_rows(R, w->intermediate));
-    *last_rows = c.take(bf16_rows(n_seq, d));
-    *argmax_sc = c.take(4096);
+    llm_tail_carve(c, w, n_seq, tail);
     *gemm_ws = c.take(kGemmScratch);
     return c.off;
 }
 
 size_t fo1_llm_prefill_workspace_bytes(const fo1_llm_weights_t* w, int rows, int n_seq) {
     if (!w || rows <= 0 || n_seq <= 0) return 0;
-    void* p[9];
-    return llm_prefill_layout(w, rows, n_seq, nullptr, 0, &p[0], &p[1], &p[2], &p[3], &p[4], &p[5], &p[6], &p[7], &p[8]);
+    void* p[7];
+    TailBufs t;
+    return llm_prefill_layout(w, rows, n_seq, nullptr, 0, &p[0], &p[1], &p[2], &p[3], &p[4], &p[5], &t, &p[6]);
+}
+
+// final RMSNorm of the n_seq last rows, lm_head, one greedy pick for all of them
+static int llm_head(const fo1_llm_weights_t* w, const void* last_rows, int n_seq, void* last_hidden, void* logits, int32_t* next_ids, void* argmax_sc,
+                    void* gws, void* stream) {
+    const int d = w->hidden;
+    FO1_TRY(fo1_rmsnorm_bf16(last_rows, d, w->final_norm, last_hidden, d, n_seq, d, w->rms_eps, stream));
+    FO1_TRY(fo1_gemm_bf16_ws(last_hidden, d, w->lm_head, d, nullptr, nullptr, 0, logits, w->vocab, n_seq, w->vocab, d, 0, 0, gws, kGemmScratch, stream));
+    return fo1_argmax_rows_bf16(logits, w->vocab, w->vocab, n_seq, next_ids, argmax_sc, stream);
+}
+
+// The last layer after its attention, for the n_seq rows the head reads: the launches of a layer's second half at M = n_seq, through the same
+// dispatch as every other product (the process-wide tile / split-K / GEMV pins of the test build apply here too), then the head.
+static int llm_tail(const fo1_llm_weights_t* w, const void* x, int ldx, const void* att, int ld_att, const int32_t* last_plan, int n_seq, void* last_hidden,
+                    void* logits, int32_t* next_ids, const TailBufs& t, void* gws, void* stream) {
+    const int d = w->hidden, qo = w->n_heads * w->head_dim, I = w->intermediate;
+    const fo1_llm_layer_t& L = w->layers[w->n_layers - 1];
+    FO1_TRY(fo1_gather_rows_bf16(att, ld_att, nullptr, 0, nullptr, 0, last_plan, t.att_rows, qo, n_seq, qo, stream));
+    FO1_TRY(fo1_gather_rows_bf16(x, ldx, nullptr, 0, nullptr, 0, last_plan, t.x_rows, d, n_seq, d, stream));
+    FO1_TRY(fo1_gemm_bf16_ws(t.att_rows, qo, L.wo, qo, nullptr, t.x_rows, d, t.xa, d, n_seq, d, qo, 0, 0, gws, kGemmScratch, stream));
+    FO1_TRY(fo1_rmsnorm_bf16(t.xa, d, L.ln2, t.h, d, n_seq, d, w->rms_eps, stream));
+    FO1_TRY(fo1_gemm_bf16_ws(t.h, d, L.wgu, d, nullptr, nullptr, 0, t.a, I, n_seq, 2 * I, d, 3, 0, gws, kGemmScratch, stream));
+    FO1_TRY(fo1_gemm_bf16_ws(t.a, I, L.wdown, I, nullptr, t.xa, d, t.xb, d, n_seq, d, I, 0, 0, gws, kGemmScratch, stream));
+    return llm_head(w, t.xb, n_seq, last_hidden, logits, next_ids, t.argmax_sc, gws, stream);
+}
+
+size_t fo1_llm_prefill_tail_workspace_bytes(const fo1_llm_weights_t* w, int n_seq) {
+    if (!w || n_seq <= 0) return 0;
+    Carver c(nullptr, 0);
+    TailBufs t;
+    llm_tail_carve(c, w, n_seq, &t);
+    c.take(kGemmScratch);
+    return c.off;
+}
+
+int fo1_llm_prefill_tail(const fo1_llm_weights_t* w, const void* x, int ldx, const void* att, int ld_att, const int32_t* last_plan, int n_seq,
+                         void* last_hidden, void* logits, int32_t* next_ids, void* workspace, size_t workspace_bytes, void* stream) {
+    FO1_CHECK_ARG(w && x && att && last_plan && last_hidden && logits && next_ids && w->layers, "llm_prefill_tail: NULL argument");
+    FO1_CHECK_ARG(n_seq > 0 && w->n_layers > 0 && ldx >= w->hidden && ld_att >= w->n_heads * w->head_dim, "llm_prefill_tail: n_seq %d, ldx %d, ld_att %d", n_seq,
+                  ldx, ld_att);
+    const size_t need = fo1_llm_prefill_tail_workspace_bytes(w, n_seq);
+    if (!workspace || workspace_bytes < need) return fo1::set_err(FO1_ERR_WORKSPACE, "llm_prefill_tail: workspace %zu B < required %zu B", workspace_bytes, need);
+    Carver c(workspace, workspace_bytes);
+    TailBufs t;
+    llm_tail_carve(c, w, n_seq, &t);
+    void* gws = c.take(kGemmScratch);
+    return llm_tail(w, x, ldx, att, ld_att, last_plan, n_seq, last_hidden, logits, next_ids, t, gws, stream);
 }
 
 int fo1_llm_prefill(const fo1_llm_weights_t* w, const fo1_kv_cache_t* kv, const void* embeds, int ld_embeds, const void* cos, const void* sin,
@@ -180,8 +243,9 @@ int fo1_llm_prefill(const fo1_llm_weights_t* w, const fo1_kv_cache_t* kv, const 
     FO1_CHECK_ARG(w && kv && embeds && cos && sin && items && last_plan && last_hidden && logits && next_ids && w->layers, "llm_prefill: NULL argument");
     const int R = rows, d = w->hidden, H = w->n_heads, KV = w->n_kv_heads, HD = w->head_dim, I = w->intermediate;
     FO1_CHECK_ARG(R > 0 && n_seq > 0 && pos0 >= 0 && pos0 + R <= kv->capacity, "llm_prefill: rows %d at %d exceed the KV cache (%d rows)", R, pos0, kv->capacity);
-    void *xa, *xb, *h, *qkv, *att, *a, *last_rows, *asc, *gws;
-    const size_t need = llm_prefill_layout(w, R, n_seq, workspace, workspace_bytes, &xa, &xb, &h, &qkv, &att, &a, &last_rows, &asc, &gws);
+    void *xa, *xb, *h, *qkv, *att, *a, *gws;
+    TailBufs tail;
+    const size_t need = llm_prefill_layout(w, R, n_seq, workspace, workspace_bytes, &xa, &xb, &h, &qkv, &att, &a, &tail, &gws);
     if (!workspace || workspace_bytes < need) return fo1::set_err(FO1_ERR_WORKSPACE, "llm_prefill: workspace %zu B < required %zu B", workspace_bytes, need);
     const int qd = (H + 2 * KV) * HD;
     const float scale = (float)(1.0 / sqrt((double)HD));
@@ -208,6 +272,9 @@ int fo1_llm_prefill(const fo1_llm_weights_t* w, const fo1_kv_cache_t* kv, const 
         FO1_TRY(fo1_attention_bf16((const uint16_t*)qkv - (long long)pos0 * qd, qd, HD, kc, HD, kv->k_head_stride, vtc, kv->vt_row_stride,
                                    (uint16_t*)att - (long long)pos0 * H * HD, (long long)H * HD, HD, items, n_items, q_block, H, KV, HD, scale, 1,
                                    nullptr, attn_flops, stream));
+        // the last layer, nobody asked for every row: o-projection and MLP on the rows the head reads (K / V^T of all rows are in the cache by now)
+        if (li + 1 == w->n_layers && !hidden_out)
+            return llm_tail(w, x, ldx, att, H * HD, last_plan, n_seq, last_hidden, logits, next_ids, tail, gws, stream);
         // residual stream: x -> xa (after attention) -> xb (after the MLP; the old x is dead by then, so xb may be what held it)
         FO1_TRY(fo1_gemm_bf16_ws(att, H * HD, L.wo, H * HD, nullptr, x, ldx, xa, d, R, d, H * HD, 0, 0, gws, kGemmScratch, stream));
         FO1_TRY(fo1_rmsnorm_bf16(xa, d, L.ln2, h, d, R, d, w->rms_eps, stream));
@@ -217,13 +284,9 @@ int fo1_llm_prefill(const fo1_llm_weights_t* w, const fo1_kv_cache_t* kv, const 
         x = dst;
         ldx = d;
     }
-    // last-row head: gather each sequence's final row, final RMSNorm, lm_head, greedy pick
-    FO1_TRY(fo1_gather_rows_bf16(x, ldx, nullptr, 0, nullptr, 0, last_plan, last_rows, d, n_seq, d, stream));
-    FO1_TRY(fo1_rmsnorm_bf16(last_rows, d, w->final_norm, last_hidden, d, n_seq, d, w->rms_eps, stream));
-    FO1_TRY(fo1_gemm_bf16_ws(last_hidden, d, w->lm_head, d, nullptr, nullptr, 0, logits, w->vocab, n_seq, w->vocab, d, 0, 0, gws, kGemmScratch, stream));
-    for (int b = 0; b < n_seq; ++b)
-        FO1_TRY(fo1_argmax_bf16((const uint16_t*)logits + (long long)b * w->vocab, w->vocab, next_ids + b, asc, stream));
-    return FO1_OK;
+    // every row was asked for (hidden_out): gather each sequence's final row, final RMSNorm, lm_head, greedy pick
+    FO1_TRY(fo1_gather_rows_bf16(x, ldx, nullptr, 0, nullptr, 0, last_plan, tail.x_rows, d, n_seq, d, stream));
+    return llm_head(w, tail.x_rows, n_seq, last_hidden, logits, next_ids, tail.argmax_sc, gws, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -141,6 +141,9 @@ SIGNATURES = {
     "fo1_llm_prefill_workspace_bytes": (c_size_t, [ctypes.POINTER(LlmWeights), c_int, c_int]),
     "fo1_llm_prefill": (c_int, [ctypes.POINTER(LlmWeights), ctypes.POINTER(KvCache), c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                                 c_int, ctypes.c_double, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fo1_llm_prefill_tail_workspace_bytes": (c_size_t, [ctypes.POINTER(LlmWeights), c_int]),
+    "fo1_llm_prefill_tail": (c_int, [ctypes.POINTER(LlmWeights), c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_size_t, c_void_p]),
     "fo1_llm_decode_workspace_bytes": (c_size_t, [ctypes.POINTER(LlmWeights), c_int, c_int]),
     "fo1_llm_decode_step": (c_int, [ctypes.POINTER(LlmWeights), ctypes.POINTER(KvCache), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                     c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -265,6 +268,7 @@ SIGNATURES = {
                                            c_void_p]),
     "fo1_decode_argmax_accept": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                          c_void_p, c_void_p, c_void_p]),
+    "fo1_argmax_rows_bf16": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "fo1_kv_relocate": (c_int, [c_void_p, c_void_p, c_longlong, c_longlong, c_longlong, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong,
                                 c_longlong, c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "fo1_gather_rows_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,

@@ -95,6 +95,46 @@ def _mrope_tables(pos: torch.Tensor, head_dim: int, theta: float, sections: Sequ
     return cs.to(torch.bfloat16).contiguous(), sn.to(torch.bfloat16).contiguous()
 
 
+def packed_item_rows(seqs, n_heads: int, head_dim: int, n_kv_heads: int):
+    """HOST: the attention work list of a packed pass (plan_batch's `seqs`) -> (rows [[q0, q1, k0, k1]], second key range per row, query block,
+    causal key-query pairs).  One segment per sequence and one per distinct shared prefix, split into query blocks, ordered for the launch."""
+    segs = []                                  # (q0, q1, second range) — one per sequence, one per distinct shared prefix
+    done = set()
+    fl = 0.0
+    for sq in seqs:
+        o, _, Lp, *pre = sq
+        if pre:
+            po, P = pre
+            if (po, P) not in done:
+                done.add((po, P))
+                segs.append((po, po + P, (0, 0)))
+                fl += P * (P + 1) / 2.0
+            segs.append((o, o + Lp, (po, po + P)))
+            fl += Lp * (Lp + 1) / 2.0 + float(Lp) * P
+        else:
+            segs.append((o, o + Lp, (0, 0)))
+            fl += Lp * (Lp + 1) / 2.0
+    blk = ops.pick_q_block([(a, b) for a, b, _ in segs], n_heads, head_dim, n_kv_heads)
+    rows = [[q0, min(q0 + blk, b), a, b] for a, b, _ in segs for q0 in range(a, b, blk)]
+    rng = [list(r2) for a, b, r2 in segs for _ in range(a, b, blk)]
+    order = ops.order_items(rows, blk, True, prefix=rng)           # 32x32 form: longest-processing-time-first over the launch
+    return [rows[i] for i in order], [rng[i] for i in order], blk, fl
+
+
+def last_rows_of(seqs) -> List[int]:
+    """HOST: the packed row of every sequence's last real token (plan_batch's `last` plan names the same rows)."""
+    return [sq[0] + sq[1] - (sq[4] if len(sq) > 3 else 0) - 1 for sq in seqs]
+
+
+def tail_item_rows(rows, rng, needed: Sequence[int]):
+    """HOST: the entries of a work list whose query block [q0, q1) holds a needed row, UNCHANGED (same block, same key range, same second
+    range) and in the list's order: each needed row walks the tiles it walks in the full launch, so its attention output has the same bits.
+    What the last decoder layer runs when only `needed` rows are read after it.  -> (rows, second ranges, causal key-query pairs kept)."""
+    keep = [i for i, (q0, q1, _, _) in enumerate(rows) if any(q0 <= r < q1 for r in needed)]
+    fl = sum((rows[i][1] - rows[i][0]) * ((rows[i][0] + rows[i][1] + 1) / 2.0 - rows[i][2] + max(0, rng[i][1] - rng[i][0])) for i in keep)
+    return [rows[i] for i in keep], [rng[i] for i in keep], fl
+
+
 class QwenLLM:
     def __init__(self, cfg: LLMConfig, state: Dict[str, torch.Tensor], device, lm_head: Optional[torch.Tensor] = None):
         self.cfg = cfg
@@ -264,7 +304,12 @@ class QwenLLM:
 
     # ---- transformer -------------------------------------------------------------------------
     def _forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos0: int, collect: Optional[list] = None,
-                 items: Optional[torch.Tensor] = None, flops: Optional[float] = None, prefix_ranges: Optional[torch.Tensor] = None):
+                 items: Optional[torch.Tensor] = None, flops: Optional[float] = None, prefix_ranges: Optional[torch.Tensor] = None,
+                 tail: Optional[tuple] = None):
+        """-> the residual stream after the last layer [L, d]; or, with `tail` = (gather plan int32 [B, 2] of the rows read after the last layer,
+        reduced work items, their flop count, their second ranges), the head's (last hidden [B, d], logits [B, V], next ids [B]): the last layer
+        then writes K / V^T of every row as always, attends over the reduced list only and leaves o-projection, MLP and head of the B rows to the
+        native tail (fo1_llm_prefill_tail) — no other row of that layer is read by anyone.  `collect` keeps the all-row path."""
         c = self.cfg
         L = x.shape[0]
         H, KV, HD = c.num_heads, c.num_kv_heads, c.head_dim
@@ -281,7 +326,11 @@ class QwenLLM:
         fused = (HD == 128 and pos0 % 8 == 0 and self.capacity % 8 == 0 and ((H + 2 * KV) * HD) % 256 == 0
                  and cos.data_ptr() % 16 == 0 and sin.data_ptr() % 16 == 0 and cos.is_contiguous() and sin.is_contiguous()
                  and ops.qkv_fused_for(L, (H + 2 * KV) * HD, c.hidden_size) and not ops.fp8_routed(self.layers[0]["wqkv"], L))
+        if collect is not None:
+            tail = None
         for li, w in enumerate(self.layers):
+            if tail is not None and li + 1 == len(self.layers):
+                last_plan, items, flops, prefix_ranges = tail
             if fused:
                 # q/k/v projection with mRoPE + K append + V^T in the GEMM's epilogue (ops.qkv_proj_rope mode 0): same bits, one launch less and no
                 # second pass over the [L, 2560] activation
@@ -291,6 +340,9 @@ class QwenLLM:
                 ops.qkv_post_llm(qkv, H, KV, HD, cos, sin, self.kcache[li], self.vtcache[li], pos0)   # mRoPE + K append + V^T, one launch
             att = ops.attention_strided(qkv[:, :H * HD], q_row0=pos0, k=self.kcache[li], vt=self.vtcache[li], items=items,
                                         n_q_heads=H, n_kv_heads=KV, head_dim=HD, scale=scale, causal=True, flops=flops, prefix_ranges=prefix_ranges)
+            if tail is not None and li + 1 == len(self.layers):
+                from . import stage_abi
+                return stage_abi.llm_stage(self).prefill_tail(x, att, last_plan)
             x = ops.gemm(att, w["wo"], residual=x)
             a = ops.norm_linear(x, w["ln2"], c.rms_norm_eps, w["wgu"], act=ops.ACT_SWIGLU16)   # gate/up GEMM, SwiGLU in its epilogue
             x = ops.gemm(a, w["wdown"], residual=x)
@@ -298,18 +350,35 @@ class QwenLLM:
                 collect.append(x)
         return x
 
+    def _item_rows(self, pos0: int, kv_end: int):
+        """HOST: work list of one sequence's rows [pos0, kv_end) against keys [0, kv_end) -> (rows, query block)."""
+        blk = ops.pick_q_block([(pos0, kv_end)], self.cfg.num_heads, self.cfg.head_dim, self.cfg.num_kv_heads)
+        rows = [[q0, min(q0 + blk, kv_end), 0, kv_end] for q0 in range(pos0, kv_end, blk)]
+        return [rows[i] for i in ops.order_items(rows, blk, True)], blk      # 32x32 form: the blocks with the most key tiles first
+
     def _items(self, pos0: int, kv_end: int) -> torch.Tensor:
         key = (pos0, kv_end)
         it = self._item_cache.get(key)
         if it is None:
             # never evict: a captured prefill graph may hold this tensor's pointer (entries are a few hundred bytes each)
-            blk = ops.pick_q_block([(pos0, kv_end)], self.cfg.num_heads, self.cfg.head_dim, self.cfg.num_kv_heads)
-            rows = [[q0, min(q0 + blk, kv_end), 0, kv_end] for q0 in range(pos0, kv_end, blk)]
-            rows = [rows[i] for i in ops.order_items(rows, blk, True)]      # 32x32 form: the blocks with the most key tiles first
+            rows, blk = self._item_rows(pos0, kv_end)
             it = torch.tensor(rows, dtype=torch.int32).to(self.dev)
             it.q_block = blk
             self._item_cache[key] = it
         return it
+
+    def _tail(self, pos0: int, kv_end: int):
+        """The `tail` of _forward for one sequence at rows [pos0, kv_end): its last row, and the one query block of _items that holds it."""
+        key = ("tail", pos0, kv_end)
+        hit = self._item_cache.get(key)
+        if hit is None:
+            rows, blk = self._item_rows(pos0, kv_end)
+            rows, _, fl = tail_item_rows(rows, [[0, 0]] * len(rows), [kv_end - 1])
+            it = torch.tensor(rows, dtype=torch.int32).to(self.dev)
+            it.q_block = blk
+            plan = torch.tensor([[0, kv_end - 1 - pos0]], dtype=torch.int32).to(self.dev)
+            hit = self._item_cache[key] = (plan, it, 4.0 * self.cfg.num_heads * self.cfg.head_dim * fl, None)
+        return hit
 
     def prefill(self, embeds: torch.Tensor, pos: torch.Tensor, rope_delta: int = 0, collect: Optional[list] = None,
                 tables: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
@@ -323,10 +392,10 @@ class QwenLLM:
         else:
             cos, sin = tables
         with ops.workspace_scope(self._ws_owner):
-            x = self._forward(embeds, cos, sin, 0, collect)
+            out = self._forward(embeds, cos, sin, 0, collect, tail=self._tail(0, embeds.shape[0]))
             self.kv_len = embeds.shape[0]
             self.rope_delta = rope_delta
-            return self._head(x)
+            return self._head(out) if collect is not None else out
 
     # ---- several prompts packed into one pass (the reference's batch-aware splice, omchat_qwen2_5_vl.py:380-416) ----
     PACK_ALIGN = 4   # the attention kernel reads V^T in 8-byte (4-key) pieces: every sequence starts at a multiple of 4
@@ -414,31 +483,30 @@ class QwenLLM:
         key = ("packed", tuple(seqs))
         hit = self._item_cache.get(key)
         if hit is None:
-            segs = []                                  # (q0, q1, second range) — one per sequence, one per distinct shared prefix
-            done = set()
-            fl = 0.0
-            for sq in seqs:
-                o, _, Lp, *pre = sq
-                if pre:
-                    po, P = pre
-                    if (po, P) not in done:
-                        done.add((po, P))
-                        segs.append((po, po + P, (0, 0)))
-                        fl += P * (P + 1) / 2.0
-                    segs.append((o, o + Lp, (po, po + P)))
-                    fl += Lp * (Lp + 1) / 2.0 + float(Lp) * P
-                else:
-                    segs.append((o, o + Lp, (0, 0)))
-                    fl += Lp * (Lp + 1) / 2.0
-            blk = ops.pick_q_block([(a, b) for a, b, _ in segs], self.cfg.num_heads, self.cfg.head_dim, self.cfg.num_kv_heads)
-            rows = [[q0, min(q0 + blk, b), a, b] for a, b, _ in segs for q0 in range(a, b, blk)]
-            rng = [list(r2) for a, b, r2 in segs for _ in range(a, b, blk)]
-            order = ops.order_items(rows, blk, True, prefix=rng)           # 32x32 form: longest-processing-time-first over the launch
-            rows, rng = [rows[i] for i in order], [rng[i] for i in order]
+            c = self.cfg
+            rows, rng, blk, fl = packed_item_rows(seqs, c.num_heads, c.head_dim, c.num_kv_heads)
             it = torch.tensor(rows, dtype=torch.int32).to(self.dev)
             it.q_block = blk
             r2 = torch.tensor(rng, dtype=torch.int32).to(self.dev) if any(x[1] > x[0] for x in rng) else None
-            hit = (it, 4.0 * self.cfg.num_heads * self.cfg.head_dim * fl, r2)
+            hit = (it, 4.0 * c.num_heads * c.head_dim * fl, r2)
+            self._item_cache[key] = hit
+        return hit
+
+    def packed_tail_items(self, seqs):
+        """packed_items for the LAST layer of a pass whose head reads each sequence's last real row only: the entries of the full list that
+        hold such a row (tail_item_rows) -> (items, flop count, prefix ranges — given exactly when the full list has them: the same kernel
+        entry runs).  Kept like the full list: a captured graph holds the pointers."""
+        key = ("packed_tail", tuple(seqs))
+        hit = self._item_cache.get(key)
+        if hit is None:
+            c = self.cfg
+            rows, rng, blk, _ = packed_item_rows(seqs, c.num_heads, c.head_dim, c.num_kv_heads)
+            shared = any(x[1] > x[0] for x in rng)
+            rows, rng, fl = tail_item_rows(rows, rng, last_rows_of(seqs))
+            it = torch.tensor(rows, dtype=torch.int32).to(self.dev)
+            it.q_block = blk
+            r2 = torch.tensor(rng, dtype=torch.int32).to(self.dev) if shared else None
+            hit = (it, 4.0 * c.num_heads * c.head_dim * fl, r2)
             self._item_cache[key] = hit
         return hit
 
@@ -446,7 +514,8 @@ class QwenLLM:
                        collect: Optional[list] = None):
         """DEVICE: embeds [R, d] (packed rows of plan_batch), cos/sin [R, hd] device tables, last_plan int32 [B,2] (device).
         K / V^T land at cache positions = packed row indices.  Returns (final-norm last hidden [B, d], logits [B, V], next ids
-        int32 [B])."""
+        int32 [B]).  last_plan names each sequence's last real row (plan_batch's `last`): the last layer computes nothing else past its
+        K / V^T entries unless `collect` asks for every row."""
         c = self.cfg
         items, flops, prefix_ranges = self.packed_items(seqs)
         from . import stage_abi
@@ -456,13 +525,13 @@ class QwenLLM:
             with ops.workspace_scope(self._ws_owner):
                 return stage_abi.llm_stage(self).prefill_packed(embeds, cos, sin, seqs, last_plan)
         with ops.workspace_scope(self._ws_owner):
+            if collect is None:
+                return self._forward(embeds, cos, sin, 0, items=items, flops=flops, prefix_ranges=prefix_ranges,
+                                     tail=(last_plan,) + self.packed_tail_items(seqs))
             x = self._forward(embeds, cos, sin, 0, collect, items=items, flops=flops, prefix_ranges=prefix_ranges)
             last = ops.rmsnorm(ops.gather_rows(last_plan, c.hidden_size, x), self.norm, c.rms_norm_eps)
             logits = ops.gemm(last, self.lm_head)
-            toks = torch.empty(last.shape[0], dtype=torch.int32, device=self.dev)
-            for b in range(last.shape[0]):
-                ops.argmax(logits[b], out=toks[b:b + 1])
-            return last, logits, toks
+            return last, logits, ops.argmax_rows(logits)
 
     def _check_room(self):
         """The device-side decode state indexes the caches blindly: grow them on the host before a step would run past them."""

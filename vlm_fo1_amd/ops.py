@@ -509,6 +509,19 @@ def argmax(row: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tenso
     return out
 
 
+def argmax_rows(logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 [B]: greedy pick of every row of logits [B, V] bf16, first index among ties — the ids argmax() gives row by row, in one launch
+    pair (fo1_argmax_rows_bf16)."""
+    _chk(logits, "logits")
+    pl, ld, B, V = _rows(logits, "logits")
+    if out is None:
+        out = torch.empty(B, dtype=torch.int32, device=logits.device)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == B
+    sc = _workspace("argmax_rows", logits.device, 2 * 128 * B * 4)
+    _L.check(_L.load().fo1_argmax_rows_bf16(pl, ld, V, B, out.data_ptr(), sc.data_ptr(), _stream()), "fo1_argmax_rows_bf16")
+    return out
+
+
 def attention_decode(q: torch.Tensor, kcache: torch.Tensor, vtcache: torch.Tensor, kv_len_dev: torch.Tensor, max_kv_len: int,
                      n_q_heads: int, n_kv_heads: int, head_dim: int, scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One new token (q [1, n_q_heads*head_dim]) against the cache; kv_len_dev = device int32 scalar holding the

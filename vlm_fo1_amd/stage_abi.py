@@ -161,6 +161,25 @@ class LlmStage:
         _lib.check(rc, "fo1_llm_prefill")
         return (last, logits, toks, hidden) if want_hidden else (last, logits, toks)
 
+    def prefill_tail(self, x: torch.Tensor, att: torch.Tensor, last_plan: torch.Tensor):
+        """The last layer after its attention, for the rows `last_plan` names (fo1_llm_prefill_tail): x [R, d] residual stream entering the
+        o-projection, att [R, heads * head_dim] -> (last hidden [B, d], logits [B, V], next ids [B])."""
+        L = _lib.load()
+        c = self.llm.cfg
+        dev = x.device
+        assert x.stride(1) == 1 and att.stride(1) == 1 and x.shape[0] == att.shape[0]
+        assert last_plan.dtype == torch.int32 and last_plan.is_contiguous()
+        B = last_plan.shape[0]
+        last = torch.empty(B, c.hidden_size, dtype=torch.bfloat16, device=dev)
+        logits = torch.empty(B, self.W.vocab, dtype=torch.bfloat16, device=dev)
+        toks = torch.empty(B, dtype=torch.int32, device=dev)
+        need = L.fo1_llm_prefill_tail_workspace_bytes(ctypes.byref(self.W), B)
+        ws = ops._workspace("stage_llm_tail", dev, need)
+        rc = L.fo1_llm_prefill_tail(ctypes.byref(self.W), x.data_ptr(), x.stride(0), att.data_ptr(), att.stride(0), last_plan.data_ptr(), B,
+                                    last.data_ptr(), logits.data_ptr(), toks.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream_ptr())
+        _lib.check(rc, "fo1_llm_prefill_tail")
+        return last, logits, toks
+
     def decode_step(self, dec) -> torch.Tensor:
         """One step of a started BatchDecoder `dec` through fo1_llm_decode_step; returns the logits [B, V]."""
         L = _lib.load()
