@@ -833,14 +833,16 @@ def tile_weight(w: torch.Tensor) -> torch.Tensor:
     return w.view(N // 128, 128, K // 64, 64).permute(0, 2, 1, 3).contiguous()
 
 
-def gemm_wtiled(a: torch.Tensor, w_tiled: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, act: int = ACT_NONE) -> torch.Tensor:
-    """a @ W.T (+ epilogue) with W given as ops.tile_weight(W): the weight-streaming form for <= 128 rows (fo1_gemm_bf16_wtiled)."""
+def gemm_wtiled(a: torch.Tensor, w_tiled: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, act: int = ACT_NONE,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """a @ W.T (+ epilogue) with W given as ops.tile_weight(W): the weight-streaming form for <= 128 rows (fo1_gemm_bf16_wtiled).  out: a
+    row-major [M, N (N / 2 with SwiGLU)] bf16 view to write into (its row stride may be padded)."""
     _need_ab("fo1_gemm_bf16_wtiled")
     _chk(a, "a"); _chk(w_tiled, "w_tiled")
     pa, lda, M, K = _rows(a, "a")
     assert w_tiled.dim() == 4 and w_tiled.shape[2:] == (128, 64) and w_tiled.is_contiguous() and w_tiled.shape[1] * 64 == K
     N = w_tiled.shape[0] * 128
-    out = torch.empty(M, N // 2 if act == ACT_SWIGLU16 else N, dtype=torch.bfloat16, device=a.device)
+    out = _out_rows(out, M, N // 2 if act == ACT_SWIGLU16 else N, a.device)
     po, ldc, _, _ = _rows(out, "out")
     pr, ldr = (None, 0)
     if residual is not None:
