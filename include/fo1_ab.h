@@ -30,8 +30,12 @@ int fo1_hfre_set_pixel_budget(int pixels);
 int fo1_hfre_set_tuning(int unroll, int chunk, int budget, int grid);
 
 /* ---- GEMM ---- */
-/* staging 0 auto / 1 register-staged / 2 LDS-DMA two-stage / 3, 4, 6 LDS-DMA ring of that depth (counted vmcnt; 6 only for the 64x64 tile,
- * else 4); tile 0 auto / 1 128x128 / 2 64x128 / 3 64x64 / 4 128x256 (8 waves) / 5 256x256; split-K 0 auto / n forced.
+/* staging 0 auto / 1 register-staged / 2 LDS-DMA two-stage / 3, 4, 6 LDS-DMA ring of that depth (counted vmcnt; 6 only for the 64x64 and
+ * 128x64 tiles, 5 on the 128x96 tile, else 4) / 5 the 128x96 tile's 5-deep ring (accepted with tile 6 only);
+ * tile 0 auto / 1 128x128 / 2 64x128 / 3 64x64 / 4 128x256 (8 waves) / 5 256x256 / 6 128x96 ring, waves 4 x 1 (the decode pool's SwiGLU
+ * gate/up product; 3 deep unless the staging asks for more) / 7 128x64 ring (6 deep under split-K, else 3, unless the staging says);
+ * 6 and 7 fall back to 128x128 for batched, fp32-output or register-staged (K % 64 != 0) products;
+ * split-K 0 auto / n forced.
  * (2, 1) + splitk 1 + gemv 0 is the determinism pin of the parity tests. */
 int fo1_gemm_set_variant(int staging, int tile);
 int fo1_gemm_set_splitk(int splits);

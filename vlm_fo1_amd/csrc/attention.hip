@@ -1321,11 +1321,7 @@ __global__ __launch_bounds__(256) void attn_decode_ws_kernel(const AttnDecParams
 
 static int launch_attn_decode_ws(AttnDecParams& p, int max_kv_len, int batch, hipStream_t st) {
     constexpr int smem = 4 * (64 * (128 + 8) + 128 * (64 + 4)) * 2;
-    static bool attr_done = false;
-    if (!attr_done) {
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)attn_decode_ws_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_done = true;
-    }
+    FO1_DYNAMIC_LDS_ONCE(smem, attn_decode_ws_kernel);
     FO1_LAUNCH("attn_decode_ws", (double)batch * max_kv_len * p.n_kv_heads * 128 * 4.0, attn_decode_ws_kernel, dim3(1, p.n_kv_heads, batch), dim3(256), smem, st, p);
     return FO1_OK;
 }
@@ -1338,11 +1334,7 @@ template <int HD, int HPW>
 static int launch_attn32(const AttnParams& p, hipStream_t st, double flops) {
     constexpr int LDK = HD + 8, LDV = 64 + 8, HDV = (HD + 31) / 32 * 32;
     constexpr int smem = 2 * (64 * LDK + HDV * LDV) * 2;
-    static bool attr_done = false;      // > 64 KB of dynamic LDS needs the attribute (first call of an instantiation; never inside a capture: passes run eagerly first)
-    if (!attr_done) {
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)attn_fwd32_kernel<HD, HPW>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_done = true;
-    }
+    FO1_DYNAMIC_LDS_ONCE(smem, attn_fwd32_kernel<HD, HPW>);      // > 64 KB of dynamic LDS (first call of an instantiation; never inside a capture: passes run eagerly first)
     char pname[48];
     const char* name = "attn_fwd32";
     if (profile_enabled() && g_gemv_profile_shapes) {

@@ -69,6 +69,17 @@ __device__ __forceinline__ float fo1_gelu_erf(float v) {
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// A launch with more than 64 KB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize on that kernel instantiation.  Set once per
+// process: the function-local static is initialised by the first call (host threads that make it together — engine replicas, the decode
+// pool's thread, the prefetch helpers — see one hipFuncSetAttribute and all of them its result; later launches read a guard byte, no
+// lock).  The first call of an instantiation is never inside a stream capture: passes run eagerly first.
+template <auto KERNEL, int BYTES>
+inline hipError_t dynamic_lds_once() {
+    static const hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES);
+    return e;
+}
+#define FO1_DYNAMIC_LDS_ONCE(bytes, ...) FO1_CHECK_HIP((fo1::dynamic_lds_once<__VA_ARGS__, bytes>()))   // (kernel last: its template arguments carry commas)
+
 // ---- optional per-kernel timing (fo1_profile_*) ---------------------------------------
 // When enabled every FO1_LAUNCH goes through hipExtLaunchKernelGGL with a start/stop event pair, which the runtime fills
 // from the dispatch packet's own begin/end timestamps (the clocks rocprofv3's kernel trace reads), so a row's time is

@@ -332,11 +332,7 @@ __global__ __launch_bounds__(256) void gemv_batch_kernel(const GemvBParams p) {
 template <int MM, int MODE, bool KS, int RPL>
 static int launch_gemv_b(const GemvBParams& p, const char* name, int n_units, hipStream_t st) {
     const size_t smem = (size_t)MM * p.kp_chunks * 16;
-    static bool attr = false;
-    if (!attr) {
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemv_batch_kernel<MM, MODE, KS, RPL>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        attr = true;
-    }
+    FO1_DYNAMIC_LDS_ONCE(150 * 1024, gemv_batch_kernel<MM, MODE, KS, RPL>);
     // persistent workgroups (grid-stride over work items): x is staged / normalised once per workgroup; <= 4 workgroups per CU
     const int n_super = cdiv(n_units, RPL);
     int grid = KS ? n_super : cdiv(n_super, 4);

@@ -526,11 +526,7 @@ static int launch_gemv_mfma_mp(const GemvBParams& p, int n_units, int nsteps, co
     const size_t smem = (MM == 32 && !MP) ? (size_t)MM * xpitch + 128
                                           : xrows * xpitch + (size_t)GM_NW * NB * 2048 + (size_t)2 * ng * GM_NW * NB * 1024 + 128;
     if (smem > 156 * 1024) return set_err(FO1_ERR_ARG, "gemv_batch: %zu B of LDS for M=%d K=%d (internal dispatch error)", smem, p.M, p.K);
-    static bool attr = false;
-    if (!attr) {
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemv_mfma_kernel<MM, MODE, NB, MP, HALF, R8>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-        attr = true;
-    }
+    FO1_DYNAMIC_LDS_ONCE(156 * 1024, gemv_mfma_kernel<MM, MODE, NB, MP, HALF, R8>);
     // persistent workgroups, one per CU (x is staged / normalised once per workgroup when K fits one piece)
     const int grid = n_units < 256 ? n_units : 256;
     FO1_LAUNCH(name, (double)p.N * p.K * 2.0, (gemv_mfma_kernel<MM, MODE, NB, MP, HALF, R8>), dim3(grid), dim3(GM_NT), smem, st, p, n_units, nsteps);

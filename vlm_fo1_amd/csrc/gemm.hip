@@ -23,6 +23,7 @@
 #include "ab.h"
 
 #include <type_traits>
+#include <utility>
 
 namespace fo1 {
 
@@ -34,24 +35,24 @@ typedef __attribute__((ext_vector_type(8))) int v8i32;
 typedef __attribute__((ext_vector_type(4))) unsigned int v4u32;
 
 struct GemmParams {
-    const uint16_t* A;
-    const uint16_t* W;
-    const uint16_t* bias;
-    const uint16_t* res;
-    uint16_t* C;
-    float* C32;
-    int M, N, K, lda, ldw, ldc, ldr;
-    int act;
-    int tiles_m, tiles_n;
-    long long sA, sW, sC, sR;  // batch strides (elements), blockIdx.y = batch
-    int splits, kper;          // split-K: blockIdx.z = split, kper k-tiles (of 64) per split
-    float* part;               // fp32 partials [splits][M][N] when splits > 1
-    int stages;                // LDS ring depth: 2 = two-stage kernel, 3/4/6 = counted-vmcnt ring
-    int debug;                 // ablation (bench only): 1 skip global loads after tile 0, 2 skip MFMA, 4 skip LDS reads + MFMA
-    int coal;                  // 256x256 kernels: epilogue staged through LDS and written as whole 128-byte row segments (16-B stores)
+    const uint16_t* A = nullptr;
+    const uint16_t* W = nullptr;
+    const uint16_t* bias = nullptr;
+    const uint16_t* res = nullptr;
+    uint16_t* C = nullptr;
+    float* C32 = nullptr;
+    int M = 0, N = 0, K = 0, lda = 0, ldw = 0, ldc = 0, ldr = 0;
+    int act = 0;
+    int tiles_m = 0, tiles_n = 0;      // set by the launcher, from its tile
+    long long sA = 0, sW = 0, sC = 0, sR = 0;  // batch strides (elements), blockIdx.y = batch
+    int splits = 1, kper = 0;  // split-K: blockIdx.z = split, kper k-tiles (of 64) per split
+    float* part = nullptr;     // fp32 partials [splits][M][N] when splits > 1
+    int stages = 2;            // LDS ring depth: 2 = two-stage kernel, 3/4/6 = counted-vmcnt ring
+    int debug = 0;             // ablation (bench only): 1 skip global loads after tile 0, 2 skip MFMA, 4 skip LDS reads + MFMA
+    int coal = 0;              // 256x256 kernels: epilogue staged through LDS and written as whole 128-byte row segments (16-B stores)
     // fp8 (fo1_gemm_fp8): A and W are OCP e4m3 bytes, C = (A W^T) * scale_m[m] * scale_n[n] before the epilogue
-    const float* scale_m;
-    const float* scale_n;
+    const float* scale_m = nullptr;
+    const float* scale_n = nullptr;
     // ring kernels with BN = 128 (fo1_gemm_bf16_wtiled): W is a copy pre-tiled as [N / 128][K / 64][128 rows][64] — a K tile of a column tile is ONE
     // contiguous 16 KB block (the decode pool's weight streams: profiles/r04_hbm_stream_patterns.jsonl)
     int w_tiled = 0;
@@ -74,6 +75,14 @@ struct GemmParams {
     const uint32_t* a_rows = nullptr;
     uint32_t conv_row_bytes = 0, conv_cin_bytes = 0;
     int conv_lgc = 0;
+
+    // What every entry point states: operands, shape, leading dimensions, activation; one unsplit run over all K tiles (kper: one more
+    // than there are).  Everything else keeps its default until the entry point or the launcher says otherwise.
+    GemmParams(const void* A_, int lda_, const void* W_, int ldw_, const void* bias_, const void* res_, int ldr_, void* C_, int ldc_, bool out_f32,
+               int M_, int N_, int K_, int act_)
+        : A((const uint16_t*)A_), W((const uint16_t*)W_), bias((const uint16_t*)bias_), res((const uint16_t*)res_),
+          C(out_f32 ? nullptr : (uint16_t*)C_), C32(out_f32 ? (float*)C_ : nullptr), M(M_), N(N_), K(K_), lda(lda_), ldw(ldw_), ldc(ldc_),
+          ldr(ldr_), act(act_), kper(K_ / 64 + 1) {}
 };
 
 enum { ACT_NONE = 0, ACT_GELU = 1, ACT_SILU = 2, ACT_SWIGLU16 = 3, ACT_RELU = 5 };   // (4 = the split-K partial epilogue of the 256x256 kernels)
@@ -1356,8 +1365,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bt_p8_kernel(const GemmParams p) 
 
 #endif   // FO1_ENABLE_AB (gemm_bt_p8_kernel)
 
-FO1_AB_VAR g_gemm_variant = 0;  // 0 auto, 1 reg, 2 glds two-stage, 3/4/6 glds ring of that depth
-FO1_AB_VAR g_gemm_tile = 0;     // 0 auto, 1 = 128x128, 2 = 64x128, 3 = 64x64, 4 = 128x256 (8 waves), 5 = 256x256 ping-pong
+FO1_AB_VAR g_gemm_variant = 0;  // 0 auto, 1 reg, 2 glds two-stage, 3/4/6 glds ring of that depth (ring_depth), 5 = the <128, 96> tile's deepest ring (tile 6 only)
+FO1_AB_VAR g_gemm_tile = 0;     // 0 auto, 1 = 128x128, 2 = 64x128, 3 = 64x64, 4 = 128x256 (8 waves), 5 = 256x256 two-phase, 6 = 128x96 ring (waves 4 x 1), 7 = 128x64 ring
 FO1_AB_VAR g_gemm_splitk = 0;   // 0 auto, n >= 1 forced
 static int g_gemm_profile_shapes = 0;   // profile-row naming (fo1_gemm_profile_shapes, include/fo1_ab.h)
 FO1_AB_VAR g_gemm_debug = 0;
@@ -1371,32 +1380,45 @@ extern int g_gemv_profile_shapes;
 int gemv_dispatch(const void* A, int lda, const void* W, int ldw, const void* bias, const void* residual, int ldr, void* C, int ldc,
                   int M, int N, int K, int act, hipStream_t st, const void* norm_w, float norm_eps);
 
+// The row of a GEMM launch in the profile.  FO1_LAUNCH reads it only while the profile is on; while it is off nothing is formatted.
+//   default: the kernel's own name, one row per kernel template, so the rows map 1:1 onto rocprofv3's kernel names — `kernel` as it stands,
+//            or, for a ring kernel (ring > 0: the depth the row states), kernel<BM,BN,ring>;
+//   fo1_gemm_profile_shapes: "gemm MxNxK tBMxBN" + tail (" s<splits>", " s<splits> r<ring>", " qkv<mode>", " conv"; "gemm_fp8 ..." for fp8
+//            operands); tail == nullptr: a row that never carries the shape.
+// tests/test_gemm_routes_gpu.py and scripts/{make_profiles_readme, check_profile_agreement, pmc_summary}.py key on these strings.
+static const char* gemm_row(char (&buf)[64], const char* kernel, int ring, const GemmParams& p, int BM, int BN, const char* tail, int t0 = 0, int t1 = 0) {
+    if (!profile_enabled()) return kernel;
+    if (g_gemm_profile_shapes && tail) {
+        const int n = snprintf(buf, sizeof buf, "%s %dx%dx%d t%dx%d", p.scale_m ? "gemm_fp8" : "gemm", p.M, p.N, p.K, BM, BN);
+        snprintf(buf + n, sizeof buf - n, tail, t0, t1);
+        return buf;
+    }
+    if (ring == 0) return kernel;
+    snprintf(buf, sizeof buf, "%s<%d,%d,%d>", kernel, BM, BN, ring);
+    return buf;
+}
+
+// Sum of the split-K planes + epilogue (every kernel form that writes planes, unless the caller asked for the planes themselves)
+static int launch_splitk_reduce(const GemmParams& p, hipStream_t st) {
+    const long long total = (long long)p.M * (p.N / 4);
+    const int rg = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    FO1_LAUNCH("gemm_splitk_reduce", (double)p.M * p.N * 4.0 * p.splits, gemm_splitk_reduce_kernel, dim3(rg), dim3(256), 0, st, p);
+    return FO1_OK;
+}
+
 // 128 x 256 tile, 8 waves (2 x 4): halves the L2->LDS traffic of the 64 x 128 tile for wide-N GEMMs
-template <int BM, int BN>
 static int launch_gemm_wide(GemmParams& p, int batch, hipStream_t st, bool reduce = true) {
+    constexpr int BM = 128, BN = 256;
     p.tiles_m = cdiv(p.M, BM);
     p.tiles_n = cdiv(p.N, BN);
     const dim3 grid(p.tiles_m * p.tiles_n, batch, p.splits);
     const double flops = 2.0 * p.M * (double)p.N * p.K * batch;
-    char pname[48];
-    const char* name = BM == 128 ? "gemm_bt_glds<128,256>" : "gemm_bt_glds<256,256>";
-    if (profile_enabled() && g_gemm_profile_shapes) {
-        snprintf(pname, sizeof pname, "gemm %dx%dx%d t%dx%d s%d", p.M, p.N, p.K, BM, BN, p.splits);
-        name = pname;
-    }
+    char buf[64];
+    const char* name = gemm_row(buf, "gemm_bt_glds<128,256>", 0, p, BM, BN, " s%d", p.splits);
     constexpr int smem = 2 * (BM + BN) * 128;
-    static bool attr_done = false;
-    if (!attr_done) {
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_glds_kernel<BM, BN, 2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_done = true;
-    }
+    FO1_DYNAMIC_LDS_ONCE(smem, gemm_bt_glds_kernel<BM, BN, 2, 4>);
     FO1_LAUNCH(name, flops, (gemm_bt_glds_kernel<BM, BN, 2, 4>), grid, dim3(512), smem, st, p);
-    if (p.splits > 1 && reduce) {
-        const long long total = (long long)p.M * (p.N / 4);
-        const int rg = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-        FO1_LAUNCH("gemm_splitk_reduce", (double)p.M * p.N * 4.0 * p.splits, gemm_splitk_reduce_kernel, dim3(rg), dim3(256), 0, st, p);
-    }
-    return FO1_OK;
+    return p.splits > 1 && reduce ? launch_splitk_reduce(p, st) : FO1_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1995,141 +2017,108 @@ FO1_AB_VAR g_gemm_coal = 1;        // 256x256 kernels: LDS-staged coalesced epil
 FO1_AB_VAR g_gemm_nt_store = 0;    // 256x256 kernels: non-temporal stores in the coalesced epilogue (A/B)
 FO1_AB_VAR g_gemm_big_sched = 1;   // 256x256 kernel schedule: 0 = four phases per K tile (p8), 1 = two fat phases with DMA issued between MFMAs (p4, default: +3..10 % measured, profiles/r02_gemm_bench_p8_v2.log)
 
-// 256 x 256 ping-pong kernel (gemm_bt_p8_kernel)
-static int launch_gemm_p8(GemmParams& p, int batch, hipStream_t st) {
+// The 256 x 256 kernels (512 threads, the same LDS image).  One struct per family: ids is THE list of its instantiations (the template argument
+// that varies: the epilogue, or the ablation mask), kernel<ID>() the instantiation, name its profile row, smem its dynamic LDS.  launch_big
+// takes the attribute, the row and the launch from here, so an instantiation added to ids is complete.
+// Epilogues: 0..3 = act (none, GELU, SiLU, interleaved SwiGLU), 4 = split-K partial planes, 6 / 7 = fused q/k/v + rotary (LLM / ViT).
+constexpr int kBigSmem = 2 * 4 * 16384;
+struct BigP4 {
+    using ids = std::integer_sequence<int, 0, 1, 2, 3, 4>;
+    template <int EPI> static constexpr auto kernel() { return gemm_bt_p4_kernel<EPI>; }
+    static constexpr const char* name = "gemm_bt_p4<256,256>";
+    static constexpr int smem = kBigSmem;
+};
+struct BigP4Qkv : BigP4 {
+    using ids = std::integer_sequence<int, 6, 7>;
+};
+struct BigP4Fp8 {
+    using ids = std::integer_sequence<int, 0, 1, 2, 3>;
+    template <int EPI> static constexpr auto kernel() { return gemm_bt_p4_kernel<EPI, true>; }
+    static constexpr const char* name = "gemm_fp8_p4<256,256>";
+    static constexpr int smem = kBigSmem;
+};
+struct BigP4Conv {
+    using ids = std::integer_sequence<int, 0, 1>;
+    template <int EPI> static constexpr auto kernel() { return gemm_bt_p4_kernel<EPI, false, 0, true>; }
+    static constexpr const char* name = "gemm_bt_p4<256,256>";
+    static constexpr int smem = kBigSmem;
+};
+#ifdef FO1_ENABLE_AB
+struct BigP8 {
+    using ids = std::integer_sequence<int, 0, 1, 2, 3, 4>;
+    template <int EPI> static constexpr auto kernel() { return gemm_bt_p8_kernel<EPI>; }
+    static constexpr const char* name = "gemm_bt_p8<256,256>";
+    static constexpr int smem = kBigSmem;
+};
+struct BigP4p {      // persistent form: 256 workgroups (one per CU, a multiple of 8: every workgroup stays in its XCD's run of tiles)
+    using ids = std::integer_sequence<int, 0, 1, 2, 3>;
+    template <int EPI> static constexpr auto kernel() { return gemm_bt_p4p_kernel<EPI>; }
+    static constexpr const char* name = "gemm_bt_p4p<256,256>";
+    static constexpr int smem = kBigSmem + 8 * 4096;
+};
+struct BigP4Ablated {      // main-loop ablations of epilogue 0 (debug bits 6-12 = ABL), timing only
+    using ids = std::integer_sequence<int, 1, 2, 4, 8, 16, 24, 32, 64>;
+    template <int ABL> static constexpr auto kernel() { return gemm_bt_p4_kernel<0, false, ABL>; }
+    static constexpr const char* name = "gemm_bt_p4_ablated";
+    static constexpr int smem = kBigSmem;
+};
+#endif
+
+template <class F, int ID>
+static int launch_big_id(const GemmParams& p, const char* row, double flops, dim3 grid, hipStream_t st) {
+    FO1_DYNAMIC_LDS_ONCE(F::smem, F::template kernel<ID>());
+    FO1_LAUNCH(row, flops, F::template kernel<ID>(), grid, dim3(512), F::smem, st, p);
+    return FO1_OK;
+}
+
+// Launches family F's instantiation `id` on p's 256 x 256 tiles; tail: see gemm_row.  grid_x > 0: that many (persistent) workgroups.
+template <class F, int... ID>
+static int launch_big(std::integer_sequence<int, ID...>, int id, GemmParams& p, int batch, hipStream_t st, const char* tail, int t0 = 0, int grid_x = 0) {
     p.tiles_m = cdiv(p.M, 256);
     p.tiles_n = cdiv(p.N, 256);
-    if (g_gemm_group_m > 0) p.gm = g_gemm_group_m;
-    const dim3 grid(p.tiles_m * p.tiles_n, batch, p.splits);
+    const dim3 grid = grid_x > 0 ? dim3(grid_x, 1, 1) : dim3(p.tiles_m * p.tiles_n, batch, p.splits);
     const double flops = 2.0 * p.M * (double)p.N * p.K * batch;
-    char pname[48];
-    const char* name = "gemm_bt_p8<256,256>";
-    if (profile_enabled() && g_gemm_profile_shapes) {
-        snprintf(pname, sizeof pname, "gemm %dx%dx%d t256x256 s%d", p.M, p.N, p.K, p.splits);
-        name = pname;
-    }
-    constexpr int smem = 2 * 4 * 16384;
-    {
-        const int nc = p.act == ACT_SWIGLU16 ? p.N / 2 : p.N;
-        p.coal = g_gemm_coal && nc % 8 == 0 && p.ldc % 8 == 0 && ((uintptr_t)p.C & 15) == 0 && p.sC % 8 == 0 &&
-                 (p.res == nullptr || (p.ldr % 8 == 0 && ((uintptr_t)p.res & 15) == 0 && p.sR % 8 == 0));
-        if (g_gemm_nt_store != 0 && p.coal) p.coal = 2;
-    }
+    char buf[64];
+    const char* row = gemm_row(buf, F::name, 0, p, 256, 256, tail, t0);
+    int rc = FO1_OK;
+    if (((id == ID && ((rc = launch_big_id<F, ID>(p, row, flops, grid, st)), true)) || ...)) return rc;
+    return set_err(FO1_ERR_ARG, "gemm: %s has no instantiation %d", F::name, id);
+}
+template <class F>
+static int launch_big(int id, GemmParams& p, int batch, hipStream_t st, const char* tail, int t0 = 0, int grid_x = 0) {
+    return launch_big<F>(typename F::ids{}, id, p, batch, st, tail, t0, grid_x);
+}
+
+// THE rule for the LDS-staged coalesced epilogue of the 256 x 256 kernels: whole 16-byte stores need 8-element alignment of everything the
+// epilogue addresses (the batch strides included: zero where there is no batch)
+static int coal_epilogue(const GemmParams& p) {
+    const int nc = p.act == ACT_SWIGLU16 ? p.N / 2 : p.N;
+    return g_gemm_coal && nc % 8 == 0 && p.ldc % 8 == 0 && ((uintptr_t)p.C & 15) == 0 && p.sC % 8 == 0 &&
+           (p.res == nullptr || (p.ldr % 8 == 0 && ((uintptr_t)p.res & 15) == 0 && p.sR % 8 == 0));
+}
+
+// 256 x 256 kernel of gemm_dispatch: the two-phase kernel; in the test / bench build also its persistent, ablated and four-phase (p8) forms
+static int launch_gemm_p8(GemmParams& p, int batch, hipStream_t st) {
+    if (g_gemm_group_m > 0) p.gm = g_gemm_group_m;
+    p.coal = coal_epilogue(p);
+    if (g_gemm_nt_store != 0 && p.coal) p.coal = 2;
     const int epi = p.splits > 1 ? 4 : p.act;
+    int rc;
 #ifdef FO1_ENABLE_AB
     if (p.debug & 32) {       // workgroup timeline: the stamps go to the (otherwise unused) split-K partial pointer
         if (p.splits == 1 && g_gemm_stamp_buf && p.coal) p.part = (float*)g_gemm_stamp_buf;
         else p.debug &= ~32;
     }
-    static bool attr_done = false;
-    if (!attr_done) {
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p8_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p8_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p8_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p8_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p8_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_done = true;
-    }
-    const int n_tiles = p.tiles_m * p.tiles_n, nk64 = p.K / 64;
-    if (g_gemm_big_sched == 1 && g_gemm_persist && p.splits == 1 && batch == 1 && p.coal && n_tiles > 256 && nk64 >= 2 && nk64 % 2 == 0) {
-        // persistent form: 256 workgroups (one per CU, a multiple of 8: every workgroup stays in its XCD's run of tiles)
-        constexpr int smem_p = 2 * 4 * 16384 + 8 * 4096;
-        static bool attrp = false;
-        if (!attrp) {
-            FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p4p_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_p));
-            FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p4p_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_p));
-            FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p4p_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_p));
-            FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p4p_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_p));
-            attrp = true;
-        }
-        const char* np = (profile_enabled() && g_gemm_profile_shapes) ? name : "gemm_bt_p4p<256,256>";
-        const dim3 gp(256, 1, 1);
-        if (epi == 0) FO1_LAUNCH(np, flops, gemm_bt_p4p_kernel<0>, gp, dim3(512), smem_p, st, p);
-        else if (epi == 1) FO1_LAUNCH(np, flops, gemm_bt_p4p_kernel<1>, gp, dim3(512), smem_p, st, p);
-        else if (epi == 2) FO1_LAUNCH(np, flops, gemm_bt_p4p_kernel<2>, gp, dim3(512), smem_p, st, p);
-        else FO1_LAUNCH(np, flops, gemm_bt_p4p_kernel<3>, gp, dim3(512), smem_p, st, p);
-        return FO1_OK;
-    }
+    const int n_tiles = cdiv(p.M, 256) * cdiv(p.N, 256), nk64 = p.K / 64;
+    if (g_gemm_big_sched == 1 && g_gemm_persist && p.splits == 1 && batch == 1 && p.coal && n_tiles > 256 && nk64 >= 2 && nk64 % 2 == 0)
+        return launch_big<BigP4p>(epi, p, batch, st, " s%d", p.splits, 256);
+    if (g_gemm_big_sched == 1 && epi == 0 && (p.debug >> 6) & 127) return launch_big<BigP4Ablated>((p.debug >> 6) & 127, p, batch, st, nullptr);
+    if (g_gemm_big_sched != 1) rc = launch_big<BigP8>(epi, p, batch, st, " s%d", p.splits);
+    else
 #endif
-#ifdef FO1_ENABLE_AB
-    if (g_gemm_big_sched == 1 && epi == 0 && (p.debug >> 6) & 127) {      // main-loop ablations (debug bits 6-8 = ABL), timing only
-        const int abl = (p.debug >> 6) & 127;
-#define FO1_ABL_CASE(V)                                                                                                                   \
-    case V: {                                                                                                                             \
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p4_kernel<0, false, V>, hipFuncAttributeMaxDynamicSharedMemorySize, smem)); \
-        FO1_LAUNCH("gemm_bt_p4_ablated", flops, (gemm_bt_p4_kernel<0, false, V>), grid, dim3(512), smem, st, p);                          \
-    } break;
-        switch (abl) {
-            FO1_ABL_CASE(1) FO1_ABL_CASE(2) FO1_ABL_CASE(4) FO1_ABL_CASE(8) FO1_ABL_CASE(16) FO1_ABL_CASE(24) FO1_ABL_CASE(32) FO1_ABL_CASE(64)
-            default: return set_err(FO1_ERR_ARG, "gemm: no such ablation %d", abl);
-        }
-#undef FO1_ABL_CASE
-        return FO1_OK;
-    }
-#endif
-    if (g_gemm_big_sched == 1) {
-        static bool attr4 = false;
-        if (!attr4) {
-            FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p4_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p4_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p4_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p4_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p4_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            attr4 = true;
-        }
-        const char* n4 = (profile_enabled() && g_gemm_profile_shapes) ? name : "gemm_bt_p4<256,256>";
-        if (epi == 0) FO1_LAUNCH(n4, flops, gemm_bt_p4_kernel<0>, grid, dim3(512), smem, st, p);
-        else if (epi == 1) FO1_LAUNCH(n4, flops, gemm_bt_p4_kernel<1>, grid, dim3(512), smem, st, p);
-        else if (epi == 2) FO1_LAUNCH(n4, flops, gemm_bt_p4_kernel<2>, grid, dim3(512), smem, st, p);
-        else if (epi == 3) FO1_LAUNCH(n4, flops, gemm_bt_p4_kernel<3>, grid, dim3(512), smem, st, p);
-        else FO1_LAUNCH(n4, flops, gemm_bt_p4_kernel<4>, grid, dim3(512), smem, st, p);
-    }
-#ifdef FO1_ENABLE_AB
-    else if (epi == 0) FO1_LAUNCH(name, flops, gemm_bt_p8_kernel<0>, grid, dim3(512), smem, st, p);
-    else if (epi == 1) FO1_LAUNCH(name, flops, gemm_bt_p8_kernel<1>, grid, dim3(512), smem, st, p);
-    else if (epi == 2) FO1_LAUNCH(name, flops, gemm_bt_p8_kernel<2>, grid, dim3(512), smem, st, p);
-    else if (epi == 3) FO1_LAUNCH(name, flops, gemm_bt_p8_kernel<3>, grid, dim3(512), smem, st, p);
-    else FO1_LAUNCH(name, flops, gemm_bt_p8_kernel<4>, grid, dim3(512), smem, st, p);
-#endif
-    if (p.splits > 1) {
-        const long long total = (long long)p.M * (p.N / 4);
-        const int rg = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-        FO1_LAUNCH("gemm_splitk_reduce", (double)p.M * p.N * 4.0 * p.splits, gemm_splitk_reduce_kernel, dim3(rg), dim3(256), 0, st, p);
-    }
-    return FO1_OK;
-}
-
-// fp8 form of the 256 x 256 two-phase kernel (fo1_gemm_fp8)
-static int launch_gemm_p4_fp8(GemmParams& p, hipStream_t st) {
-    p.tiles_m = cdiv(p.M, 256);
-    p.tiles_n = cdiv(p.N, 256);
-    const dim3 grid(p.tiles_m * p.tiles_n, 1, 1);
-    const double flops = 2.0 * p.M * (double)p.N * p.K;
-    char pname[56];
-    const char* name = "gemm_fp8_p4<256,256>";
-    if (profile_enabled() && g_gemm_profile_shapes) {
-        snprintf(pname, sizeof pname, "gemm_fp8 %dx%dx%d t256x256", p.M, p.N, p.K);
-        name = pname;
-    }
-    constexpr int smem = 2 * 4 * 16384;
-    {
-        const int nc = p.act == ACT_SWIGLU16 ? p.N / 2 : p.N;
-        p.coal = g_gemm_coal && nc % 8 == 0 && p.ldc % 8 == 0 && ((uintptr_t)p.C & 15) == 0 &&
-                 (p.res == nullptr || (p.ldr % 8 == 0 && ((uintptr_t)p.res & 15) == 0));
-    }
-    static bool attr = false;
-    if (!attr) {
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p4_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p4_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p4_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p4_kernel<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr = true;
-    }
-    if (p.act == 0) FO1_LAUNCH(name, flops, (gemm_bt_p4_kernel<0, true>), grid, dim3(512), smem, st, p);
-    else if (p.act == 1) FO1_LAUNCH(name, flops, (gemm_bt_p4_kernel<1, true>), grid, dim3(512), smem, st, p);
-    else if (p.act == 2) FO1_LAUNCH(name, flops, (gemm_bt_p4_kernel<2, true>), grid, dim3(512), smem, st, p);
-    else FO1_LAUNCH(name, flops, (gemm_bt_p4_kernel<3, true>), grid, dim3(512), smem, st, p);
-    return FO1_OK;
+    rc = launch_big<BigP4>(epi, p, batch, st, " s%d", p.splits);
+    if (rc != FO1_OK) return rc;
+    return p.splits > 1 ? launch_splitk_reduce(p, st) : FO1_OK;
 }
 
 // One workgroup per row: absmax -> scale = absmax / 448 (1 for an all-zero row) -> q = e4m3(clamp(x / scale, +-448)), RNE (v_cvt_pk_fp8_f32:
@@ -2182,19 +2171,33 @@ __global__ __launch_bounds__(256) void quantize_rows_e4m3_kernel(const uint16_t*
     for (int c = tid + RC * 256; c < nch; c += 256) quant8(*reinterpret_cast<const uint4*>(xr + c * 8), c);   // (L2 hit: just read)
 }
 
-template <int BM, int BN, int NS, int WGM = 2, int WGN = 2>
-static int launch_ring(GemmParams& p, const char* name, double flops, dim3 grid, hipStream_t st) {
+// The ring depth that runs for a requested one: 3 and 4 as asked; a deeper request takes the tile's deepest ring — 5 for <128, 96> (140 KB),
+// 6 for <128, 64> and <64, 64> (144 / 96 KB), 4 for the 128-column tiles of gemm_dispatch.  (tests/gemm_route_cases.py restates it: Route.ring_depth.)
+constexpr int ring_depth(int BM, int BN, int requested) {
+    if (requested == 3 || requested == 4) return requested;
+    if (BN == 96) return 5;
+    return BN == 64 ? 6 : 4;
+}
+
+template <int BM, int BN, int NS, int WGM, int WGN>
+static int launch_ring_ns(const GemmParams& p, const char* name, double flops, dim3 grid, hipStream_t st) {
     static_assert((NS - 2) * ((BM + BN) / 32) <= 63, "vmcnt is a 6-bit counter");
     static_assert(NS - 2 <= 4, "the K loop's counted waits cover up to 4 tiles in flight behind the current one");
     constexpr int smem = NS * (BM + BN) * 128;
     static_assert(smem <= 160 * 1024, "LDS per workgroup");
-    static bool attr_done = false;
-    if (!attr_done) {
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_ring_kernel<BM, BN, NS, WGM, WGN>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_done = true;
-    }
+    FO1_DYNAMIC_LDS_ONCE(smem, gemm_bt_ring_kernel<BM, BN, NS, WGM, WGN>);
     FO1_LAUNCH(name, flops, (gemm_bt_ring_kernel<BM, BN, NS, WGM, WGN>), grid, dim3(256), smem, st, p);
     return FO1_OK;
+}
+
+// The ring kernel of tile <BM, BN> at depth ring_depth(BM, BN, p.stages); instantiated per tile: 3, 4 and the deepest
+template <int BM, int BN, int WGM = 2, int WGN = 2>
+static int launch_ring(const GemmParams& p, const char* name, double flops, dim3 grid, hipStream_t st) {
+    constexpr int deepest = ring_depth(BM, BN, 6);
+    const int ns = ring_depth(BM, BN, p.stages);
+    if (ns == 3) return launch_ring_ns<BM, BN, 3, WGM, WGN>(p, name, flops, grid, st);
+    if (ns == 4) return launch_ring_ns<BM, BN, 4, WGM, WGN>(p, name, flops, grid, st);
+    return launch_ring_ns<BM, BN, deepest, WGM, WGN>(p, name, flops, grid, st);
 }
 
 // Skinny-M weight streams of the decode pool (65..128 rows; round 6): tiles whose ring is DEEP — what a weight stream needs is bytes in flight
@@ -2202,25 +2205,16 @@ static int launch_ring(GemmParams& p, const char* name, double flops, dim3 grid,
 //   <128, 96> waves 4 x 1, 5 stages (140 KB): 48 KB of W in flight per workgroup, 230 workgroups for N = 22016 (SwiGLU pairs stay in a wave);
 //   <128, 64> waves 2 x 2, 6 stages (144 KB): 40 KB of W in flight, N / 64 column tiles x splits workgroups (down as split-K planes);
 //   <128, 64> 3 stages (72 KB): two workgroups per CU.
+// (its default profile row states the REQUESTED depth ns)
 template <int BM, int BN, int WGM, int WGN>
 static int launch_ring_deep(GemmParams& p, int ns, hipStream_t st) {
     p.tiles_m = cdiv(p.M, BM);
     p.tiles_n = cdiv(p.N, BN);
     const dim3 grid(p.tiles_m * p.tiles_n, 1, p.splits);
     const double flops = 2.0 * p.M * (double)p.N * p.K;
-    char pname[56];
-    snprintf(pname, sizeof pname, "gemm_bt_ring<%d,%d,%d>", BM, BN, ns);
-    if (profile_enabled() && g_gemm_profile_shapes) snprintf(pname, sizeof pname, "gemm %dx%dx%d t%dx%d s%d r%d", p.M, p.N, p.K, BM, BN, p.splits, ns);
     p.stages = ns;
-    if constexpr (BN == 96) {
-        if (ns == 3) return launch_ring<BM, BN, 3, WGM, WGN>(p, pname, flops, grid, st);
-        if (ns == 4) return launch_ring<BM, BN, 4, WGM, WGN>(p, pname, flops, grid, st);
-        return launch_ring<BM, BN, 5, WGM, WGN>(p, pname, flops, grid, st);
-    } else {
-        if (ns == 3) return launch_ring<BM, BN, 3, WGM, WGN>(p, pname, flops, grid, st);
-        if (ns == 4) return launch_ring<BM, BN, 4, WGM, WGN>(p, pname, flops, grid, st);
-        return launch_ring<BM, BN, 6, WGM, WGN>(p, pname, flops, grid, st);
-    }
+    char buf[64];
+    return launch_ring<BM, BN, WGM, WGN>(p, gemm_row(buf, "gemm_bt_ring", ns, p, BM, BN, " s%d r%d", p.splits, ns), flops, grid, st);
 }
 
 template <int BM, int BN>
@@ -2229,85 +2223,34 @@ static int launch_gemm(GemmParams& p, int batch, bool glds, hipStream_t st, bool
     p.tiles_n = cdiv(p.N, BN);
     const dim3 grid(p.tiles_m * p.tiles_n, batch, glds ? p.splits : 1);
     const double flops = 2.0 * p.M * (double)p.N * p.K * batch;
-    char pname[48];
-    // one profile row per kernel template, so the rows map 1:1 onto rocprofv3's kernel names
-    const char* name = !glds ? "gemm_bf16_reg"
-                     : (BM == 128 ? "gemm_bt_glds<128,128>" : (BN == 128 ? "gemm_bt_glds<64,128>" : "gemm_bt_glds<64,64>"));
-    if (glds && p.stages >= 3) {
-        const int ns = p.stages == 3 ? 3 : ((p.stages == 4 || BM + BN > 128) ? 4 : 6);
-        snprintf(pname, sizeof pname, "gemm_bt_ring<%d,%d,%d>", BM, BN, ns);
-        name = pname;
-    }
-    if (profile_enabled() && g_gemm_profile_shapes) {
-        snprintf(pname, sizeof pname, "gemm %dx%dx%d t%dx%d s%d r%d", p.M, p.N, p.K, BM, BN, glds ? p.splits : 1, glds ? p.stages : 0);
-        name = pname;
-    }
-    if (glds && p.stages >= 3) {
-        int rc = FO1_OK;
-        if (p.stages == 3) rc = launch_ring<BM, BN, 3>(p, name, flops, grid, st);
-        else if (p.stages == 4) rc = launch_ring<BM, BN, 4>(p, name, flops, grid, st);
-        else if constexpr (BM + BN <= 128) rc = launch_ring<BM, BN, 6>(p, name, flops, grid, st);
-        else rc = launch_ring<BM, BN, 4>(p, name, flops, grid, st);
-        if (rc != FO1_OK) return rc;
-        if (p.splits > 1 && reduce) {
-            const long long total = (long long)p.M * (p.N / 4);
-            const int rg = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-            FO1_LAUNCH("gemm_splitk_reduce", (double)p.M * p.N * 4.0 * p.splits, gemm_splitk_reduce_kernel, dim3(rg), dim3(256), 0, st, p);
-        }
+    const bool ring = glds && p.stages >= 3;
+    char buf[64];
+    const char* name = gemm_row(buf, !glds ? "gemm_bf16_reg" : ring ? "gemm_bt_ring"
+                                     : (BM == 128 ? "gemm_bt_glds<128,128>" : (BN == 128 ? "gemm_bt_glds<64,128>" : "gemm_bt_glds<64,64>")),
+                                ring ? ring_depth(BM, BN, p.stages) : 0, p, BM, BN, " s%d r%d", glds ? p.splits : 1, glds ? p.stages : 0);
+    if (!glds) {
+        FO1_LAUNCH(name, flops, (gemm_bt_reg_kernel<BM, BN>), grid, dim3(256), 0, st, p);
         return FO1_OK;
     }
-    if (glds) {
-        constexpr int smem = 2 * (BM + BN) * 128;
-        static bool attr_done = false;
-        if (!attr_done) {
-            FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_glds_kernel<BM, BN>,
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            attr_done = true;
-        }
-        FO1_LAUNCH(name, flops, (gemm_bt_glds_kernel<BM, BN>), grid, dim3(256), smem, st, p);
-        if (p.splits > 1 && reduce) {
-            const long long total = (long long)p.M * (p.N / 4);
-            const int rg = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-            FO1_LAUNCH("gemm_splitk_reduce", (double)p.M * p.N * 4.0 * p.splits, gemm_splitk_reduce_kernel, dim3(rg), dim3(256), 0, st, p);
-        }
+    if (ring) {
+        const int rc = launch_ring<BM, BN>(p, name, flops, grid, st);
+        if (rc != FO1_OK) return rc;
     } else {
-        FO1_LAUNCH(name, flops, (gemm_bt_reg_kernel<BM, BN>), grid, dim3(256), 0, st, p);
+        constexpr int smem = 2 * (BM + BN) * 128;
+        FO1_DYNAMIC_LDS_ONCE(smem, gemm_bt_glds_kernel<BM, BN>);
+        FO1_LAUNCH(name, flops, (gemm_bt_glds_kernel<BM, BN>), grid, dim3(256), smem, st, p);
     }
-    return FO1_OK;
+    return p.splits > 1 && reduce ? launch_splitk_reduce(p, st) : FO1_OK;
 }
 
 // q/k/v projection with the fused epilogue (EPI 6 LLM / 7 ViT): always the 256 x 256 two-phase kernel (the epilogue pairs waves of one tile row)
 static int launch_qkv_p4(GemmParams& p, int mode, hipStream_t st) {
-    p.tiles_m = cdiv(p.M, 256);
-    p.tiles_n = cdiv(p.N, 256);
     if (g_gemm_group_m > 0) p.gm = g_gemm_group_m;
-    p.splits = 1;
-    p.kper = p.K / 64 + 1;
-    p.part = nullptr;
-    p.debug = 0;
 #ifdef FO1_ENABLE_AB
     if ((g_gemm_debug & 32) && g_gemm_stamp_buf) { p.debug = 32; p.part = (float*)g_gemm_stamp_buf; }      // workgroup timeline (scripts/r06_qkv_timeline.py)
 #endif
     p.coal = 1;
-    p.stages = 2;
-    const dim3 grid(p.tiles_m * p.tiles_n, 1, 1);
-    const double flops = 2.0 * p.M * (double)p.N * p.K;
-    constexpr int smem = 2 * 4 * 16384;
-    static bool attr = false;
-    if (!attr) {
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p4_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p4_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr = true;
-    }
-    char pname[56];
-    const char* name = "gemm_bt_p4<256,256>";
-    if (profile_enabled() && g_gemm_profile_shapes) {
-        snprintf(pname, sizeof pname, "gemm %dx%dx%d t256x256 qkv%d", p.M, p.N, p.K, mode);
-        name = pname;
-    }
-    if (mode == 0) FO1_LAUNCH(name, flops, gemm_bt_p4_kernel<6>, grid, dim3(512), smem, st, p);
-    else FO1_LAUNCH(name, flops, gemm_bt_p4_kernel<7>, grid, dim3(512), smem, st, p);
-    return FO1_OK;
+    return launch_big<BigP4Qkv>(mode == 0 ? 6 : 7, p, 1, st, " qkv%d", mode);
 }
 
 // THE statement of "this [M, K] x [N, K]^T product runs on the 256 x 256 two-phase kernel": gemm_dispatch picks its tile with it and
@@ -2397,17 +2340,12 @@ int gemm_dispatch(GemmParams& p, int batch, hipStream_t st, float* ws, size_t ws
     if (tile == 7) {
         const int rc = launch_ring_deep<128, 64, 2, 2>(p, g_gemm_variant >= 3 ? g_gemm_variant : (p.splits > 1 ? 6 : 3), st);
         if (rc != FO1_OK) return rc;
-        if (p.splits > 1) {
-            const long long total = (long long)p.M * (p.N / 4);
-            const int rg = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-            FO1_LAUNCH("gemm_splitk_reduce", (double)p.M * p.N * 4.0 * p.splits, gemm_splitk_reduce_kernel, dim3(rg), dim3(256), 0, st, p);
-        }
-        return FO1_OK;
+        return p.splits > 1 ? launch_splitk_reduce(p, st) : FO1_OK;
     }
     if (g_gemm_variant >= 3) p.stages = g_gemm_variant;
     else if (g_gemm_variant == 0 && glds && ((tile == 3 && t64 <= 768) || (tile == 2 && tiles * p.splits < 512) || (tile == 1 && auto_tile && p.M <= 128))) p.stages = 3;
     else p.stages = 2;
-    if (tile == 4 && glds && p.stages == 2) return launch_gemm_wide<128, 256>(p, batch, st);
+    if (tile == 4 && glds && p.stages == 2) return launch_gemm_wide(p, batch, st);
     if (tile == 4) tile = 1;
     if (tile == 1) return launch_gemm<128, 128>(p, batch, glds, st);
     if (tile == 2) return launch_gemm<64, 128>(p, batch, glds, st);
@@ -2502,14 +2440,7 @@ int fo1_gemm_bf16_ws(const void* A, int lda, const void* W, int ldw, const void*
     }
     FO1_CHECK_ARG(!out_f32 || residual == nullptr, "gemm: fp32 output does not take a residual");
     FO1_CHECK_ARG(residual == nullptr || ldr >= N, "gemm: ldr too small");
-    GemmParams p;
-    p.A = (const uint16_t*)A; p.W = (const uint16_t*)W; p.bias = (const uint16_t*)bias; p.res = (const uint16_t*)residual;
-    p.C = out_f32 ? nullptr : (uint16_t*)C;
-    p.C32 = out_f32 ? (float*)C : nullptr;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr; p.act = act;
-    p.sA = p.sW = p.sC = p.sR = 0;
-    p.coal = 0;
-    p.scale_m = p.scale_n = nullptr;
+    GemmParams p(A, lda, W, ldw, bias, residual, ldr, C, ldc, out_f32 != 0, M, N, K, act);      // (split-K, ring depth, debug bits: gemm_dispatch)
     FO1_CHECK_ARG(workspace == nullptr || ((uintptr_t)workspace & 15) == 0, "gemm: workspace must be 16-byte aligned");
     if (g_gemm_gemv && M <= 4 && !out_f32 && (size_t)(M > 2 ? 4 : M) * K * 2 <= 150 * 1024 && (act != 3 || N % 32 == 0))
         return gemv_dispatch(A, lda, W, ldw, bias, residual, ldr, C, ldc, M, N, K, act, (hipStream_t)stream, nullptr, 0.f);
@@ -2532,39 +2463,14 @@ int fo1_conv3x3_gemm_bf16(const void* Xpad, const uint32_t* a_rows, int Wp, int 
     FO1_CHECK_ARG(((uintptr_t)Xpad & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)C & 15) == 0 && (bias == nullptr || ((uintptr_t)bias & 7) == 0),
                   "conv3x3_gemm: operands must be 16-byte aligned");
     FO1_CHECK_ARG(act == 0 || act == 1, "conv3x3_gemm: act=%d (0 none, 1 GELU)", act);
-    GemmParams p;
-    p.A = (const uint16_t*)Xpad; p.W = (const uint16_t*)W; p.bias = (const uint16_t*)bias; p.res = nullptr;
-    p.C = (uint16_t*)C; p.C32 = nullptr;
-    p.M = M; p.N = N; p.K = 9 * Cin; p.lda = Cin; p.ldw = ldw; p.ldc = ldc; p.ldr = 0; p.act = act;
-    p.sA = p.sW = p.sC = p.sR = 0;
-    p.scale_m = p.scale_n = nullptr;
+    GemmParams p(Xpad, Cin, W, ldw, bias, nullptr, 0, C, ldc, false, M, N, 9 * Cin, act);
     p.a_rows = a_rows; p.conv_row_bytes = (uint32_t)Wp * Cin * 2u; p.conv_cin_bytes = (uint32_t)Cin * 2u;
     int lg = 0;
     while ((64 << lg) < Cin) ++lg;
     p.conv_lgc = lg;
-    p.tiles_m = cdiv(M, 256);
-    p.tiles_n = cdiv(N, 256);
     if (g_gemm_group_m > 0) p.gm = g_gemm_group_m;
-    p.splits = 1; p.kper = p.K / 64 + 1; p.part = nullptr; p.debug = 0; p.coal = 1; p.stages = 2;
-    const dim3 grid(p.tiles_m * p.tiles_n, 1, 1);
-    constexpr int smem = 2 * 4 * 16384;
-    static bool attr = false;
-    if (!attr) {
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p4_kernel<0, false, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bt_p4_kernel<1, false, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr = true;
-    }
-    const double flops = 2.0 * M * (double)N * p.K;
-    char pname[56];
-    const char* name = "gemm_bt_p4<256,256>";
-    if (profile_enabled() && g_gemm_profile_shapes) {
-        snprintf(pname, sizeof pname, "gemm %dx%dx%d t256x256 conv", M, N, p.K);
-        name = pname;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (act == 0) FO1_LAUNCH(name, flops, (gemm_bt_p4_kernel<0, false, 0, true>), grid, dim3(512), smem, st, p);
-    else FO1_LAUNCH(name, flops, (gemm_bt_p4_kernel<1, false, 0, true>), grid, dim3(512), smem, st, p);
-    return FO1_OK;
+    p.coal = 1;
+    return launch_big<BigP4Conv>(act, p, 1, (hipStream_t)stream, " conv");
 }
 
 // 1 when fo1_gemm_bf16 runs an [M, K] x [N, K]^T product (bf16 out, K % 64 == 0, aligned operands) on the 256 x 256 two-phase kernel — the
@@ -2601,12 +2507,7 @@ int fo1_qkv_proj_rope_bf16(const void* A, int lda, const void* W, int ldw, const
     } else {
         FO1_CHECK_ARG(n_q_heads > 0 && N == n_q_heads * 256, "qkv_proj_rope: N=%d is not %d head tiles of 256", N, n_q_heads);
     }
-    GemmParams p;
-    p.A = (const uint16_t*)A; p.W = (const uint16_t*)W; p.bias = (const uint16_t*)bias; p.res = nullptr;
-    p.C = (uint16_t*)C; p.C32 = nullptr;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = 0; p.act = 0;
-    p.sA = p.sW = p.sC = p.sR = 0;
-    p.scale_m = p.scale_n = nullptr;
+    GemmParams p(A, lda, W, ldw, bias, nullptr, 0, C, ldc, false, M, N, K, ACT_NONE);
     p.rope_cos = cos_table; p.rope_sin = sin_table;
     p.kcache = (uint16_t*)kcache; p.kc_head_stride = kcache_head_stride;
     p.vt = (uint16_t*)vt; p.vt_ld = vt_ld; p.pos0 = pos0; p.n_q = n_q_heads; p.n_kv = n_kv_heads;
@@ -2627,12 +2528,8 @@ int fo1_gemm_bf16_partials(const void* A, int lda, const void* W, int ldw, int M
     FO1_CHECK_ARG(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)part & 15) == 0, "gemm_partials: operands must be 16-byte aligned");
     const int nk = K / 64;
     FO1_CHECK_ARG(splits >= 2 && splits <= nk && splits <= 64, "gemm_partials: splits=%d (2 .. min(64, K / 64 = %d))", splits, nk);
-    GemmParams p;
-    p.A = (const uint16_t*)A; p.W = (const uint16_t*)W; p.bias = nullptr; p.res = nullptr; p.C = nullptr; p.C32 = nullptr;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldc = N; p.ldr = 0; p.act = ACT_NONE;
-    p.sA = p.sW = p.sC = p.sR = 0;
-    p.coal = 0; p.debug = 0; p.stages = 3;
-    p.scale_m = p.scale_n = nullptr;
+    GemmParams p(A, lda, W, ldw, nullptr, nullptr, 0, nullptr, N, false, M, N, K, ACT_NONE);
+    p.stages = 3;
     p.kper = cdiv(nk, splits);
     p.splits = cdiv(nk, p.kper);
     p.part = part;
@@ -2641,7 +2538,7 @@ int fo1_gemm_bf16_partials(const void* A, int lda, const void* W, int ldw, int M
     // wide outputs (gate/up: 22016 columns) at 65..128 rows: 128 x 256 tiles — the activations come back from L2 once per tile COLUMN, and
     // 86 column tiles x 3 planes fill the chip where 172 tiles of 128 x 128 with the SwiGLU epilogue leave a third of it idle
     if (g_gemm_tile == 7 && M > 64 && M <= 128) return launch_ring_deep<128, 64, 2, 2>(p, g_gemm_variant >= 3 ? g_gemm_variant : 6, (hipStream_t)stream);   // (A/B pin)
-    if (M > 64 && M <= 128 && N >= 8192 && nk >= 16) return launch_gemm_wide<128, 256>(p, 1, (hipStream_t)stream, false);
+    if (M > 64 && M <= 128 && N >= 8192 && nk >= 16) return launch_gemm_wide(p, 1, (hipStream_t)stream, false);
     // (128 x 128 tiles for the 65..128-row down projection — the weights fetched once instead of once per 64-row tile — measured no faster:
     // 17.4 vs 16.3 us at 12-16 planes, profiles/r04_pool_step_splitk_sweep.json)
     if ((long long)cdiv(M, 64) * cdiv(N, 128) * p.splits >= 256) return launch_gemm<64, 128>(p, 1, true, (hipStream_t)stream, false);
@@ -2663,13 +2560,8 @@ int fo1_gemm_bf16_wtiled(const void* A, int lda, const void* W_tiled, const void
     if (act == 3) FO1_CHECK_ARG(residual == nullptr && ldc % 4 == 0 && ((uintptr_t)C & 7) == 0 && ldc >= N / 2, "gemm_wtiled: swiglu epilogue layout");
     else FO1_CHECK_ARG(ldc >= N, "gemm_wtiled: ldc too small");
     FO1_CHECK_ARG(residual == nullptr || ldr >= N, "gemm_wtiled: ldr too small");
-    GemmParams p;
-    p.A = (const uint16_t*)A; p.W = (const uint16_t*)W_tiled; p.bias = (const uint16_t*)bias; p.res = (const uint16_t*)residual;
-    p.C = (uint16_t*)C; p.C32 = nullptr;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = K; p.ldc = ldc; p.ldr = ldr; p.act = act;
-    p.sA = p.sW = p.sC = p.sR = 0;
-    p.splits = 1; p.kper = K / 64 + 1; p.part = nullptr; p.stages = 3; p.debug = 0; p.coal = 0;
-    p.scale_m = p.scale_n = nullptr;
+    GemmParams p(A, lda, W_tiled, K, bias, residual, ldr, C, ldc, false, M, N, K, act);
+    p.stages = 3;
     p.w_tiled = 1;
     if (M > 64) return launch_gemm<128, 128>(p, 1, true, (hipStream_t)stream);
     return launch_gemm<64, 128>(p, 1, true, (hipStream_t)stream);
@@ -2695,14 +2587,11 @@ int fo1_gemm_fp8(const void* Aq, int lda, const float* scale_a, const void* Wq, 
     FO1_CHECK_ARG(residual == nullptr || (ldr % 4 == 0 && ((uintptr_t)residual & 7) == 0 && ldr >= N), "gemm_fp8: residual layout");
     if (act == 3) FO1_CHECK_ARG(residual == nullptr && N % 32 == 0 && ldc >= N / 2, "gemm_fp8: swiglu epilogue needs no residual, N %% 32 == 0, ldc >= N/2");
     else FO1_CHECK_ARG(ldc >= N, "gemm_fp8: ldc too small");
-    GemmParams p;
-    p.A = (const uint16_t*)Aq; p.W = (const uint16_t*)Wq; p.bias = (const uint16_t*)bias; p.res = (const uint16_t*)residual;
-    p.C = (uint16_t*)C; p.C32 = nullptr;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr; p.act = act;
-    p.sA = p.sW = p.sC = p.sR = 0;
-    p.splits = 1; p.kper = K / 128 + 1; p.part = nullptr; p.stages = 2; p.debug = 0; p.coal = 0;
+    GemmParams p(Aq, lda, Wq, ldw, bias, residual, ldr, C, ldc, false, M, N, K, act);
+    p.kper = K / 128 + 1;      // (a K tile = 128 bytes per row = 128 e4m3 elements)
     p.scale_m = scale_a; p.scale_n = scale_w;
-    return launch_gemm_p4_fp8(p, (hipStream_t)stream);
+    p.coal = coal_epilogue(p);
+    return launch_big<BigP4Fp8>(act, p, 1, (hipStream_t)stream, "");
 }
 
 // Row-wise e4m3 quantisation of a bf16 matrix: q[m, :] = e4m3(x[m, :] / scales[m]), scales[m] = absmax(x[m, :]) / 448.

@@ -184,11 +184,7 @@ template <int MM, bool SW, bool KS>
 static int launch_gemv2(const GemvParams& p, const char* name, hipStream_t st) {
     const size_t smem = (size_t)MM * p.K * 2;
     const int units = cdiv(SW ? p.N / 2 : p.N, 4);
-    static bool attr = false;
-    if (!attr) {
-        FO1_CHECK_HIP(hipFuncSetAttribute((const void*)gemv_kernel<MM, SW, KS>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        attr = true;
-    }
+    FO1_DYNAMIC_LDS_ONCE(150 * 1024, gemv_kernel<MM, SW, KS>);
     FO1_LAUNCH(name, (double)p.N * p.K * 2.0, (gemv_kernel<MM, SW, KS>), dim3(KS ? units : cdiv(units, 4)), dim3(256), smem, st, p);
     return FO1_OK;
 }

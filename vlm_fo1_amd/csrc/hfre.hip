@@ -1100,11 +1100,7 @@ int fo1_hfre_region_pool_ex(const fo1_hfre_source_t* sources, int n_sources, con
     for (int i = 0; i < n_sources; ++i) bytes += (double)sources[i].H * sources[i].W * sources[i].C * 2.0 * (opts ? opts->batch : 1);
 #ifdef FO1_ENABLE_AB
     if (p.band_mode) {
-        static bool attr = false;
-        if (!attr) {
-            FO1_CHECK_HIP(hipFuncSetAttribute((const void*)hfre_pool_bands_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kHfreBandSmem));
-            attr = true;
-        }
+        FO1_DYNAMIC_LDS_ONCE(kHfreBandSmem, hfre_pool_bands_kernel);
         FO1_LAUNCH("hfre_pool_bands", bytes, hfre_pool_bands_kernel, dim3(p.band_items), dim3(kHfreBandThreads), kHfreBandSmem, st, p);
     } else
 #endif
