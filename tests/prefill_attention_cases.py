@@ -24,7 +24,7 @@ The remaining rows are N(0, 1); temperature 3 makes random scores of std ~3, so 
 moves by -SCORE_SHIFT along u_kvh: each query's scores all drop by the same amount (the softmax is unchanged), and a zero K row — what a
 guarded load past a range reads — outscores every real key: a missing mask is a gross error too (fault zero_key).
 
-emulate() is the kernels' arithmetic on the CPU, the same for every entry up to the key tile (attn_fwd_kernel, attention.hip:269-327;
+emulate() is the kernels' arithmetic on the CPU, the same for every entry up to the key tile (attn_fwd_kernel, attention.hip:278-336;
 attn_win1_kernel, one tile per item; attn_fwd32_kernel, whose per-lane partial row sums are only fp32 re-association; win_attn32_kernel,
 window_attention.hip:125-163, with 32-key tiles): fp32 scores; a base-2 running maximum m = max(m, c1 * tile max) per key tile, tiles taken
 from the prefix range's first key, then from the own range's first key (kv_start); e = exp2(c1 s - m) in fp32, P = bf16(e) into the PV

@@ -98,6 +98,43 @@ def test_single_sequence_decode_attention_against_fp64(case, product_library):
     assert torch.equal(outs[0], outs[1]), f"{case.name}: bound {case.max_kv_len} and {n} differ"
 
 
+def _attn_rows(launch):
+    """One launch under the profile -> the names of its attn_ rows in first-launch order (each launched once)."""
+    from vlm_fo1_amd import lib as L
+    L.profile_rows()
+    L.profile(True)
+    try:
+        launch()
+        torch.cuda.synchronize()
+        rows = [r for r in L.profile_rows() if r["name"].startswith("attn_")]
+    finally:
+        L.profile(False)
+    assert all(r["calls"] == 1 for r in rows), rows
+    return [r["name"] for r in rows]
+
+
+LAUNCH_ROWS = {"split64-B1-L65": ["attn_decode_split", "attn_decode_combine"], "two_tile-B17-L65": ["attn_decode_split", "attn_decode_combine"],
+               "pool_split-B33-L1025": ["attn_decode_split", "attn_decode_combine"], "single-n1": ["attn_decode_split", "attn_decode_combine"],
+               "one_chunk-B1-L1": ["attn_decode_one_chunk"], "pool_one-B33-L1": ["attn_decode_one_chunk"],
+               "gemv-B1-L65": ["attn_decode_split"]}
+
+
+def test_launch_rows_per_route(product_library):
+    """The kernels each route launches, by their profile rows: the smallest case of every route (16 query / 2 KV heads), run once."""
+    from vlm_fo1_amd import ops
+    for prefix, want in LAUNCH_ROWS.items():
+        c = next(c for c in C.ALL_CASES if c.name == prefix or c.name.startswith(prefix + "-h16x2"))
+        dev = C.to_device(C.build(c))
+        if c.route == "single":
+            kv_len = torch.tensor([1], dtype=torch.int32, device="cuda")
+            run = lambda: ops.attention_decode(dev["q"].contiguous(), dev["kc"], dev["vt"], kv_len, c.max_kv_len, c.Hq, c.Hkv, HD, HD ** -0.5)
+        elif c.route == "gemv":
+            run = lambda: ops.attention_decode_batch_partials(dev["q"], dev["kc"], dev["vt"], dev["state"], c.max_kv_len, c.Hq, c.Hkv, HD, HD ** -0.5)
+        else:
+            run = lambda: _run(dev, c, c.max_kv_len)
+        assert _attn_rows(run) == want, c.name
+
+
 def test_tiles_per_item_do_not_change_the_bits(ab_library):
     """At 25 sequences an item walks 1 / 2 / 3 / 8 tiles of 64 keys (fo1_attention_decode_set_small_chunk(1 .. 8)): the same bits, and within
     the fp64 bound, at one-chunk, odd and even chunk counts."""

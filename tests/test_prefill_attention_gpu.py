@@ -155,3 +155,50 @@ def test_prefill_attention_route_against_fp64_and_bitwise_invariants(case, produ
     if case.route == "rowbase":
         plain = _launch(d, dev, plain_base=True)
         assert _same(plain[case.row_base:], got), f"{case.name}: the q_row_base launch differs from the plain launch on shifted rows"
+
+
+def _attn_rows(launch):
+    """One launch under the profile -> the names of its attn_ rows in first-launch order (each launched once)."""
+    from vlm_fo1_amd import lib as L
+    L.profile_rows()
+    L.profile(True)
+    try:
+        launch()
+        rows = [r for r in L.profile_rows() if r["name"].startswith("attn_")]
+    finally:
+        L.profile(False)
+    assert all(r["calls"] == 1 for r in rows), rows
+    return [r["name"] for r in rows]
+
+
+def _case(name):
+    return next(c for c in C.SWEEP if c.name == name)
+
+
+# the smallest case of every route through attention.hip -> its one profile row
+LAUNCH_ROWS = {"fwd16-hd128-12x2-causal": "attn_fwd", "prefix16-hd128-16x2-causal": "attn_fwd", "swin-ws12-s0-1x1-h6-q64": "attn_fwd",
+               "rowbase-base0": "attn_fwd", "fwd32-hd128-q256-4x4-causal": "attn_fwd32", "prefix32-hd128-16x2-causal": "attn_fwd32",
+               "win1-n1-packed": "attn_win1"}
+
+
+def test_launch_rows_per_route(product_library):
+    """The kernel each route launches, by its profile row: one launch of the smallest case of the route on the product library; then, on the
+    test build with fo1_gemm_profile_shapes(1), the row of the 16x16 and of the 32x32 form states head dim, query block, item and head counts."""
+    from vlm_fo1_amd import lib as L, ops
+    for name, row in LAUNCH_ROWS.items():
+        d = C.build(_case(name))
+        dev = C.to_device(d)
+        assert _attn_rows(lambda: _launch(d, dev)) == [row], name
+    with L.use_ab() as ab:
+        L.check(ab.fo1_gemm_profile_shapes(1), "profile_shapes")
+        try:
+            for name, kernel, qb in (("fwd16-hd128-12x2-causal", "attn_fwd", 16), ("fwd16-hd128-12x2-causal", "attn_fwd", 64),
+                                     ("fwd32-hd128-q128-16x2-causal", "attn_fwd32", 128)):
+                c = _case(name)
+                d = C.build(c)
+                dev = C.to_device(d)
+                n = ops.make_items(d["segs"], "cpu", causal=c.causal, block=qb).shape[0]
+                want = f"{kernel} hd{c.HD} q{qb} items{n} heads{c.Hq}" + (" causal" if c.causal else "")
+                assert _attn_rows(lambda: _launch(d, dev, q_block=qb)) == [want], name
+        finally:
+            ab.fo1_gemm_profile_shapes(0)

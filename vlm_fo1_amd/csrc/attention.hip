@@ -30,36 +30,45 @@ struct AttnItem {
 };
 
 struct AttnParams {
-    const uint16_t* Q; long long q_tok, q_head;      // element strides
-    const uint16_t* K; long long k_tok, k_head;
-    const uint16_t* VT; long long vt_row;            // V^T row stride (elements); row = kv_head*HD + d
-    uint16_t* O; long long o_tok, o_head;
-    const AttnItem* items;
-    const int2* items2;                              // optional, per item: a SECOND key range [x, y) every query of the item sees in full, walked
+    const uint16_t* Q = nullptr; long long q_tok = 0, q_head = 0;      // element strides
+    const uint16_t* K = nullptr; long long k_tok = 0, k_head = 0;
+    const uint16_t* VT = nullptr; long long vt_row = 0;                // V^T row stride (elements); row = kv_head*HD + d
+    uint16_t* O = nullptr; long long o_tok = 0, o_head = 0;
+    const AttnItem* items = nullptr;
+    const int2* items2 = nullptr;                    // optional, per item: a SECOND key range [x, y) every query of the item sees in full, walked
                                                      // before the item's own range — the shared prompt prefix of several prompts over one
                                                      // image (its rows precede the item's in the index space, so `key <= query` holds)
-    int n_items, Hq, group;                          // group = Hq / Hkv
-    float scale;
-    int causal;
-    const int* q_row_base;                           // optional: Q/O row = query index - *q_row_base (decode graphs)
+    int n_items = 0, Hq = 0, group = 0;              // group = Hq / Hkv
+    float scale = 0.f;
+    int causal = 0;
+    const int* q_row_base = nullptr;                 // optional: Q/O row = query index - *q_row_base (decode graphs)
     // split-KV decode (PARTIAL): each item covers one KV chunk; unnormalised fp32 O and (m, l) go to `part`
-    float* part;                                     // [n_items][Hq][16 slots][HD + 2]
-    const int* dyn_kv_len;                           // optional: kv_end/kv_start of item i derived on device: chunk i of *dyn_kv_len keys
-    int kv_chunk;
-    int q_range_end;                                 // PARTIAL: number of query heads per KV head
-    int grid_batch;                                  // PARTIAL with seq_state: > 0 = 1-D grid of n_items x Hq x grid_batch workgroups walked sequence-fastest (see the kernel)
-    int part_tiles;                                  // PARTIAL, > 1: an item walks part_tiles 64-key tiles (kv_chunk = 64 x part_tiles) and writes ONE PARTIAL PER TILE, each
+    float* part = nullptr;                           // [n_items][Hq][16 slots][HD + 2] (decode_common.h: ATTN_PART_ROWS, attn_part_row_floats)
+    const int* dyn_kv_len = nullptr;                 // optional: kv_end/kv_start of item i derived on device: chunk i of *dyn_kv_len keys
+    int kv_chunk = 0;
+    int q_range_end = 0;                             // PARTIAL: number of query heads per KV head
+    int grid_batch = 0;                              // PARTIAL with seq_state: > 0 = 1-D grid of n_items x Hq x grid_batch workgroups walked sequence-fastest (see the kernel)
+    int part_tiles = 0;                              // PARTIAL, > 1: an item walks part_tiles 64-key tiles (kv_chunk = 64 x part_tiles) and writes ONE PARTIAL PER TILE, each
                                                      // exactly what a one-tile item writes (state reset between tiles): the workgroup count and the load / compute overlap of a
                                                      // long item with the partial sums of 64-key splits — a sequence's attention does not depend on the choice (round 6)
     // batched decode (PARTIAL): blockIdx.z = sequence; keys [state[z][2], state[z][0]] (decode.hip state layout)
-    const int* seq_state;
-    long long q_seq_stride;                          // Q elements between sequences
-    long long part_seq_stride;                       // floats between sequences in `part`
+    const int* seq_state = nullptr;
+    long long q_seq_stride = 0;                      // Q elements between sequences
+    long long part_seq_stride = 0;                   // floats between sequences in `part`
     // window attention with an additive bias (Swin: relative position bias + shifted-window mask, backbone/swin.py:150-175):
     // bias fp32 [Hq][wlen][wlen], indexed by the query / key position inside the item's kv range (= one window of wlen tokens)
-    const float* bias;
-    int wlen;
-    int sw_ws, sw_shift, sw_nwy, sw_nwx;             // sw_shift > 0: -100 between tokens of different shift regions (:446-466)
+    const float* bias = nullptr;
+    int wlen = 0;
+    int sw_ws = 0, sw_shift = 0, sw_nwy = 0, sw_nwx = 0;   // sw_shift > 0: -100 between tokens of different shift regions (:446-466)
+
+    // What every entry point states: the operands with their strides, the work list, head counts and scale (group 0: no KV heads, which
+    // the entry's checks reject).  Everything else keeps its default until the entry point says otherwise.
+    AttnParams(const void* Q_, long long q_tok_, long long q_head_, const void* K_, long long k_tok_, long long k_head_, const void* VT_,
+               long long vt_row_, void* O_, long long o_tok_, long long o_head_, const void* items_, int n_items_, int n_q_heads, int n_kv_heads,
+               float scale_)
+        : Q((const uint16_t*)Q_), q_tok(q_tok_), q_head(q_head_), K((const uint16_t*)K_), k_tok(k_tok_), k_head(k_head_),
+          VT((const uint16_t*)VT_), vt_row(vt_row_), O((uint16_t*)O_), o_tok(o_tok_), o_head(o_head_), items((const AttnItem*)items_),
+          n_items(n_items_), Hq(n_q_heads), group(n_kv_heads > 0 ? n_q_heads / n_kv_heads : 0), scale(scale_) {}
 };
 
 template <int HD, int NW, bool PARTIAL = false>
@@ -355,7 +364,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_fwd_kernel(cons
             // per-tile partial (wave-uniform branch): chunk index = item * part_tiles + tile of the item
             if (wave == 0 && q_ok) {
                 const long long ci = (long long)bx * p.part_tiles + (k0 - it.kv_start) / KB;
-                float* pr = partb + ((ci * p.Hq + h) * 16 + ql) * (HD + 2);
+                float* pr = partb + ((ci * p.Hq + h) * ATTN_PART_ROWS + ql) * attn_part_row_floats(HD);
 #pragma unroll
                 for (int db = 0; db < NDB; ++db)
                     *reinterpret_cast<float4*>(pr + db * 16 + g * 4) = float4{o[db][0], o[db][1], o[db][2], o[db][3]};
@@ -390,7 +399,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_fwd_kernel(cons
             return;
         }
         if (wave == 0 && q_ok) {
-            float* pr = partb + (((long long)bx * p.Hq + h) * 16 + ql) * (HD + 2);
+            float* pr = partb + (((long long)bx * p.Hq + h) * ATTN_PART_ROWS + ql) * attn_part_row_floats(HD);
 #pragma unroll
             for (int db = 0; db < NDB; ++db)
                 *reinterpret_cast<float4*>(pr + db * 16 + g * 4) = float4{o[db][0], o[db][1], o[db][2], o[db][3]};
@@ -927,8 +936,19 @@ __global__ __launch_bounds__(HD) void attn_decode_combine_kernel(const float* __
     // the arithmetic lives in attn_combine_row (decode_common.h): the decode GEMV's fused prologue (M <= 2) runs the same code, so a sequence's
     // attention rows are the same bits with and without this launch
     float o1[1];
-    attn_combine_row<1>(part + ((long long)kvh * 16 + slot) * (HD + 2), (long long)n_kv_heads * 16 * (HD + 2), n_valid, d, o1);
+    attn_combine_row<1>(part + ((long long)kvh * ATTN_PART_ROWS + slot) * attn_part_row_floats(HD), attn_part_seq_floats(1, n_kv_heads, HD), n_valid, d, o1);
     out[(long long)head * HD + d] = f32_to_bf16(o1[0]);
+}
+
+// The fixed-order merge of `batch` sequences' partials (chunks of kv_chunk keys) into their bf16 rows: per-sequence state and strides, or
+// (seq_state null: one sequence) the device-side key count
+template <int HD>
+static int launch_decode_combine(const float* part, long long part_seq_stride, const int* dyn_kv_len, const int* seq_state, int batch, int kv_chunk,
+                                 int n_kv_heads, int group, uint16_t* out, long long out_seq_stride, hipStream_t st) {
+    const int n_q_heads = n_kv_heads * group;
+    FO1_LAUNCH("attn_decode_combine", (double)batch * n_q_heads * HD * 8.0, attn_decode_combine_kernel<HD>, dim3(n_q_heads, batch), dim3(HD), 0, st,
+               part, dyn_kv_len, kv_chunk, n_kv_heads, group, out, seq_state, part_seq_stride, out_seq_stride);
+    return FO1_OK;
 }
 
 // ---- decode attention, one workgroup per (KV head, sequence[, KV split]) ---------------------------------------------------
@@ -944,15 +964,24 @@ __global__ __launch_bounds__(HD) void attn_decode_combine_kernel(const float* __
 // stages them coalesced through LDS.  Kept as an A/B option (fo1_attention_decode_set_impl), not the default.
 #ifdef FO1_ENABLE_AB      // one workgroup per (KV head, sequence): measured slower than split + combine, A/B only
 struct AttnDecParams {
-    const uint16_t* Q; long long q_seq_stride;       // q rows [B][n_q_heads * 128]
-    const uint16_t* K; long long k_tok, k_head;
-    const uint16_t* VT; long long vt_row;
-    uint16_t* O; long long o_seq_stride;
-    float* part; long long part_seq_stride;          // [split][kv head][16][HD + 2] per sequence
-    const int* seq_state;                            // [B][8] (decode.hip) or null
-    const int* dyn_kv_len;                           // single-sequence form: keys [0, *dyn_kv_len)
-    int n_kv_heads, group, split_keys, n_splits;
-    float scale;
+    const uint16_t* Q = nullptr; long long q_seq_stride = 0;       // q rows [B][n_q_heads * 128]
+    const uint16_t* K = nullptr; long long k_tok = 0, k_head = 0;
+    const uint16_t* VT = nullptr; long long vt_row = 0;
+    uint16_t* O = nullptr; long long o_seq_stride = 0;
+    float* part = nullptr; long long part_seq_stride = 0;          // [split][kv head][16][HD + 2] per sequence (decode_common.h)
+    const int* seq_state = nullptr;                  // [B][8] (decode.hip) or null
+    const int* dyn_kv_len = nullptr;                 // single-sequence form: keys [0, *dyn_kv_len)
+    int n_kv_heads = 0, group = 0, split_keys = 0, n_splits = 1;   // one split over the whole range until the launcher says otherwise
+    float scale = 0.f;
+
+    // What the decode entries state; exactly one of seq_state_ (batched: per-sequence strides) and dyn_kv_len_ (one sequence) is set
+    AttnDecParams(const void* q, long long q_seq_stride_, const void* kcache, long long k_tok_, long long k_head_, const void* vtcache,
+                  long long vt_row_, void* out, long long o_seq_stride_, void* part_, const void* seq_state_, const void* dyn_kv_len_,
+                  int n_q_heads, int n_kv_heads_, float scale_)
+        : Q((const uint16_t*)q), q_seq_stride(q_seq_stride_), K((const uint16_t*)kcache), k_tok(k_tok_), k_head(k_head_),
+          VT((const uint16_t*)vtcache), vt_row(vt_row_), O((uint16_t*)out), o_seq_stride(o_seq_stride_), part((float*)part_),
+          seq_state((const int*)seq_state_), dyn_kv_len((const int*)dyn_kv_len_), n_kv_heads(n_kv_heads_), group(n_q_heads / n_kv_heads_),
+          scale(scale_) {}
 };
 
 template <int NW>
@@ -1102,7 +1131,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_wg_kernel(const AttnDecPa
         if (p.n_splits == 1) {
             p.O[(long long)b * p.o_seq_stride + (long long)(kvh * p.group + slot) * HD + d] = f32_to_bf16(den > 0.f ? num / den : 0.f);
         } else {
-            float* pr = p.part + (long long)b * p.part_seq_stride + (((long long)split * p.n_kv_heads + kvh) * 16 + slot) * (HD + 2);
+            float* pr = p.part + (long long)b * p.part_seq_stride + (((long long)split * p.n_kv_heads + kvh) * ATTN_PART_ROWS + slot) * attn_part_row_floats(HD);
             pr[d] = num;
             if (d == 0) { pr[HD] = M; pr[HD + 1] = den; }
         }
@@ -1112,17 +1141,15 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_wg_kernel(const AttnDecPa
 static int g_attn_decode_impl = 0;   // 0 = 64-key split-KV partials + combine; 1 = attn_decode_wg_kernel (measured slower: see the note below)
 
 // One launch for slots up to 2048 rows (32 tiles over 8 waves); longer slots: 1024-key splits + the fixed-order combine.
-static int launch_attn_decode_wg(AttnDecParams& p, int max_kv_len, int batch, int n_q_heads, hipStream_t st) {
+static int launch_attn_decode_wg(AttnDecParams& p, int max_kv_len, int batch, hipStream_t st) {
     constexpr int NW = 8;
     if (max_kv_len <= 2048) { p.n_splits = 1; p.split_keys = cdiv(max_kv_len, 64) * 64; }
     else { p.split_keys = 1024; p.n_splits = cdiv(max_kv_len, 1024); }
-    p.part_seq_stride = (long long)p.n_splits * p.n_kv_heads * 16 * (128 + 2);
+    p.part_seq_stride = attn_part_seq_floats(p.n_splits, p.n_kv_heads, 128);
     FO1_LAUNCH("attn_decode_wg", (double)batch * max_kv_len * p.n_kv_heads * 128 * 4.0, (attn_decode_wg_kernel<NW>),
                dim3(p.n_splits, p.n_kv_heads, batch), dim3(NW * 64), 0, st, p);
-    if (p.n_splits > 1)
-        FO1_LAUNCH("attn_decode_combine", (double)batch * n_q_heads * 128 * 8.0, attn_decode_combine_kernel<128>, dim3(n_q_heads, batch), dim3(128), 0,
-                   st, (const float*)p.part, p.dyn_kv_len, p.split_keys, p.n_kv_heads, p.group, p.O, p.seq_state, p.part_seq_stride, p.o_seq_stride);
-    return FO1_OK;
+    if (p.n_splits == 1) return FO1_OK;
+    return launch_decode_combine<128>(p.part, p.part_seq_stride, p.dyn_kv_len, p.seq_state, batch, p.split_keys, p.n_kv_heads, p.group, p.O, p.o_seq_stride, st);
 }
 
 // impl 2 (round 4, A/B): one workgroup per (KV head, sequence) whose FOUR WAVES EACH WALK THEIR OWN 64-key tiles (wave w: tiles w, w + 4, ...)
@@ -1330,29 +1357,29 @@ static int launch_attn_decode_ws(AttnDecParams& p, int max_kv_len, int batch, hi
 
 extern int g_gemv_profile_shapes;   // gemv.hip: per-shape profile rows (fo1_gemm_profile_shapes)
 
+// The row of an attn_fwd / attn_fwd32 launch in the profile: the kernel's own name or, under fo1_gemm_profile_shapes,
+// "<kernel> hd<HD> q<q_block> items<n> heads<Hq>[ causal]".  FO1_LAUNCH reads it only while the profile is on; while the profile or the
+// switch is off nothing is formatted.  scripts/{make_profiles_readme, check_profile_agreement, pmc_summary}.py key on these strings.
+static const char* attn_row(char (&buf)[48], const char* kernel, int hd, int q_block, const AttnParams& p) {
+    if (!profile_enabled() || !g_gemv_profile_shapes) return kernel;
+    snprintf(buf, sizeof buf, "%s hd%d q%d items%d heads%d%s", kernel, hd, q_block, p.n_items, p.Hq, p.causal ? " causal" : "");
+    return buf;
+}
+
 template <int HD, int HPW>
 static int launch_attn32(const AttnParams& p, hipStream_t st, double flops) {
     constexpr int LDK = HD + 8, LDV = 64 + 8, HDV = (HD + 31) / 32 * 32;
     constexpr int smem = 2 * (64 * LDK + HDV * LDV) * 2;
     FO1_DYNAMIC_LDS_ONCE(smem, attn_fwd32_kernel<HD, HPW>);      // > 64 KB of dynamic LDS (first call of an instantiation; never inside a capture: passes run eagerly first)
-    char pname[48];
-    const char* name = "attn_fwd32";
-    if (profile_enabled() && g_gemv_profile_shapes) {
-        snprintf(pname, sizeof pname, "attn_fwd32 hd%d q%d items%d heads%d%s", HD, 256 / HPW, p.n_items, p.Hq, p.causal ? " causal" : "");
-        name = pname;
-    }
-    FO1_LAUNCH(name, flops, (attn_fwd32_kernel<HD, HPW>), dim3(p.Hq / HPW, p.n_items), dim3(512), smem, st, p);
+    char row[48];
+    FO1_LAUNCH(attn_row(row, "attn_fwd32", HD, 256 / HPW, p), flops, (attn_fwd32_kernel<HD, HPW>), dim3(p.Hq / HPW, p.n_items), dim3(512), smem, st, p);
     return FO1_OK;
 }
 
 template <int HD>
 static int launch_attn(const AttnParams& p, int q_block, hipStream_t st, double flops) {
-    char pname[48];
-    const char* name = "attn_fwd";
-    if (profile_enabled() && g_gemv_profile_shapes) {
-        snprintf(pname, sizeof pname, "attn_fwd hd%d q%d items%d heads%d%s", HD, q_block, p.n_items, p.Hq, p.causal ? " causal" : "");
-        name = pname;
-    }
+    char row[48];
+    const char* name = attn_row(row, "attn_fwd", HD, q_block, p);
     if (q_block == 16)
         FO1_LAUNCH(name, flops, (attn_fwd_kernel<HD, 1>), dim3(p.n_items, p.Hq), dim3(64), 0, st, p);
     else if (q_block == 32)
@@ -1360,6 +1387,39 @@ static int launch_attn(const AttnParams& p, int q_block, hipStream_t st, double 
     else
         FO1_LAUNCH(name, flops, (attn_fwd_kernel<HD, 4>), dim3(p.n_items, p.Hq), dim3(256), 0, st, p);
     return FO1_OK;
+}
+
+// What the kernels of the prefill entries need of their operands (16-byte Q / K loads, 8-byte V^T loads and O stores); `who`: the entry the message names
+static int check_attn_operands(const char* who, const AttnParams& p, int n_kv_heads) {
+    FO1_CHECK_ARG(p.Q && p.K && p.VT && p.O && p.items, "%s: NULL operand", who);
+    FO1_CHECK_ARG(p.n_items > 0 && p.Hq > 0 && n_kv_heads > 0 && p.Hq % n_kv_heads == 0, "%s: bad head / item counts", who);
+    FO1_CHECK_ARG(p.q_tok % 8 == 0 && p.q_head % 8 == 0 && p.k_tok % 8 == 0 && p.k_head % 8 == 0, "%s: Q/K strides must be multiples of 8 elements", who);
+    FO1_CHECK_ARG(p.vt_row % 4 == 0 && p.o_tok % 4 == 0 && p.o_head % 4 == 0, "%s: V^T / O strides must be multiples of 4 elements", who);
+    FO1_CHECK_ARG(((uintptr_t)p.Q & 15) == 0 && ((uintptr_t)p.K & 15) == 0 && ((uintptr_t)p.VT & 7) == 0 && ((uintptr_t)p.O & 7) == 0, "%s: misaligned operand", who);
+    return FO1_OK;
+}
+
+// What the decode entries check alike (`operands`: the entry's own NULL test; q_seq_stride 0: one sequence)
+static int check_decode_operands(const char* who, bool operands, long long k_tok, long long k_head, long long vt_row, long long q_seq_stride,
+                                 int n_q_heads, int n_kv_heads, int head_dim, size_t workspace_bytes, size_t workspace_need) {
+    FO1_CHECK_ARG(operands, "%s: NULL operand", who);
+    FO1_CHECK_ARG(head_dim == 128, "%s: head_dim %d not built (128)", who, head_dim);
+    FO1_CHECK_ARG(n_q_heads % n_kv_heads == 0 && n_q_heads / n_kv_heads <= 16, "%s: at most 16 query heads per KV head", who);
+    FO1_CHECK_ARG(vt_row % 4 == 0 && k_tok % 8 == 0 && k_head % 8 == 0 && q_seq_stride % 8 == 0, "%s: bad strides", who);
+    if (workspace_bytes < workspace_need) return set_err(FO1_ERR_WORKSPACE, "%s: workspace too small", who);
+    return FO1_OK;
+}
+
+// The split-KV (PARTIAL) launch of the decode entries: one item per chunk of kv_chunk keys and KV head; the query heads that share the
+// KV head are the item's "queries" (rows of q_tok = head_dim elements), the partials go to `workspace`.  The entry adds where the key
+// range comes from: dyn_kv_len (one sequence) or seq_state with its strides (a batch).
+static AttnParams decode_split_params(const void* q, const void* kcache, long long k_tok, long long k_head, const void* vtcache, long long vt_row,
+                                      int n_q_heads, int n_kv_heads, int head_dim, float scale, void* workspace, int n_items, int kv_chunk) {
+    const int group = n_q_heads / n_kv_heads;
+    AttnParams p(q, head_dim, (long long)group * head_dim, kcache, k_tok, k_head, vtcache, vt_row, nullptr, 0, 0, nullptr, n_items, n_kv_heads,
+                 n_kv_heads, scale);
+    p.part = (float*)workspace; p.kv_chunk = kv_chunk; p.q_range_end = group;
+    return p;
 }
 
 }  // namespace fo1
@@ -1375,28 +1435,14 @@ static int attention_entry(const void* Q, long long q_tok_stride, long long q_he
                        const float* bias, int wlen, int sw_ws, int sw_shift, int sw_nwy, int sw_nwx, const int32_t* prefix_ranges = nullptr) {
     using namespace fo1;
     if (n_items == 0) return FO1_OK;
-    FO1_CHECK_ARG(Q && K && VT && O && items, "attention: NULL operand");
-    FO1_CHECK_ARG(n_items > 0 && n_q_heads > 0 && n_kv_heads > 0 && n_q_heads % n_kv_heads == 0, "attention: bad head counts");
+    AttnParams p(Q, q_tok_stride, q_head_stride, K, k_tok_stride, k_head_stride, VT, vt_row_stride, O, o_tok_stride, o_head_stride, items, n_items,
+                 n_q_heads, n_kv_heads, scale);
+    if (int rc = check_attn_operands("attention", p, n_kv_heads)) return rc;
     FO1_CHECK_ARG(head_dim == 32 || head_dim == 80 || head_dim == 128, "attention: head_dim %d not built (32, 80, 128)", head_dim);
     FO1_CHECK_ARG(q_block == 16 || q_block == 32 || q_block == 64 || q_block == 128 || q_block == 256,
                   "attention: q_block %d must be 16, 32, 64 (16x16 MFMA form) or 128, 256 (32x32 form)", q_block);
-    FO1_CHECK_ARG(q_tok_stride % 8 == 0 && q_head_stride % 8 == 0 && k_tok_stride % 8 == 0 && k_head_stride % 8 == 0,
-                  "attention: Q/K strides must be multiples of 8 elements");
-    FO1_CHECK_ARG(vt_row_stride % 4 == 0 && o_tok_stride % 4 == 0 && o_head_stride % 4 == 0,
-                  "attention: V^T / O strides must be multiples of 4 elements");
-    FO1_CHECK_ARG(((uintptr_t)Q & 15) == 0 && ((uintptr_t)K & 15) == 0 && ((uintptr_t)VT & 7) == 0 && ((uintptr_t)O & 7) == 0,
-                  "attention: misaligned operand");
-    AttnParams p;
-    p.Q = (const uint16_t*)Q; p.q_tok = q_tok_stride; p.q_head = q_head_stride;
-    p.K = (const uint16_t*)K; p.k_tok = k_tok_stride; p.k_head = k_head_stride;
-    p.VT = (const uint16_t*)VT; p.vt_row = vt_row_stride;
-    p.O = (uint16_t*)O; p.o_tok = o_tok_stride; p.o_head = o_head_stride;
-    p.items = (const AttnItem*)items;
     p.items2 = (const int2*)prefix_ranges;
-    p.n_items = n_items; p.Hq = n_q_heads; p.group = n_q_heads / n_kv_heads;
-    p.scale = scale; p.causal = causal; p.q_row_base = (const int*)q_row_base;
-    p.part = nullptr; p.dyn_kv_len = nullptr; p.kv_chunk = 0; p.q_range_end = 0; p.part_tiles = 0; p.grid_batch = 0;
-    p.seq_state = nullptr; p.q_seq_stride = 0; p.part_seq_stride = 0;
+    p.causal = causal; p.q_row_base = (const int*)q_row_base;
     p.bias = bias; p.wlen = wlen; p.sw_ws = sw_ws; p.sw_shift = sw_shift; p.sw_nwy = sw_nwy; p.sw_nwx = sw_nwx;
     hipStream_t st = (hipStream_t)stream;
     if (q_block >= 128) {
@@ -1427,41 +1473,29 @@ int fo1_attention_bf16(const void* Q, long long q_tok_stride, long long q_head_s
                            q_block, n_q_heads, n_kv_heads, head_dim, scale, causal, q_row_base, flops_hint, stream, nullptr, 0, 0, 0, 0, 0);
 }
 
-// fo1_attention_bf16 with a second key range per item (prefix_ranges: int32 [n_items][2] = [start, end), empty when start >= end) that
-// every query of the item attends in full, before its own (causal) range: several prompts over ONE image share the rows of their common
-// prefix (system text + the image tokens) — the prefix rows run through the layer once, every prompt's remaining rows attend
-// [prefix | own rows].  The prefix rows must precede the item's rows in the index space.  (The reference runs the whole model once per
-// prompt, mm_utils.py:600 caps a prompt at 100 region features: BASELINE configs[4]'s 300 proposals are three such prompts.)
 int fo1_attention_windows_bf16(const void* Q, long long q_tok_stride, long long q_head_stride, const void* K, long long k_tok_stride,
                                 long long k_head_stride, const void* VT, long long vt_row_stride, void* O, long long o_tok_stride, long long o_head_stride,
                                 long long o_rows, const int32_t* items, int n_items, int n_q_heads, int n_kv_heads, int head_dim, float scale,
                                 double flops_hint, void* stream) {
     using namespace fo1;
     if (n_items == 0) return FO1_OK;
-    FO1_CHECK_ARG(Q && K && VT && O && items, "attention_windows: NULL operand");
+    const AttnParams p(Q, q_tok_stride, q_head_stride, K, k_tok_stride, k_head_stride, VT, vt_row_stride, O, o_tok_stride, o_head_stride, items, n_items,
+                       n_q_heads, n_kv_heads, scale);
+    if (int rc = check_attn_operands("attention_windows", p, n_kv_heads)) return rc;
     FO1_CHECK_ARG(head_dim == 80, "attention_windows: built for head dim 80 (got %d)", head_dim);
-    FO1_CHECK_ARG(n_items > 0 && n_q_heads > 0 && n_kv_heads > 0 && n_q_heads % n_kv_heads == 0 && n_q_heads <= 65535, "attention_windows: bad head / item counts");
-    FO1_CHECK_ARG(q_tok_stride % 8 == 0 && q_head_stride % 8 == 0 && k_tok_stride % 8 == 0 && k_head_stride % 8 == 0 && vt_row_stride % 4 == 0 &&
-                  o_tok_stride % 4 == 0 && o_head_stride % 4 == 0, "attention_windows: strides (Q / K: multiples of 8 elements, V^T / O: of 4)");
-    FO1_CHECK_ARG(((uintptr_t)Q & 15) == 0 && ((uintptr_t)K & 15) == 0 && ((uintptr_t)VT & 7) == 0 && ((uintptr_t)O & 7) == 0, "attention_windows: misaligned operand");
+    FO1_CHECK_ARG(n_q_heads <= 65535, "attention_windows: the heads walk grid.y: at most 65535 (got %d)", n_q_heads);
     const long long o_bytes = (o_rows - 1) * o_tok_stride * 2 + ((long long)(n_q_heads - 1) * o_head_stride + head_dim) * 2;
     FO1_CHECK_ARG(o_rows > 0 && o_bytes <= (1ll << 31), "attention_windows: the output spans %lld bytes (32-bit store offsets: at most 2 GiB)", o_bytes);
-    AttnParams p;
-    p.Q = (const uint16_t*)Q; p.q_tok = q_tok_stride; p.q_head = q_head_stride;
-    p.K = (const uint16_t*)K; p.k_tok = k_tok_stride; p.k_head = k_head_stride;
-    p.VT = (const uint16_t*)VT; p.vt_row = vt_row_stride;
-    p.O = (uint16_t*)O; p.o_tok = o_tok_stride; p.o_head = o_head_stride;
-    p.items = (const AttnItem*)items; p.items2 = nullptr;
-    p.n_items = n_items; p.Hq = n_q_heads; p.group = n_q_heads / n_kv_heads;
-    p.scale = scale; p.causal = 0; p.q_row_base = nullptr;
-    p.part = nullptr; p.dyn_kv_len = nullptr; p.kv_chunk = 0; p.q_range_end = 0; p.part_tiles = 0; p.grid_batch = 0;
-    p.seq_state = nullptr; p.q_seq_stride = 0; p.part_seq_stride = 0;
-    p.bias = nullptr; p.wlen = 0; p.sw_ws = 0; p.sw_shift = 0; p.sw_nwy = 0; p.sw_nwx = 0;
     constexpr int IPW = 4;
     FO1_LAUNCH("attn_win1", flops_hint, (attn_win1_kernel<80, IPW>), dim3(cdiv(n_items, IPW), n_q_heads), dim3(256), 0, (hipStream_t)stream, p, (uint32_t)o_bytes);
     return FO1_OK;
 }
 
+// fo1_attention_bf16 with a second key range per item (prefix_ranges: int32 [n_items][2] = [start, end), empty when start >= end) that
+// every query of the item attends in full, before its own (causal) range: several prompts over ONE image share the rows of their common
+// prefix (system text + the image tokens) — the prefix rows run through the layer once, every prompt's remaining rows attend
+// [prefix | own rows].  The prefix rows must precede the item's rows in the index space.  (The reference runs the whole model once per
+// prompt, mm_utils.py:600 caps a prompt at 100 region features: BASELINE configs[4]'s 300 proposals are three such prompts.)
 int fo1_attention_prefix_bf16(const void* Q, long long q_tok_stride, long long q_head_stride,
                               const void* K, long long k_tok_stride, long long k_head_stride,
                               const void* VT, long long vt_row_stride,
@@ -1493,53 +1527,30 @@ int fo1_attention_window_bias_bf16(const void* Q, long long q_tok_stride, long l
 // ride as the query columns of the MFMA.  Chunk count follows the DEVICE-side kv length (state[0] + 1 keys), so the
 // launch is graph-replayable for every step; partial (O, m, l) are merged in a fixed order by a second kernel.
 size_t fo1_attention_decode_workspace_bytes(int max_kv_len, int n_kv_heads, int head_dim) {
-    return (size_t)fo1::cdiv(max_kv_len, 64) * n_kv_heads * 16 * (head_dim + 2) * sizeof(float);
+    return (size_t)fo1::attn_part_seq_floats(fo1::cdiv(max_kv_len, 64), n_kv_heads, head_dim) * sizeof(float);
 }
 
 int fo1_attention_decode_bf16(const void* q, const void* kcache, long long k_tok_stride, long long k_head_stride, const void* vtcache,
                               long long vt_row_stride, void* out, const int32_t* dyn_kv_len, int max_kv_len, int n_q_heads,
                               int n_kv_heads, int head_dim, float scale, void* workspace, size_t workspace_bytes, void* stream) {
     using namespace fo1;
-    FO1_CHECK_ARG(q && kcache && vtcache && out && dyn_kv_len && workspace, "attention_decode: NULL operand");
-    FO1_CHECK_ARG(head_dim == 128, "attention_decode: head_dim %d not built (128)", head_dim);
-    FO1_CHECK_ARG(n_q_heads % n_kv_heads == 0 && n_q_heads / n_kv_heads <= 16, "attention_decode: at most 16 query heads per KV head");
-    FO1_CHECK_ARG(vt_row_stride % 4 == 0 && k_tok_stride % 8 == 0 && k_head_stride % 8 == 0, "attention_decode: bad strides");
-    if (workspace_bytes < fo1_attention_decode_workspace_bytes(max_kv_len, n_kv_heads, head_dim))
-        return set_err(FO1_ERR_WORKSPACE, "attention_decode: workspace too small");
-    static const AttnItem* one_item = nullptr;
-    const int group = n_q_heads / n_kv_heads;
+    if (int rc = check_decode_operands("attention_decode", q && kcache && vtcache && out && dyn_kv_len && workspace, k_tok_stride, k_head_stride,
+                                       vt_row_stride, 0, n_q_heads, n_kv_heads, head_dim, workspace_bytes,
+                                       fo1_attention_decode_workspace_bytes(max_kv_len, n_kv_heads, head_dim)))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
 #ifdef FO1_ENABLE_AB
     if (g_attn_decode_impl == 1) {
-        AttnDecParams d;
-        d.Q = (const uint16_t*)q; d.q_seq_stride = 0;
-        d.K = (const uint16_t*)kcache; d.k_tok = k_tok_stride; d.k_head = k_head_stride;
-        d.VT = (const uint16_t*)vtcache; d.vt_row = vt_row_stride;
-        d.O = (uint16_t*)out; d.o_seq_stride = 0;
-        d.part = (float*)workspace; d.seq_state = nullptr; d.dyn_kv_len = (const int*)dyn_kv_len;
-        d.n_kv_heads = n_kv_heads; d.group = group; d.scale = scale;
-        return launch_attn_decode_wg(d, max_kv_len, 1, n_q_heads, (hipStream_t)stream);
+        AttnDecParams d(q, 0, kcache, k_tok_stride, k_head_stride, vtcache, vt_row_stride, out, 0, workspace, nullptr, dyn_kv_len, n_q_heads, n_kv_heads, scale);
+        return launch_attn_decode_wg(d, max_kv_len, 1, st);
     }
 #endif
-    AttnParams p;
-    p.Q = (const uint16_t*)q; p.q_tok = head_dim; p.q_head = (long long)group * head_dim;   // "queries" walk the heads of a group
-    p.K = (const uint16_t*)kcache; p.k_tok = k_tok_stride; p.k_head = k_head_stride;
-    p.VT = (const uint16_t*)vtcache; p.vt_row = vt_row_stride;
-    p.O = nullptr; p.o_tok = 0; p.o_head = 0;
-    p.items = (const AttnItem*)workspace;   // unused in PARTIAL mode except q range below (read from a device constant)
-    p.n_items = cdiv(max_kv_len, 64); p.Hq = n_kv_heads; p.group = 1;
-    p.scale = scale; p.causal = 0; p.q_row_base = nullptr;
-    p.part = (float*)workspace; p.dyn_kv_len = (const int*)dyn_kv_len; p.kv_chunk = 64;
-    (void)one_item;
-    p.items = nullptr; p.items2 = nullptr;
-    p.q_range_end = group; p.part_tiles = 0; p.grid_batch = 0;
-    p.seq_state = nullptr; p.q_seq_stride = 0; p.part_seq_stride = 0;
-    p.bias = nullptr; p.wlen = 0; p.sw_ws = p.sw_shift = p.sw_nwy = p.sw_nwx = 0;
-    hipStream_t st = (hipStream_t)stream;
+    AttnParams p = decode_split_params(q, kcache, k_tok_stride, k_head_stride, vtcache, vt_row_stride, n_q_heads, n_kv_heads, head_dim, scale, workspace,
+                                       cdiv(max_kv_len, 64), 64);
+    p.dyn_kv_len = (const int*)dyn_kv_len;
     FO1_LAUNCH("attn_decode_split", (double)max_kv_len * n_kv_heads * head_dim * 4.0, (attn_fwd_kernel<128, 4, true>),
                dim3(p.n_items, n_kv_heads), dim3(256), 0, st, p);
-    FO1_LAUNCH("attn_decode_combine", (double)n_q_heads * head_dim * 8.0, attn_decode_combine_kernel<128>, dim3(n_q_heads), dim3(128), 0, st,
-               (const float*)workspace, (const int*)dyn_kv_len, 64, n_kv_heads, group, (uint16_t*)out, (const int*)nullptr, 0LL, 0LL);
-    return FO1_OK;
+    return launch_decode_combine<128>(p.part, 0, p.dyn_kv_len, nullptr, 1, p.kv_chunk, n_kv_heads, p.q_range_end, (uint16_t*)out, 0, st);
 }
 
 #ifdef FO1_ENABLE_AB      // include/fo1_ab.h: test / bench build only
@@ -1565,6 +1576,14 @@ FO1_AB_VAR g_attn_pool_chunk = 1024;     // A/B: fo1_attention_decode_set_pool_c
 FO1_AB_VAR g_attn_tiles_per_item = 2;    // 64-key tiles per item at 17..32 sequences (A/B: fo1_attention_decode_set_small_chunk(1 .. 8); profiles/r06_decode_attention_grid_order_ab.json: 1 / 2 / 3 / 4 tiles 2.96 / 2.89 / 2.91 / 2.98 ms per step at 25 sequences)
 FO1_AB_VAR g_attn_small_chunk = 64;      // A/B: fo1_attention_decode_set_small_chunk (<= 32 sequences)
 static inline int decode_batch_chunk(int batch) { return batch > 32 ? g_attn_pool_chunk : g_attn_small_chunk; }
+
+// How a batched decode launch cuts a slot of max_kv_len keys, and the partial floats per sequence that follow from it: the workspace size,
+// the launch and what the partials-only entry reports all read it here
+struct DecodeSplit { int chunk, n_chunks; long long part_seq_stride; };
+static inline DecodeSplit decode_batch_split(int batch, int max_kv_len, int n_kv_heads, int head_dim) {
+    const int chunk = decode_batch_chunk(batch), n_chunks = cdiv(max_kv_len, chunk);
+    return {chunk, n_chunks, attn_part_seq_floats(n_chunks, n_kv_heads, head_dim)};
+}
 }  // namespace fo1
 #ifdef FO1_ENABLE_AB
 int fo1_attention_decode_set_small_chunk(int keys) {
@@ -1583,7 +1602,7 @@ int fo1_attention_decode_set_pool_chunk(int keys) {
 }
 #endif
 size_t fo1_attention_decode_batch_workspace_bytes(int max_kv_len, int n_kv_heads, int head_dim, int batch) {
-    return (size_t)batch * fo1::cdiv(max_kv_len, fo1::decode_batch_chunk(batch)) * n_kv_heads * 16 * (head_dim + 2) * sizeof(float);
+    return (size_t)batch * fo1::decode_batch_split(batch, max_kv_len, n_kv_heads, head_dim).part_seq_stride * sizeof(float);
 }
 
 static int attention_decode_batch_impl(const void* q, long long q_seq_stride, const void* kcache, long long k_tok_stride, long long k_head_stride,
@@ -1591,58 +1610,35 @@ static int attention_decode_batch_impl(const void* q, long long q_seq_stride, co
                                        int batch, int max_kv_len, int n_q_heads, int n_kv_heads, int head_dim, float scale, void* workspace,
                                        size_t workspace_bytes, void* stream, bool combine) {
     using namespace fo1;
-    FO1_CHECK_ARG(q && kcache && vtcache && (out || !combine) && state && workspace && batch >= 1, "attention_decode_batch: NULL operand");
-    FO1_CHECK_ARG(head_dim == 128, "attention_decode_batch: head_dim %d not built (128)", head_dim);
-    FO1_CHECK_ARG(n_q_heads % n_kv_heads == 0 && n_q_heads / n_kv_heads <= 16, "attention_decode_batch: at most 16 query heads per KV head");
-    FO1_CHECK_ARG(vt_row_stride % 4 == 0 && k_tok_stride % 8 == 0 && k_head_stride % 8 == 0 && q_seq_stride % 8 == 0, "attention_decode_batch: bad strides");
-    if (workspace_bytes < fo1_attention_decode_batch_workspace_bytes(max_kv_len, n_kv_heads, head_dim, batch))
-        return set_err(FO1_ERR_WORKSPACE, "attention_decode_batch: workspace too small");
-    const int group = n_q_heads / n_kv_heads;
+    if (int rc = check_decode_operands("attention_decode_batch", q && kcache && vtcache && (out || !combine) && state && workspace && batch >= 1,
+                                       k_tok_stride, k_head_stride, vt_row_stride, q_seq_stride, n_q_heads, n_kv_heads, head_dim, workspace_bytes,
+                                       fo1_attention_decode_batch_workspace_bytes(max_kv_len, n_kv_heads, head_dim, batch)))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
 #ifdef FO1_ENABLE_AB
     // the A/B kernels write the output rows (or their own partial layout): the partials-only entry (combine false, out null) keeps the split
     // kernel below, whose layout fo1_gemv_attn_combine_bf16 reads
     if (combine && g_attn_decode_impl == 1) {
-        AttnDecParams d;
-        d.Q = (const uint16_t*)q; d.q_seq_stride = q_seq_stride;
-        d.K = (const uint16_t*)kcache; d.k_tok = k_tok_stride; d.k_head = k_head_stride;
-        d.VT = (const uint16_t*)vtcache; d.vt_row = vt_row_stride;
-        d.O = (uint16_t*)out; d.o_seq_stride = out_seq_stride;
-        d.part = (float*)workspace; d.seq_state = (const int*)state; d.dyn_kv_len = nullptr;
-        d.n_kv_heads = n_kv_heads; d.group = group; d.scale = scale;
-        return launch_attn_decode_wg(d, max_kv_len, batch, n_q_heads, (hipStream_t)stream);
+        AttnDecParams d(q, q_seq_stride, kcache, k_tok_stride, k_head_stride, vtcache, vt_row_stride, out, out_seq_stride, workspace, state, nullptr,
+                        n_q_heads, n_kv_heads, scale);
+        return launch_attn_decode_wg(d, max_kv_len, batch, st);
     }
     if (combine && g_attn_decode_impl == 2) {
-        AttnDecParams d;
-        d.Q = (const uint16_t*)q; d.q_seq_stride = q_seq_stride;
-        d.K = (const uint16_t*)kcache; d.k_tok = k_tok_stride; d.k_head = k_head_stride;
-        d.VT = (const uint16_t*)vtcache; d.vt_row = vt_row_stride;
-        d.O = (uint16_t*)out; d.o_seq_stride = out_seq_stride;
-        d.part = nullptr; d.part_seq_stride = 0; d.seq_state = (const int*)state; d.dyn_kv_len = nullptr;
-        d.n_kv_heads = n_kv_heads; d.group = group; d.scale = scale; d.split_keys = 0; d.n_splits = 1;
-        return launch_attn_decode_ws(d, max_kv_len, batch, (hipStream_t)stream);
+        AttnDecParams d(q, q_seq_stride, kcache, k_tok_stride, k_head_stride, vtcache, vt_row_stride, out, out_seq_stride, nullptr, state, nullptr,
+                        n_q_heads, n_kv_heads, scale);
+        return launch_attn_decode_ws(d, max_kv_len, batch, st);
     }
 #endif
-    AttnParams p;
-    p.Q = (const uint16_t*)q; p.q_tok = head_dim; p.q_head = (long long)group * head_dim;
-    p.K = (const uint16_t*)kcache; p.k_tok = k_tok_stride; p.k_head = k_head_stride;
-    p.VT = (const uint16_t*)vtcache; p.vt_row = vt_row_stride;
-    p.O = nullptr; p.o_tok = 0; p.o_head = 0;
-    p.items = nullptr; p.items2 = nullptr;
-    const int chunk = decode_batch_chunk(batch);
+    const DecodeSplit sp = decode_batch_split(batch, max_kv_len, n_kv_heads, head_dim);
     // 17..32 sequences: an item walks 2 tiles of 64 keys and writes each tile's partial separately (see AttnParams.part_tiles) — half the
     // workgroups, the next tile's loads under the current tile's arithmetic, the SAME partials as one-tile items (the batch invariance holds)
     // (not with ONE chunk: that launch writes the normalised rows itself, and the per-tile partial form returns before that store)
-    const int n_chunks = cdiv(max_kv_len, chunk);
-    const int ptiles = (batch > 16 && batch <= 32 && chunk == 64 && combine && n_chunks > 1) ? g_attn_tiles_per_item : 1;
-    p.n_items = cdiv(n_chunks, ptiles); p.Hq = n_kv_heads; p.group = 1;
-    p.scale = scale; p.causal = 0; p.q_row_base = nullptr;
-    p.part = (float*)workspace; p.dyn_kv_len = nullptr; p.kv_chunk = chunk * ptiles;
-    p.q_range_end = group; p.part_tiles = ptiles; p.grid_batch = batch;
-    p.seq_state = (const int*)state; p.q_seq_stride = q_seq_stride;
-    p.part_seq_stride = (long long)n_chunks * n_kv_heads * 16 * (head_dim + 2);
-    p.bias = nullptr; p.wlen = 0; p.sw_ws = p.sw_shift = p.sw_nwy = p.sw_nwx = 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (n_chunks == 1 && combine) {       // one chunk per (sequence, KV head) — the pool's slots, or a short context at any batch size -> rows written by the split kernel itself, no combine launch
+    const int ptiles = (batch > 16 && batch <= 32 && sp.chunk == 64 && combine && sp.n_chunks > 1) ? g_attn_tiles_per_item : 1;
+    AttnParams p = decode_split_params(q, kcache, k_tok_stride, k_head_stride, vtcache, vt_row_stride, n_q_heads, n_kv_heads, head_dim, scale, workspace,
+                                       cdiv(sp.n_chunks, ptiles), sp.chunk * ptiles);
+    p.part_tiles = ptiles; p.grid_batch = batch;
+    p.seq_state = (const int*)state; p.q_seq_stride = q_seq_stride; p.part_seq_stride = sp.part_seq_stride;
+    if (sp.n_chunks == 1 && combine) {       // one chunk per (sequence, KV head) — the pool's slots, or a short context at any batch size -> rows written by the split kernel itself, no combine launch
         p.O = (uint16_t*)out; p.o_tok = out_seq_stride; p.o_head = head_dim;
         FO1_LAUNCH("attn_decode_one_chunk", (double)batch * max_kv_len * n_kv_heads * head_dim * 4.0, (attn_fwd_kernel<128, 4, true>),
                    dim3(n_kv_heads * batch), dim3(256), 0, st, p);
@@ -1651,10 +1647,7 @@ static int attention_decode_batch_impl(const void* q, long long q_seq_stride, co
     FO1_LAUNCH("attn_decode_split", (double)batch * max_kv_len * n_kv_heads * head_dim * 4.0, (attn_fwd_kernel<128, 4, true>),
                dim3(p.n_items * n_kv_heads * batch), dim3(256), 0, st, p);
     if (!combine) return FO1_OK;       // the consumer sums the partials itself (fo1_gemv_attn_combine_bf16)
-    FO1_LAUNCH("attn_decode_combine", (double)batch * n_q_heads * head_dim * 8.0, attn_decode_combine_kernel<128>, dim3(n_q_heads, batch), dim3(128), 0,
-               st, (const float*)workspace, (const int*)nullptr, chunk, n_kv_heads, group, (uint16_t*)out, (const int*)state, p.part_seq_stride,
-               out_seq_stride);
-    return FO1_OK;
+    return launch_decode_combine<128>(p.part, p.part_seq_stride, nullptr, p.seq_state, batch, sp.chunk, n_kv_heads, p.q_range_end, (uint16_t*)out, out_seq_stride, st);
 }
 
 int fo1_attention_decode_batch_bf16(const void* q, long long q_seq_stride, const void* kcache, long long k_tok_stride, long long k_head_stride,
@@ -1673,9 +1666,9 @@ int fo1_attention_decode_batch_partials_bf16(const void* q, long long q_seq_stri
                                              int n_q_heads, int n_kv_heads, int head_dim, float scale, void* workspace, size_t workspace_bytes,
                                              int* kv_chunk_out, long long* part_seq_stride_out, void* stream) {
     FO1_CHECK_ARG(kv_chunk_out && part_seq_stride_out, "attention_decode_batch_partials: NULL output");
-    const int chunk = fo1::decode_batch_chunk(batch);
-    *kv_chunk_out = chunk;
-    *part_seq_stride_out = (long long)fo1::cdiv(max_kv_len, chunk) * n_kv_heads * 16 * (head_dim + 2);
+    const fo1::DecodeSplit sp = fo1::decode_batch_split(batch, max_kv_len, n_kv_heads, head_dim);
+    *kv_chunk_out = sp.chunk;
+    *part_seq_stride_out = sp.part_seq_stride;
     return attention_decode_batch_impl(q, q_seq_stride, kcache, k_tok_stride, k_head_stride, vtcache, vt_row_stride, nullptr, 0, state, batch, max_kv_len,
                                        n_q_heads, n_kv_heads, head_dim, scale, workspace, workspace_bytes, stream, false);
 }

@@ -31,6 +31,15 @@ struct GemvBParams {
     int attn_chunk = 0, attn_n_kv = 0, attn_group = 0;
 };
 
+// The split-KV partials of the decode attention, fp32 [chunks][n_kv_heads][ATTN_PART_ROWS][head_dim + 2] per sequence: a row per query head
+// of the KV head's group (the MFMA's 16 query columns: at most 16 query heads per KV head) = the unnormalised O row, then m (base 2) and l.
+// Written by attn_fwd_kernel<128, 4, PARTIAL> (and the A/B attn_decode_wg_kernel), read by attn_combine_row's two callers.
+constexpr int ATTN_PART_ROWS = 16;
+constexpr int attn_part_row_floats(int head_dim) { return head_dim + 2; }
+constexpr long long attn_part_seq_floats(int chunks, int n_kv_heads, int head_dim) {
+    return (long long)chunks * n_kv_heads * ATTN_PART_ROWS * attn_part_row_floats(head_dim);
+}
+
 // One (query head, 8 consecutive head-dim elements) of the split-KV combine: out[d] = sum_s exp(m_s - M) O_s[d] / sum_s exp(m_s - M) l_s over
 // the chunks in ascending order — THE arithmetic of attn_decode_combine_kernel (attention.hip), which calls it with ND = 1; the decode GEMV's
 // fused prologue calls it with ND = 8.  Explicit fmaf: both callers round identically whatever the contraction setting.

@@ -289,8 +289,8 @@ __global__ __launch_bounds__(GM_NT) void gemv_mfma_kernel(const GemvBParams p, c
                     const int kvh = head / p.attn_group, slot = head - kvh * p.attn_group;
                     const int n_valid = (stt[0] + 1 - stt[2] + p.attn_chunk - 1) / p.attn_chunk;
                     float v[8];
-                    attn_combine_row<8>(p.attn_part + (long long)m0 * p.attn_part_seq_stride + ((long long)kvh * 16 + slot) * 130,
-                                        (long long)p.attn_n_kv * 16 * 130, n_valid, d0, v);
+                    attn_combine_row<8>(p.attn_part + (long long)m0 * p.attn_part_seq_stride + ((long long)kvh * ATTN_PART_ROWS + slot) * attn_part_row_floats(128),
+                                        attn_part_seq_floats(1, p.attn_n_kv, 128), n_valid, d0, v);
                     o.x = pack_bf16x2(v[0], v[1]); o.y = pack_bf16x2(v[2], v[3]); o.z = pack_bf16x2(v[4], v[5]); o.w = pack_bf16x2(v[6], v[7]);
                 }
             }

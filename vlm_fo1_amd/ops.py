@@ -522,20 +522,27 @@ def argmax_rows(logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> tor
     return out
 
 
+def _decode_operands(q: torch.Tensor, kcache: torch.Tensor, vtcache: torch.Tensor, size_fn, *size_args):
+    """What the decode attention front ends share: the operand checks and the split-KV partials workspace of size_fn(*size_args) bytes ->
+    (workspace, the cache arguments (K, k_tok_stride, k_head_stride, V^T, vt_row_stride) and the tail (workspace, its bytes, stream) of the C entry)."""
+    _chk(q, "q"); _chk(kcache, "kcache"); _chk(vtcache, "vtcache")
+    assert kcache.dim() == 3
+    ws = _workspace("attn_decode", q.device, size_fn(*size_args))
+    pv, ldv, _, _ = _rows(vtcache, "vtcache")
+    return ws, (kcache.data_ptr(), kcache.stride(1), kcache.stride(0), pv, ldv), (ws.data_ptr(), ws.numel(), _stream())
+
+
 def attention_decode(q: torch.Tensor, kcache: torch.Tensor, vtcache: torch.Tensor, kv_len_dev: torch.Tensor, max_kv_len: int,
                      n_q_heads: int, n_kv_heads: int, head_dim: int, scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One new token (q [1, n_q_heads*head_dim]) against the cache; kv_len_dev = device int32 scalar holding the
     number of keys to attend (cache position + 1)."""
-    _chk(q, "q"); _chk(kcache, "kcache"); _chk(vtcache, "vtcache")
-    assert kv_len_dev.dtype == torch.int32 and kcache.dim() == 3 and q.shape[0] == 1
-    need = _L.load().fo1_attention_decode_workspace_bytes(max_kv_len, n_kv_heads, head_dim)
-    ws = _workspace("attn_decode", q.device, need)
+    assert kv_len_dev.dtype == torch.int32 and q.shape[0] == 1
+    lib = _L.load()
+    _, cache, tail = _decode_operands(q, kcache, vtcache, lib.fo1_attention_decode_workspace_bytes, max_kv_len, n_kv_heads, head_dim)
     if out is None:
         out = torch.empty(1, n_q_heads * head_dim, dtype=torch.bfloat16, device=q.device)
-    pv, ldv, _, _ = _rows(vtcache, "vtcache")
-    rc = _L.load().fo1_attention_decode_bf16(q.data_ptr(), kcache.data_ptr(), kcache.stride(1), kcache.stride(0), pv, ldv, out.data_ptr(),
-                                             kv_len_dev.data_ptr(), max_kv_len, n_q_heads, n_kv_heads, head_dim, float(scale),
-                                             ws.data_ptr(), ws.numel(), _stream())
+    rc = lib.fo1_attention_decode_bf16(q.data_ptr(), *cache, out.data_ptr(), kv_len_dev.data_ptr(), max_kv_len, n_q_heads, n_kv_heads, head_dim,
+                                       float(scale), *tail)
     _L.check(rc, "fo1_attention_decode_bf16")
     return out
 
@@ -713,18 +720,14 @@ def gemv_batch(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = 
 def attention_decode_batch(q: torch.Tensor, kcache: torch.Tensor, vtcache: torch.Tensor, state: torch.Tensor, max_kv_len: int,
                            n_q_heads: int, n_kv_heads: int, head_dim: int, scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q [B, n_q_heads*head_dim] (one new token per sequence) against the slots described by state int32 [B, 8]."""
-    _chk(q, "q"); _chk(kcache, "kcache"); _chk(vtcache, "vtcache")
-    assert state.dtype == torch.int32 and state.is_contiguous() and kcache.dim() == 3
+    assert state.dtype == torch.int32 and state.is_contiguous()
     pq, ldq, B, _ = _rows(q, "q")
-    need = _L.load().fo1_attention_decode_batch_workspace_bytes(max_kv_len, n_kv_heads, head_dim, B)
-    ws = _workspace("attn_decode", q.device, need)
+    lib = _L.load()
+    _, cache, tail = _decode_operands(q, kcache, vtcache, lib.fo1_attention_decode_batch_workspace_bytes, max_kv_len, n_kv_heads, head_dim, B)
     if out is None:
         out = torch.empty(B, n_q_heads * head_dim, dtype=torch.bfloat16, device=q.device)
     po, ldo, _, _ = _rows(out, "out")
-    pv, ldv, _, _ = _rows(vtcache, "vtcache")
-    rc = _L.load().fo1_attention_decode_batch_bf16(pq, ldq, kcache.data_ptr(), kcache.stride(1), kcache.stride(0), pv, ldv, po, ldo,
-                                                   state.data_ptr(), B, max_kv_len, n_q_heads, n_kv_heads, head_dim, float(scale),
-                                                   ws.data_ptr(), ws.numel(), _stream())
+    rc = lib.fo1_attention_decode_batch_bf16(pq, ldq, *cache, po, ldo, state.data_ptr(), B, max_kv_len, n_q_heads, n_kv_heads, head_dim, float(scale), *tail)
     _L.check(rc, "fo1_attention_decode_batch_bf16")
     return out
 
@@ -732,16 +735,13 @@ def attention_decode_batch(q: torch.Tensor, kcache: torch.Tensor, vtcache: torch
 def attention_decode_batch_partials(q: torch.Tensor, kcache: torch.Tensor, vtcache: torch.Tensor, state: torch.Tensor, max_kv_len: int,
                                     n_q_heads: int, n_kv_heads: int, head_dim: int, scale: float):
     """The split-KV half of attention_decode_batch alone -> (partials workspace, floats per sequence, keys per chunk) for gemv_attn_combine."""
-    _chk(q, "q"); _chk(kcache, "kcache"); _chk(vtcache, "vtcache")
-    assert state.dtype == torch.int32 and state.is_contiguous() and kcache.dim() == 3
+    assert state.dtype == torch.int32 and state.is_contiguous()
     pq, ldq, B, _ = _rows(q, "q")
-    need = _L.load().fo1_attention_decode_batch_workspace_bytes(max_kv_len, n_kv_heads, head_dim, B)
-    ws = _workspace("attn_decode", q.device, need)
-    pv, ldv, _, _ = _rows(vtcache, "vtcache")
+    lib = _L.load()
+    ws, cache, (pws, ws_bytes, stream) = _decode_operands(q, kcache, vtcache, lib.fo1_attention_decode_batch_workspace_bytes, max_kv_len, n_kv_heads, head_dim, B)
     chunk, stride = ctypes.c_int(0), ctypes.c_longlong(0)
-    rc = _L.load().fo1_attention_decode_batch_partials_bf16(pq, ldq, kcache.data_ptr(), kcache.stride(1), kcache.stride(0), pv, ldv, state.data_ptr(), B,
-                                                            max_kv_len, n_q_heads, n_kv_heads, head_dim, float(scale), ws.data_ptr(), ws.numel(),
-                                                            ctypes.byref(chunk), ctypes.byref(stride), _stream())
+    rc = lib.fo1_attention_decode_batch_partials_bf16(pq, ldq, *cache, state.data_ptr(), B, max_kv_len, n_q_heads, n_kv_heads, head_dim, float(scale),
+                                                      pws, ws_bytes, ctypes.byref(chunk), ctypes.byref(stride), stream)
     _L.check(rc, "fo1_attention_decode_batch_partials_bf16")
     return ws, stride.value, chunk.value
 
@@ -988,23 +988,29 @@ def make_items(segments: Sequence[Sequence[int]], device, causal: bool = False, 
     return t
 
 
+def _qkv_rows(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor):
+    """The checked q / k / V^T operands of the prefill attention front ends -> (rows of q, (q ptr, ld), (k ptr, ld), (V^T ptr, ld))."""
+    _chk(q, "q"); _chk(k, "k"); _chk(vt, "vt")
+    pq, ldq, L, _ = _rows(q, "q")
+    pk, ldk, _, _ = _rows(k, "k")
+    pv, ldv, _, _ = _rows(vt, "vt")
+    return L, (pq, ldq), (pk, ldk), (pv, ldv)
+
+
 def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, items: torch.Tensor, n_q_heads: int, n_kv_heads: int,
               head_dim: int, scale: float, causal: bool, out: Optional[torch.Tensor] = None,
               flops: float = 0.0, qk_head_stride: Optional[int] = None) -> torch.Tensor:
     """q: [L, >= n_q_heads*head_dim] view (heads contiguous), k: [Lk, ...] view, vt: [n_kv_heads*head_dim, ld] (V^T).
     qk_head_stride: elements between consecutive heads of q and of k when they are not packed (the head-major q/k/v layout of
     qkv_proj_rope mode 1: 256).  Returns out [L, n_q_heads*head_dim]."""
-    _chk(q, "q"); _chk(k, "k"); _chk(vt, "vt")
     assert items.dtype == torch.int32 and items.is_contiguous() and items.device == q.device
-    pq, ldq, L, _ = _rows(q, "q")
-    pk, ldk, _, _ = _rows(k, "k")
-    pv, ldv, _, _ = _rows(vt, "vt")
+    L, rq, rk, rv = _qkv_rows(q, k, vt)
     if out is None:
         out = torch.empty(L, n_q_heads * head_dim, dtype=torch.bfloat16, device=q.device)
     po, ldo, _, _ = _rows(out, "out")
     hs = head_dim if qk_head_stride is None else int(qk_head_stride)
-    _check_attn32_extent(getattr(items, "q_block", 64), k.shape[0], ldk * 2)
-    rc = _L.load().fo1_attention_bf16(pq, ldq, hs, pk, ldk, hs, pv, ldv, po, ldo, head_dim,
+    _check_attn32_extent(getattr(items, "q_block", 64), k.shape[0], rk[1] * 2)
+    rc = _L.load().fo1_attention_bf16(*rq, hs, *rk, hs, *rv, po, ldo, head_dim,
                                       items.data_ptr(), items.shape[0], getattr(items, "q_block", 64), n_q_heads, n_kv_heads,
                                       head_dim, float(scale), 1 if causal else 0, None, float(flops), _stream())
     _L.check(rc, "fo1_attention_bf16")
@@ -1023,14 +1029,11 @@ def attention_windows(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, items:
                       flops: float = 0.0, qk_head_stride: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ops.attention (non-causal, q_block 64) for a work list of single-tile items (items.single_tile, see single_tile_items): the pipelined
     fo1_attention_windows_bf16, the same bits.  out: an optional [L, n_heads*head_dim] row-major view (any row stride) to write into."""
-    _chk(q, "q"); _chk(k, "k"); _chk(vt, "vt")
     assert items.dtype == torch.int32 and items.is_contiguous() and items.device == q.device and getattr(items, "single_tile", False)
-    pq, ldq, L, _ = _rows(q, "q")
-    pk, ldk, _, _ = _rows(k, "k")
-    pv, ldv, _, _ = _rows(vt, "vt")
+    L, rq, rk, rv = _qkv_rows(q, k, vt)
     out = _out_rows(out, L, n_heads * head_dim, q.device)
     hs = head_dim if qk_head_stride is None else int(qk_head_stride)
-    rc = _L.load().fo1_attention_windows_bf16(pq, ldq, hs, pk, ldk, hs, pv, ldv, out.data_ptr(), out.stride(0), head_dim, L, items.data_ptr(), items.shape[0],
+    rc = _L.load().fo1_attention_windows_bf16(*rq, hs, *rk, hs, *rv, out.data_ptr(), out.stride(0), head_dim, L, items.data_ptr(), items.shape[0],
                                               n_heads, n_heads, head_dim, float(scale), float(flops), _stream())
     _L.check(rc, "fo1_attention_windows_bf16")
     return out
@@ -1321,20 +1324,15 @@ def attention_strided(q: torch.Tensor, q_row0: int, k: torch.Tensor, vt: torch.T
     if q_row_base is not None:
         q_row0 = 0
     _check_attn32_extent(getattr(items, "q_block", 64), k.shape[1], k.stride(1) * 2)
+    lib = _L.load()
+    operands = (pq - q_row0 * ldq * 2, ldq, head_dim, k.data_ptr(), k.stride(1), k.stride(0), pv, ldv, po - q_row0 * ldo * 2, ldo, head_dim, items.data_ptr())
+    shape = (getattr(items, "q_block", 64), n_q_heads, n_kv_heads, head_dim, float(scale), 1 if causal else 0)
     if prefix_ranges is not None:      # items with a second (shared-prefix) key range: fo1_attention_prefix_bf16
         assert prefix_ranges.dtype == torch.int32 and prefix_ranges.is_contiguous() and prefix_ranges.shape == (items.shape[0], 2) and q_row_base is None
-        rc = _L.load().fo1_attention_prefix_bf16(pq - q_row0 * ldq * 2, ldq, head_dim, k.data_ptr(), k.stride(1), k.stride(0), pv, ldv,
-                                                 po - q_row0 * ldo * 2, ldo, head_dim, items.data_ptr(), prefix_ranges.data_ptr(), items.shape[0],
-                                                 getattr(items, "q_block", 64), n_q_heads, n_kv_heads, head_dim, float(scale), 1 if causal else 0,
-                                                 float(flops), _stream())
-        _L.check(rc, "fo1_attention_prefix_bf16")
-        return out
-    rc = _L.load().fo1_attention_bf16(pq - q_row0 * ldq * 2, ldq, head_dim, k.data_ptr(), k.stride(1), k.stride(0), pv, ldv,
-                                      po - q_row0 * ldo * 2, ldo, head_dim, items.data_ptr(),
-                                      n_items if n_items is not None else items.shape[0], getattr(items, "q_block", 64),
-                                      n_q_heads, n_kv_heads, head_dim, float(scale), 1 if causal else 0,
-                                      q_row_base.data_ptr() if q_row_base is not None else None, float(flops), _stream())
-    _L.check(rc, "fo1_attention_bf16")
+        _L.check(lib.fo1_attention_prefix_bf16(*operands, prefix_ranges.data_ptr(), items.shape[0], *shape, float(flops), _stream()), "fo1_attention_prefix_bf16")
+    else:
+        _L.check(lib.fo1_attention_bf16(*operands, n_items if n_items is not None else items.shape[0], *shape,
+                                        q_row_base.data_ptr() if q_row_base is not None else None, float(flops), _stream()), "fo1_attention_bf16")
     return out
 
 
@@ -1500,15 +1498,12 @@ def gather_rows_f32(table: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
 def attention_window_bias(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, items: torch.Tensor, n_heads: int, head_dim: int, scale: float,
                           bias: torch.Tensor, ws: int, shift: int, nwy: int, nwx: int, flops: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Swin W-MSA / SW-MSA over consecutive windows of ws*ws tokens (fo1_attention_window_bias_bf16); bias fp32 [heads, ws*ws, ws*ws]."""
-    _chk(q, "q"); _chk(k, "k"); _chk(vt, "vt")
     wlen = ws * ws
     if not bias.is_cuda or bias.dtype != torch.float32 or tuple(bias.shape) != (n_heads, wlen, wlen) or not bias.is_contiguous():
         raise TypeError("attention_window_bias: bias must be a contiguous fp32 GPU tensor [heads, ws*ws, ws*ws]")
-    pq, ldq, L, _ = _rows(q, "q")
-    pk, ldk, _, _ = _rows(k, "k")
-    pv, ldv, _, _ = _rows(vt, "vt")
+    L, rq, rk, rv = _qkv_rows(q, k, vt)
     out = _out_rows(out, L, n_heads * head_dim, q.device)
-    rc = _L.load().fo1_attention_window_bias_bf16(pq, ldq, head_dim, pk, ldk, head_dim, pv, ldv, out.data_ptr(), out.stride(0), head_dim, items.data_ptr(),
+    rc = _L.load().fo1_attention_window_bias_bf16(*rq, head_dim, *rk, head_dim, *rv, out.data_ptr(), out.stride(0), head_dim, items.data_ptr(),
                                                   items.shape[0], getattr(items, "q_block", 64), n_heads, head_dim, float(scale), bias.data_ptr(), wlen, ws,
                                                   shift, nwy, nwx, float(flops), _stream())
     _L.check(rc, "fo1_attention_window_bias_bf16")
