@@ -379,7 +379,7 @@ SWEEP: List[Case] = [
     _c("big-frag-swiglu", "p4<256,256> frag", 1025, 8200 * 2 - 16, 256, act=SW, bias=True, ldc_pad=4),
     _c("big-f32-falls-back", "glds<128,128>", 1300, 6656, 2048, bias=True, out_f32=True),
     _c("big-oddldc-falls-back", "glds<128,128>", 1300, 6656, 256, act=R, bias=True, ldc_pad=3),
-    # M <= 4: the GEMV hand-off (results: tests/test_decode_routes_gpu.py)
+    # M <= 4: the GEMV hand-off (results: tests/test_decode_linears_gpu.py)
     _c("gemv-handoff", "gemv", 4, 512, 512, bias=True),
     # fo1_gemm_bf16_partials: planes only
     _c("partials64x64", "ring<64,64,3> splitk planes s4", 33, 512, 1088, entry="partials", splits=4),

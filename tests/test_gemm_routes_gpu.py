@@ -13,7 +13,7 @@ strides, spare rows / a spare plane) and is held to:
 Bit-for-bit claims of the code: fo1_gemm_bf16_wtiled == fo1_gemm_bf16 on the same tile; the <128, 96> SwiGLU tile == the 128 x 128 ring;
 fo1_gemm_bf16 under split-K == the z-ordered fp32 sum of fo1_gemm_bf16_partials' planes through the same epilogue (no activation: bias,
 residual, fp32 out) where both take the 64 x 128 ring with the same plane count.
-The GEMV hand-off (M <= 4) is only asserted to happen; tests/test_decode_routes_gpu.py checks its results.
+The GEMV hand-off (M <= 4) is only asserted to happen here; tests/test_decode_linears_gpu.py (cases handoff-*) holds its results to the per-element bound.
 
 Each case prints "ROUTE <claim> <case>: <profile rows> worst <max |got - ref| / bound>"; test_zz_route_summary prints the worst per route."""
 import pytest

@@ -581,7 +581,7 @@ int fo1_gemv_batch_set_impl(int impl) {
 }
 #endif   // FO1_ENABLE_AB
 
-// Batched decode projection: C[M<=16, N] = epilogue(rmsnorm?(x) @ W^T), weights streamed once for all M rows.
+// Batched decode projection: C[M<=32, N] = epilogue(rmsnorm?(x) @ W^T), weights streamed once for all M rows.
 // mode 0: bias -> bf16 -> + residual;  mode 1: interleaved SwiGLU (C has N/2 columns);  mode 2: fused QKV:
 //   bias -> bf16 -> mRoPE (table row state[m][1]) -> rotated q rows to C[m, 0 : n_q*128), rotated K row to kcache[kv][state[m][0]],
 //   V to the V^T cache column state[m][0].

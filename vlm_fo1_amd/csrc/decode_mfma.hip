@@ -527,6 +527,13 @@ static int launch_gemv_mfma_mp(const GemvBParams& p, int n_units, int nsteps, co
                                           : xrows * xpitch + (size_t)GM_NW * NB * 2048 + (size_t)2 * ng * GM_NW * NB * 1024 + 128;
     if (smem > 156 * 1024) return set_err(FO1_ERR_ARG, "gemv_batch: %zu B of LDS for M=%d K=%d (internal dispatch error)", smem, p.M, p.K);
     FO1_DYNAMIC_LDS_ONCE(156 * 1024, gemv_mfma_kernel<MM, MODE, NB, MP, HALF, R8>);
+    char pname[56];
+    if (profile_enabled() && g_gemv_profile_shapes) {
+        // the route: weight rows per unit, row blocks, single- / multi-piece K, h = HALF, r = R8, x = XR32 (the launch's own x rows staged)
+        snprintf(pname, sizeof pname, "gemv_mfma m%d %dx%d mode%d u%d nb%d %s %s%s%s", p.M, p.N, p.K, MODE, NB * ((HALF || R8) ? 8 : 16), NB, MP ? "mp" : "1p",
+                 HALF ? "h" : "", R8 ? "r" : "", (MM == 32 && MP && R8) ? "x" : ((HALF || R8) ? "" : "-"));
+        name = pname;
+    }
     // persistent workgroups, one per CU (x is staged / normalised once per workgroup when K fits one piece)
     const int grid = n_units < 256 ? n_units : 256;
     FO1_LAUNCH(name, (double)p.N * p.K * 2.0, (gemv_mfma_kernel<MM, MODE, NB, MP, HALF, R8>), dim3(grid), dim3(GM_NT), smem, st, p, n_units, nsteps);
@@ -553,12 +560,8 @@ static int dispatch_gemv_mfma(GemvBParams& p, int mode, hipStream_t st) {
     // for.  The shipped model (hidden 2048) never gets here; refuse instead of failing the launch.
     if (MM == 32 && nsteps > 32 && (mode != GB_PLAIN || p.N >= 8192))
         return set_err(FO1_ERR_ARG, "gemv_batch: M > 16 with K > 2048 is built for the plain few-row form only (M=%d N=%d K=%d mode=%d)", p.M, p.N, p.K, mode);
-    char pname[56];
+    // (under fo1_gemm_profile_shapes the launcher replaces the name by the shape and the route it instantiates)
     const char* name = mode == GB_SWIGLU ? "gemv_mfma_swiglu" : (mode == GB_QKV ? "gemv_mfma_qkv" : "gemv_mfma");
-    if (profile_enabled() && g_gemv_profile_shapes) {
-        snprintf(pname, sizeof pname, "gemv_mfma m%d %dx%d mode%d", p.M, p.N, p.K, mode);
-        name = pname;
-    }
     if (mode == GB_SWIGLU) return launch_gemv_mfma<MM, GB_SWIGLU, 2>(p, p.N / 32, nsteps, name, st);
     if constexpr (MM == 8) {
         // M <= 8: half of the MFMA's columns are free — 8-row units with the k-step pair in the two halves (same sums, see the header)

@@ -193,11 +193,11 @@ template <int MM>
 static int launch_gemv(const GemvParams& p, hipStream_t st) {
     char pname[48];
     const char* name = "gemv_bf16";
+    const bool ks = p.K >= 4096;   // measured: 2048x11008 at 2.2 TB/s with one wave per 4 rows (6 serial load rounds)
     if (profile_enabled() && g_gemv_profile_shapes) {
-        snprintf(pname, sizeof pname, "gemv %dx%dx%d a%d", p.M, p.N, p.K, p.act);
+        snprintf(pname, sizeof pname, "gemv %dx%dx%d a%d ks%d", p.M, p.N, p.K, p.act, (int)ks);
         name = pname;
     }
-    const bool ks = p.K >= 4096;   // measured: 2048x11008 at 2.2 TB/s with one wave per 4 rows (6 serial load rounds)
     if (p.act == 3) return ks ? launch_gemv2<MM, true, true>(p, name, st) : launch_gemv2<MM, true, false>(p, name, st);
     return ks ? launch_gemv2<MM, false, true>(p, name, st) : launch_gemv2<MM, false, false>(p, name, st);
 }
