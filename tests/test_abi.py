@@ -172,6 +172,116 @@ def test_attention_argument_errors():
     assert lib.fo1_attention_decode_batch_workspace_bytes(2048, 2, 128, 64) == 64 * 2 * per_chunk == 2129920
 
 
+def test_decode_linear_argument_errors():
+    """fo1_gemv_bf16, fo1_gemv_batch_bf16 and fo1_gemv_attn_combine_bf16 reject every bad call before any HIP call (fake 4096-aligned
+    integers stand for device pointers): the return code, the entry's prefix and the offending quantity in fo1_last_error() — the
+    entries' own checks, then the dispatch refusals of the MFMA route (both builds) and of the v_dot2 route (test / bench build)."""
+    lib = L.load()
+    X, W, C, R, NW, COS, SIN, ST, KC, VT, PART = [4096 * (i + 1) for i in range(11)]
+
+    def rejected(rc, prefix, *words, on=None):
+        msg = (on or lib).fo1_last_error()
+        assert rc == -1, (rc, msg)
+        assert msg.startswith(prefix + b":") and all(w in msg for w in words), msg
+
+    def gemv(**kw):     # fo1_gemv_bf16: one row of a 64 x 256 projection
+        a = dict(x=X, ldx=256, W=W, ldw=256, res=None, C=C, M=1, N=64, K=256, act=0, norm=None)
+        a.update(kw)
+        return lib.fo1_gemv_bf16(a["x"], a["ldx"], a["W"], a["ldw"], None, a["res"], a["N"], a["C"], a["N"], a["M"], a["N"], a["K"], a["act"],
+                                 a["norm"], 1e-6, None)
+
+    rejected(gemv(x=None), b"gemv", b"NULL")
+    rejected(gemv(W=None), b"gemv", b"NULL")
+    rejected(gemv(C=None), b"gemv", b"NULL")
+    rejected(gemv(M=0), b"gemv", b"bad shape", b"M=0")
+    rejected(gemv(M=5), b"gemv", b"bad shape", b"M=5")
+    rejected(gemv(K=12), b"gemv", b"bad shape", b"K=12")
+    rejected(gemv(ldx=260), b"gemv", b"bad shape")
+    rejected(gemv(ldw=260), b"gemv", b"bad shape")
+    rejected(gemv(M=4, K=20000, ldx=20000, ldw=20000), b"gemv", b"does not fit LDS", b"M=4", b"K=20000")
+    rejected(gemv(act=4), b"gemv", b"bad act")
+    rejected(gemv(act=6), b"gemv", b"bad act")
+    rejected(gemv(act=3, N=48), b"gemv", b"bad act/N")
+    rejected(gemv(act=3, res=R), b"gemv", b"bad act/N")
+    rejected(gemv(x=X + 8), b"gemv", b"misaligned")
+    rejected(gemv(W=W + 8), b"gemv", b"misaligned")
+    rejected(gemv(norm=NW + 8), b"gemv", b"misaligned")
+
+    def batch(on=None, **kw):    # fo1_gemv_batch_bf16: one row of a 64 x 256 projection; mode 2: 2 query heads, 1 KV head
+        a = dict(x=X, ldx=256, W=W, ldw=256, res=None, ldr=0, C=C, M=1, N=64, K=256, mode=0, norm=None, n_q=0, n_kv=0, cos=COS, sin=SIN,
+                 state=ST, kc=KC, vt=VT)
+        a.update(kw)
+        return (on or lib).fo1_gemv_batch_bf16(a["x"], a["ldx"], a["W"], a["ldw"], None, a["res"], a["ldr"], a["C"], a["N"], a["M"], a["N"],
+                                               a["K"], a["mode"], a["norm"], 1e-6, a["n_q"], a["n_kv"], a["cos"], a["sin"], a["state"],
+                                               a["kc"], 128 * 64, a["vt"], 64, None)
+
+    rejected(batch(x=None), b"gemv_batch", b"NULL")
+    rejected(batch(W=None), b"gemv_batch", b"NULL")
+    rejected(batch(C=None), b"gemv_batch", b"NULL")
+    rejected(batch(M=0), b"gemv_batch", b"bad shape", b"M=0")
+    rejected(batch(M=33), b"gemv_batch", b"bad shape", b"M=33")
+    rejected(batch(K=12), b"gemv_batch", b"bad shape", b"K=12")
+    rejected(batch(ldx=260), b"gemv_batch", b"bad shape")
+    rejected(batch(ldw=260), b"gemv_batch", b"bad shape")
+    rejected(batch(mode=3), b"gemv_batch", b"mode 3")
+    rejected(batch(mode=-1), b"gemv_batch", b"mode -1")
+    rejected(batch(x=X + 8), b"gemv_batch", b"misaligned")
+    rejected(batch(W=W + 8), b"gemv_batch", b"misaligned")
+    rejected(batch(norm=NW + 8), b"gemv_batch", b"misaligned")
+    rejected(batch(mode=1, N=48), b"gemv_batch", b"SwiGLU", b"N % 32")
+    rejected(batch(mode=1, res=R, ldr=64), b"gemv_batch", b"SwiGLU", b"no residual")
+    qkv = dict(mode=2, n_q=2, n_kv=1, N=512)
+    rejected(batch(**dict(qkv, N=384)), b"gemv_batch", b"QKV mode needs N")
+    rejected(batch(**dict(qkv, n_kv=0, N=256)), b"gemv_batch", b"QKV mode needs N")
+    for missing in ("cos", "sin", "state", "kc", "vt"):
+        rejected(batch(**dict(qkv, **{missing: None})), b"gemv_batch", b"QKV mode operands")
+    rejected(batch(**dict(qkv, res=R, ldr=512)), b"gemv_batch", b"QKV mode operands")
+    # the MFMA route's refusals (no HIP call before them)
+    rejected(batch(norm=NW, K=2112, ldx=2112, ldw=2112), b"gemv_batch", b"fused RMSNorm", b"K=2112")
+    rejected(batch(M=17, mode=1, K=2112, ldx=2112, ldw=2112), b"gemv_batch", b"M > 16 with K > 2048", b"M=17", b"K=2112", b"mode=1")
+    rejected(batch(M=17, N=8192, K=2112, ldx=2112, ldw=2112), b"gemv_batch", b"M > 16 with K > 2048", b"M=17", b"N=8192", b"K=2112")
+    # operands the MFMA route cannot move four at a time: the product library has no other kernel
+    assert lib._name.endswith("libfo1hip.so")
+    rejected(batch(N=66), b"gemv_batch", b"operands must be 8-byte aligned", b"N=66")
+    rejected(batch(res=R + 2, ldr=64), b"gemv_batch", b"operands must be 8-byte aligned")
+    with L.use_ab() as ab:     # the v_dot2 route of the test / bench build
+        try:
+            assert ab.fo1_gemv_batch_set_impl(0) == 0
+            rejected(batch(on=ab, M=9), b"gemv_batch", b"M <= 8", b"M=9", on=ab)
+            rejected(batch(on=ab, M=8, norm=NW, K=8448, ldx=8448, ldw=8448), b"gemv_batch", b"fused RMSNorm", b"K=8448", b"M=8", on=ab)
+            rejected(ab.fo1_gemv_batch_set_impl(2), b"gemv_batch_set_impl", b"2", on=ab)
+            rejected(ab.fo1_gemv_batch_set_rows_per_lane(2), b"gemv_batch_set_rows_per_lane", b"2", on=ab)
+        finally:
+            assert ab.fo1_gemv_batch_set_impl(1) == 0
+
+    def combine(**kw):  # fo1_gemv_attn_combine_bf16: 16 query / 2 KV heads (K = 2048), a 2048-feature o-projection
+        a = dict(part=PART, state=ST, chunk=256, n_q=16, n_kv=2, W=W, ldw=2048, res=R, ldr=2048, C=C, ldc=2048, M=1, N=2048)
+        a.update(kw)
+        return lib.fo1_gemv_attn_combine_bf16(a["part"], 1 << 20, a["state"], a["chunk"], a["n_q"], a["n_kv"], a["W"], a["ldw"], a["res"], a["ldr"],
+                                              a["C"], a["ldc"], a["M"], a["N"], None)
+
+    for missing in ("part", "state", "W", "C"):
+        rejected(combine(**{missing: None}), b"gemv_attn_combine", b"NULL")
+    rejected(combine(M=0), b"gemv_attn_combine", b"M=0")
+    rejected(combine(M=3), b"gemv_attn_combine", b"M=3")
+    rejected(combine(n_kv=0), b"gemv_attn_combine", b"heads 16 / 0")
+    rejected(combine(n_q=15), b"gemv_attn_combine", b"heads 15 / 2")
+    rejected(combine(n_q=17, n_kv=1, ldw=2176), b"gemv_attn_combine", b"heads 17 / 1")
+    rejected(combine(n_q=18, ldw=2304), b"gemv_attn_combine", b"heads 18 / 2", b"<= 2048")
+    rejected(combine(N=4100, ldc=4100, ldr=4100), b"gemv_attn_combine", b"N=4100")
+    rejected(combine(N=2046), b"gemv_attn_combine", b"N=2046")
+    rejected(combine(chunk=96), b"gemv_attn_combine", b"bad layout")
+    rejected(combine(chunk=0), b"gemv_attn_combine", b"bad layout")
+    rejected(combine(ldw=2052), b"gemv_attn_combine", b"bad layout")
+    rejected(combine(ldw=1024), b"gemv_attn_combine", b"bad layout")
+    rejected(combine(W=W + 8), b"gemv_attn_combine", b"bad layout")
+    rejected(combine(part=PART + 4), b"gemv_attn_combine", b"bad layout")
+    rejected(combine(ldr=2050), b"gemv_attn_combine", b"residual / output layout")
+    rejected(combine(ldr=1024), b"gemv_attn_combine", b"residual / output layout")
+    rejected(combine(res=R + 4), b"gemv_attn_combine", b"residual / output layout")
+    rejected(combine(ldc=1024), b"gemv_attn_combine", b"residual / output layout")
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(L, "_lib", None)
     monkeypatch.setattr(L, "LIB_PATH", str(tmp_path / "nope.so"))

@@ -446,6 +446,107 @@ def test_gemv_batch_rows_independent_of_batch(ab_library):
             L.load().fo1_gemv_batch_set_rows_per_lane(0)
 
 
+def test_dot2_launch_rows(ab_library):
+    """The v_dot2 dispatcher's route per (mode, units, M): the profile row `gemv_b m{M} {N}x{K} mode{mode} ks{ks} r{r}` — K split over the
+    workgroup's waves up to 1024 units (ks1, one row per lane), one unit per wave beyond (ks0, rows per lane 1 / 1 / 2 / 4 at M = 1 / 2 / 3 / 8,
+    1 under fo1_gemv_batch_set_rows_per_lane(1)); every launch within the bound of _gemv_batch_cases against the torch fp32 restatement;
+    row 0 launched alone has the bits of row 0 launched with 7 others — also at K = 8448, the smallest K that 8 sequences stage in two LDS
+    pieces (768 + 288 chunks) while one sequence keeps x resident and walks the same two segments."""
+    from test_ops_gpu import gemm_ref, rb
+    from vlm_fo1_amd import lib as L, ops
+    lib = L.load()
+    BF = torch.bfloat16
+    g = torch.Generator().manual_seed(21)
+    K, MS = 256, (1, 2, 3, 8)
+
+    def rnd(*shape, s=1.0):
+        return (torch.randn(*shape, generator=g) * s).to(BF).cuda()
+
+    def row_of(fn):
+        L.profile_rows()
+        L.profile(True)
+        try:
+            got = fn()
+            torch.cuda.synchronize()
+            rows = L.profile_rows()
+        finally:
+            L.profile(False)
+        assert len(rows) == 1 and rows[0]["calls"] == 1, rows
+        return got, rows[0]["name"]
+
+    def close(got, ref, what):
+        err = (got.float().cpu() - ref).abs().max().item()
+        print(f"{what}: max err {err:.4g}, bound {2e-2 * ref.abs().max().item() + 1e-3:.4g}")
+        assert err <= 2e-2 * ref.abs().max().item() + 1e-3, f"{what}: max err {err:.4g}"
+
+    x = rnd(8, K, s=0.5)
+    cases = []          # (mode, N, ks, launch(M) -> tuple of tensors whose first dimension or cache position is the sequence, refs(M))
+    for N, ks in ((8192, 1), (8200, 0)):
+        w, bias, res = rnd(N, K, s=0.05), rnd(N, s=0.1), rnd(8, N)
+        ref = gemm_ref(x, w, bias, res, 0)
+        cases.append((ops.GB_PLAIN, N, ks, lambda M, w=w, bias=bias, res=res: (ops.gemv_batch(x[:M].contiguous(), w, bias, res[:M].contiguous()),),
+                      lambda M, ref=ref: (ref[:M],)))
+    for N, ks in ((8192, 1), (8224, 0)):
+        wg, wu = rnd(N // 2, K, s=0.05).cpu(), rnd(N // 2, K, s=0.05).cpu()
+        wi = ops.interleave_gate_up(wg, wu).cuda()
+        ref = rb(rb(F.silu(rb(x.float().cpu() @ wg.float().t()))) * rb(x.float().cpu() @ wu.float().t()))
+        cases.append((ops.GB_SWIGLU, N, ks, lambda M, wi=wi: (ops.gemv_batch(x[:M].contiguous(), wi, mode=ops.GB_SWIGLU),), lambda M, ref=ref: (ref[:M],)))
+    H, KV, HD, rows = 2, 1, 128, 64
+    w, bias = rnd((H + 2 * KV) * HD, K, s=0.05), rnd((H + 2 * KV) * HD, s=0.1)
+    ang = torch.rand(rows, HD, generator=g) * 6.28
+    cos, sin = ang.cos().to(BF).cuda(), ang.sin().to(BF).cuda()
+    state = torch.zeros(8, 8, dtype=torch.int32)
+    state[:, 0] = torch.arange(8) * 7 + 3            # cache row
+    state[:, 1] = 60 - torch.arange(8) * 5           # rope-table row
+    pos = state[:, 0].long()
+    state = state.cuda()
+
+    def qkv_launch(M):
+        kc = torch.zeros(KV, rows, HD, dtype=BF, device="cuda")
+        vt = torch.zeros(KV * HD, rows, dtype=BF, device="cuda")
+        q = ops.gemv_batch(x[:M].contiguous(), w, bias, mode=ops.GB_QKV,
+                           qkv=dict(n_q=H, n_kv=KV, cos=cos, sin=sin, state=state[:M].contiguous(), kcache=kc, vtcache=vt))
+        return q, kc[:, pos[:M]].transpose(0, 1).reshape(M, -1), vt[:, pos[:M]].t()
+
+    qkv = gemm_ref(x, w, bias)
+    heads = qkv[:, :(H + KV) * HD].view(8, H + KV, HD)
+    a, b = heads[..., :64], heads[..., 64:]
+    cr, sr = cos.float().cpu()[state[:, 1].long().cpu()][:, None], sin.float().cpu()[state[:, 1].long().cpu()][:, None]
+    rot = rb(torch.cat([rb(a * cr[..., :64]) + rb(-b * sr[..., :64]), rb(b * cr[..., 64:]) + rb(a * sr[..., 64:])], -1))
+    qkv_refs = (rot[:, :H].reshape(8, -1), rot[:, H:].reshape(8, -1), qkv[:, (H + KV) * HD:])
+    cases.append((ops.GB_QKV, (H + 2 * KV) * HD, 1, qkv_launch, lambda M: tuple(r[:M] for r in qkv_refs)))
+
+    L.check(lib.fo1_gemv_batch_set_impl(0), "set_impl")
+    L.check(lib.fo1_gemm_profile_shapes(1), "profile_shapes")
+    try:
+        for mode, N, ks, launch, refs in cases:
+            alone = None
+            for M in MS:
+                got, row = row_of(lambda: launch(M))
+                r = (1, 1, 2, 4)[MS.index(M)] if ks == 0 else 1
+                assert row == f"gemv_b m{M} {N}x{K} mode{mode} ks{ks} r{r}", row
+                for t, ref, what in zip(got, refs(M), ("out", "K rows", "V^T columns")):
+                    close(t, ref, f"{row} {what}")
+                L.check(lib.fo1_gemv_batch_set_rows_per_lane(1), "set_rows_per_lane")
+                got1, row1 = row_of(lambda: launch(M))
+                L.check(lib.fo1_gemv_batch_set_rows_per_lane(0), "set_rows_per_lane")
+                assert row1 == f"gemv_b m{M} {N}x{K} mode{mode} ks{ks} r1", row1
+                for t, ref, what in zip(got1, refs(M), ("out", "K rows", "V^T columns")):
+                    close(t, ref, f"{row1} {what}")
+                alone = got if M == 1 else alone
+            for t1, t8, what in zip(alone, got, ("out", "K rows", "V^T columns")):
+                assert torch.equal(t1[0], t8[0]), f"mode {mode} {N}x{K}: {what} of sequence 0 alone differ from the launch of 8"
+        lib.fo1_gemm_profile_shapes(0)
+        xd, wd = rnd(8, 8448, s=0.5), rnd(64, 8448, s=0.05)
+        full = ops.gemv_batch(xd, wd)
+        assert torch.equal(ops.gemv_batch(xd[:1].contiguous(), wd)[0], full[0]), "64x8448: sequence 0 alone differs from the launch of 8"
+        close(full, gemm_ref(xd, wd), "gemv_b m8 64x8448")
+    finally:
+        lib.fo1_gemv_batch_set_rows_per_lane(0)
+        lib.fo1_gemm_profile_shapes(0)
+        lib.fo1_gemv_batch_set_impl(1)
+
+
 def test_decode_attention_rows_do_not_depend_on_the_batch_size_bitwise():
     """The split-KV decode attention writes 64-key partials whatever the launch: at 17..32 sequences an item walks FOUR tiles and writes each tile's
     partial separately (round 6), below that an item is one tile — a sequence's attention row is the same bits alone, in 16 and in 25."""

@@ -1083,7 +1083,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_wg_kernel(const AttnDecPa
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     e[r] = (s[kt][r] == -INFINITY) ? 0.f : __expf(s[kt][r] - m_new);
-                    e[r] = bf16_to_f32(f32_to_bf16(e[r]));      // sum what is multiplied into V: the bf16-rounded probabilities
+                    e[r] = round_bf16(e[r]);      // sum what is multiplied into V: the bf16-rounded probabilities
                     psum += e[r];
                 }
                 w[t * 2 + 0] = pack_bf16x2(e[0], e[1]);

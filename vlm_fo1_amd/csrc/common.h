@@ -47,6 +47,47 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
     typedef __attribute__((ext_vector_type(2))) __bf16 fo1_bf16x2;
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(fo1_f32x2{lo, hi}, fo1_bf16x2));
 }
+// the fp32 value of what a bf16 store would hold (the reference's intermediate tensors are bf16)
+__device__ __forceinline__ float round_bf16(float v) { return bf16_to_f32(f32_to_bf16(v)); }
+// 8 bf16 (one 16-byte chunk) <-> 8 floats
+__device__ __forceinline__ void unpack8(const uint4& u, float (&f)[8]) {
+    f[0] = bf16_lo(u.x); f[1] = bf16_hi(u.x); f[2] = bf16_lo(u.y); f[3] = bf16_hi(u.y);
+    f[4] = bf16_lo(u.z); f[5] = bf16_hi(u.z); f[6] = bf16_lo(u.w); f[7] = bf16_hi(u.w);
+}
+__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
+    return uint4{pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7])};
+}
+// sum over the 64 lanes of a wave (xor shuffles: every lane gets the total, the same bits in each)
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// acc + the dot product of two 16-byte chunks of bf16 as four v_dot2_f32_bf16 (pairs summed in fp32, in element order)
+__device__ __forceinline__ float dot8_dot2(const uint4& a, const uint4& b, float acc) {
+    typedef __attribute__((ext_vector_type(2))) __bf16 fo1_bf16x2;
+    acc = __builtin_amdgcn_fdot2_f32_bf16(*reinterpret_cast<const fo1_bf16x2*>(&a.x), *reinterpret_cast<const fo1_bf16x2*>(&b.x), acc, false);
+    acc = __builtin_amdgcn_fdot2_f32_bf16(*reinterpret_cast<const fo1_bf16x2*>(&a.y), *reinterpret_cast<const fo1_bf16x2*>(&b.y), acc, false);
+    acc = __builtin_amdgcn_fdot2_f32_bf16(*reinterpret_cast<const fo1_bf16x2*>(&a.z), *reinterpret_cast<const fo1_bf16x2*>(&b.z), acc, false);
+    acc = __builtin_amdgcn_fdot2_f32_bf16(*reinterpret_cast<const fo1_bf16x2*>(&a.w), *reinterpret_cast<const fo1_bf16x2*>(&b.w), acc, false);
+    return acc;
+}
+// streamed-once weights: non-temporal 16-byte load (MI355X_MICROARCH "nt-weights": -18 % issue-to-landed on a decode weight stream)
+__device__ __forceinline__ uint4 load_nt16(const uint16_t* p) {
+    typedef __attribute__((ext_vector_type(4))) unsigned int fo1_u32x4;
+    const fo1_u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const fo1_u32x4*>(p));
+    return uint4{v.x, v.y, v.z, v.w};
+}
+// One 16-byte chunk of Qwen2RMSNorm (modeling_qwen2_5_vl.py:126-140) given the row's rstd (fp32 variance): bf16(x * rstd), then * weight -> bf16 —
+// the reference's rounding points, which is why the decode linears' three fused prologues (gemv.hip, decode.hip, decode_mfma.hip) share this one.
+__device__ __forceinline__ uint4 rmsnorm_chunk(const uint4& v, const uint4& w, float rstd) {
+    uint4 o;
+    o.x = pack_bf16x2(bf16_lo(w.x) * round_bf16(bf16_lo(v.x) * rstd), bf16_hi(w.x) * round_bf16(bf16_hi(v.x) * rstd));
+    o.y = pack_bf16x2(bf16_lo(w.y) * round_bf16(bf16_lo(v.y) * rstd), bf16_hi(w.y) * round_bf16(bf16_hi(v.y) * rstd));
+    o.z = pack_bf16x2(bf16_lo(w.z) * round_bf16(bf16_lo(v.z) * rstd), bf16_hi(w.z) * round_bf16(bf16_hi(v.z) * rstd));
+    o.w = pack_bf16x2(bf16_lo(w.w) * round_bf16(bf16_lo(v.w) * rstd), bf16_hi(w.w) * round_bf16(bf16_hi(v.w) * rstd));
+    return o;
+}
 
 // Activations of the fused epilogues.  Their result is rounded to bf16 (8 significant bits) right away, so the hardware
 // approximations (v_exp_f32, v_rcp_f32: ~1 ulp of fp32) replace the library's expf / erff / IEEE division — ~6 instructions per

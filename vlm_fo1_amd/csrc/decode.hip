@@ -20,29 +20,6 @@
 
 namespace fo1 {
 
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-
-// streamed-once weights: non-temporal 16-byte load (MI355X_MICROARCH "nt-weights": -18 % issue-to-landed on a decode weight stream)
-__device__ __forceinline__ uint4 load_nt16(const uint16_t* p) {
-    const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
-    return uint4{v.x, v.y, v.z, v.w};
-}
-
-__device__ __forceinline__ float gb_round(float v) { return bf16_to_f32(f32_to_bf16(v)); }
-__device__ __forceinline__ float gb_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float dot8b(const uint4& w, const uint4& x, float acc) {
-    acc = __builtin_amdgcn_fdot2_f32_bf16(*reinterpret_cast<const bf16x2_t*>(&w.x), *reinterpret_cast<const bf16x2_t*>(&x.x), acc, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(*reinterpret_cast<const bf16x2_t*>(&w.y), *reinterpret_cast<const bf16x2_t*>(&x.y), acc, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(*reinterpret_cast<const bf16x2_t*>(&w.z), *reinterpret_cast<const bf16x2_t*>(&x.z), acc, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(*reinterpret_cast<const bf16x2_t*>(&w.w), *reinterpret_cast<const bf16x2_t*>(&x.w), acc, false);
-    return acc;
-}
-
 // One unit = 8 weight rows:  plain: 8 consecutive output features;  SwiGLU: 4 gate rows + their up partners 16 rows further
 // (16-row interleaved weights);  QKV: q/k heads -> 4 dims d and their rotary partners d + 64, v head -> 8 consecutive dims.
 // Lane mapping: lane l streams row (l >> 3) of the unit, 16-B chunk (l & 7) + 8 i of K — a load instruction covers 8 rows x 128
@@ -90,9 +67,9 @@ __global__ __launch_bounds__(256) void gemv_batch_kernel(const GemvBParams p) {
                 float ss = 0.f;
                 for (int c = lane; c < kpn; c += 64) {
                     const uint4 v = *reinterpret_cast<const uint4*>(&sx[(m * p.kp_chunks + c) * 8]);
-                    ss = dot8b(v, v, ss);
+                    ss = dot8_dot2(v, v, ss);
                 }
-                ss = gb_wave_sum(ss);
+                ss = wave_sum(ss);
                 if (lane == 0) s_rstd[m] = rsqrtf(ss / (float)p.K + p.norm_eps);
             }
             __syncthreads();
@@ -102,12 +79,7 @@ __global__ __launch_bounds__(256) void gemv_batch_kernel(const GemvBParams p) {
                 for (int m = 0; m < MM; ++m) {
                     const float rstd = s_rstd[m];
                     const uint4 v = *reinterpret_cast<const uint4*>(&sx[(m * p.kp_chunks + c) * 8]);
-                    uint4 o;
-                    o.x = pack_bf16x2(bf16_lo(w.x) * gb_round(bf16_lo(v.x) * rstd), bf16_hi(w.x) * gb_round(bf16_hi(v.x) * rstd));
-                    o.y = pack_bf16x2(bf16_lo(w.y) * gb_round(bf16_lo(v.y) * rstd), bf16_hi(w.y) * gb_round(bf16_hi(v.y) * rstd));
-                    o.z = pack_bf16x2(bf16_lo(w.z) * gb_round(bf16_lo(v.z) * rstd), bf16_hi(w.z) * gb_round(bf16_hi(v.z) * rstd));
-                    o.w = pack_bf16x2(bf16_lo(w.w) * gb_round(bf16_lo(v.w) * rstd), bf16_hi(w.w) * gb_round(bf16_hi(v.w) * rstd));
-                    *reinterpret_cast<uint4*>(&sx[(m * p.kp_chunks + c) * 8]) = o;
+                    *reinterpret_cast<uint4*>(&sx[(m * p.kp_chunks + c) * 8]) = rmsnorm_chunk(v, w, rstd);
                 }
             }
             __syncthreads();
@@ -149,7 +121,7 @@ __global__ __launch_bounds__(256) void gemv_batch_kernel(const GemvBParams p) {
                 for (int m = 0; m < MM; ++m) {
                     const uint4 xv = *reinterpret_cast<const uint4*>(&sx[(m * p.kp_chunks + xoff + c) * 8]);
 #pragma unroll
-                    for (int q = 0; q < RPL; ++q) acc[q][m] = dot8b(w[q][u], xv, acc[q][m]);
+                    for (int q = 0; q < RPL; ++q) acc[q][m] = dot8_dot2(w[q][u], xv, acc[q][m]);
                 }
             }
         }
@@ -264,7 +236,7 @@ __global__ __launch_bounds__(256) void gemv_batch_kernel(const GemvBParams p) {
                     if (f < p.N && m < p.M) {
                         float v = red[j * MM + m];
                         if (p.bias) v += bf16_to_f32(p.bias[f]);
-                        v = gb_round(v);
+                        v = round_bf16(v);
                         if (p.res) v += bf16_to_f32(p.res[(long long)m * p.ldr + f]);
                         p.C[(long long)m * p.ldc + f] = f32_to_bf16(v);
                     }
@@ -277,9 +249,9 @@ __global__ __launch_bounds__(256) void gemv_batch_kernel(const GemvBParams p) {
                         const int grow = (f >> 4) * 32 + (f & 15);
                         float g = red[j * MM + m], u = red[(4 + j) * MM + m];
                         if (p.bias) { g += bf16_to_f32(p.bias[grow]); u += bf16_to_f32(p.bias[grow + 16]); }
-                        g = gb_round(g);
-                        u = gb_round(u);
-                        p.C[(long long)m * p.ldc + f] = f32_to_bf16(gb_round(fo1_silu(g)) * u);
+                        g = round_bf16(g);
+                        u = round_bf16(u);
+                        p.C[(long long)m * p.ldc + f] = f32_to_bf16(round_bf16(fo1_silu(g)) * u);
                     }
                 }
             } else {   // GB_QKV
@@ -291,14 +263,14 @@ __global__ __launch_bounds__(256) void gemv_batch_kernel(const GemvBParams p) {
                             const int ra = head * 128 + d, rb_ = ra + 64;
                             float a = red[j * MM + m], b = red[(4 + j) * MM + m];
                             if (p.bias) { a += bf16_to_f32(p.bias[ra]); b += bf16_to_f32(p.bias[rb_]); }
-                            a = gb_round(a);                                                 // the bf16 q/k the unfused path stores
-                            b = gb_round(b);
+                            a = round_bf16(a);                                                 // the bf16 q/k the unfused path stores
+                            b = round_bf16(b);
                             const int* st = p.state + m * 8;
                             const long long trow = st[1];
                             const float ca = bf16_to_f32(p.cos_t[trow * 128 + d]), sa = bf16_to_f32(p.sin_t[trow * 128 + d]);
                             const float cb2 = bf16_to_f32(p.cos_t[trow * 128 + d + 64]), sb = bf16_to_f32(p.sin_t[trow * 128 + d + 64]);
-                            const uint16_t oa = f32_to_bf16(gb_round(a * ca) + gb_round(-b * sa));   // rotate_half, three bf16 roundings
-                            const uint16_t ob = f32_to_bf16(gb_round(b * cb2) + gb_round(a * sb));
+                            const uint16_t oa = f32_to_bf16(round_bf16(a * ca) + round_bf16(-b * sa));   // rotate_half, three bf16 roundings
+                            const uint16_t ob = f32_to_bf16(round_bf16(b * cb2) + round_bf16(a * sb));
                             if (head < p.n_q) {
                                 p.C[(long long)m * p.ldc + ra] = oa;
                                 p.C[(long long)m * p.ldc + rb_] = ob;
@@ -330,11 +302,11 @@ __global__ __launch_bounds__(256) void gemv_batch_kernel(const GemvBParams p) {
 }
 
 template <int MM, int MODE, bool KS, int RPL>
-static int launch_gemv_b(const GemvBParams& p, const char* name, int n_units, hipStream_t st) {
+static int launch_gemv_b(const GemvBParams& p, const char* name, hipStream_t st) {
     const size_t smem = (size_t)MM * p.kp_chunks * 16;
     FO1_DYNAMIC_LDS_ONCE(150 * 1024, gemv_batch_kernel<MM, MODE, KS, RPL>);
     // persistent workgroups (grid-stride over work items): x is staged / normalised once per workgroup; <= 4 workgroups per CU
-    const int n_super = cdiv(n_units, RPL);
+    const int n_super = cdiv(gemv_units(MODE, 8, p.N, p.n_q, p.n_kv), RPL);
     int grid = KS ? n_super : cdiv(n_super, 4);
     if (grid > 512) {   // about two workgroups per CU, every wave the same number of items
         const int per = cdiv(grid, 512);
@@ -347,47 +319,43 @@ static int launch_gemv_b(const GemvBParams& p, const char* name, int n_units, hi
 extern int g_gemv_profile_shapes;
 static int g_gemv_rpl = 0;   // rows per lane: 0 = by M (fo1_gemv_batch_set_rows_per_lane)
 
+// K staged in LDS for `rows` x rows: whole K when rows * K * 2 <= 128 KiB, else the smallest number of equal pieces (multiples of 256 chunks) -> chunks per piece
+static int lds_piece_chunks(int rows, int kch) {
+    int pieces = 1;
+    while ((size_t)rows * cdiv(cdiv(kch, pieces), 256) * 256 * 16 > 128 * 1024) ++pieces;
+    const int chunks = cdiv(cdiv(kch, pieces), 256) * 256;
+    return chunks < kch ? chunks : kch;
+}
+
+// the launch ladder for one rows-per-lane choice: RA where a wave owns a unit (ks0), 1 where the K split shares it among the 4 waves
+template <int MM, int RA>
+static int launch_gemv_b_mode(const GemvBParams& p, int mode, bool ks, const char* name, hipStream_t st) {
+    if (mode == GB_SWIGLU) return ks ? launch_gemv_b<MM, GB_SWIGLU, true, 1>(p, name, st) : launch_gemv_b<MM, GB_SWIGLU, false, RA>(p, name, st);
+    if (mode == GB_QKV) return launch_gemv_b<MM, GB_QKV, true, 1>(p, name, st);
+    return ks ? launch_gemv_b<MM, GB_PLAIN, true, 1>(p, name, st) : launch_gemv_b<MM, GB_PLAIN, false, RA>(p, name, st);
+}
+
 template <int MM>
 static int dispatch_gemv_b(GemvBParams& p, int mode, hipStream_t st) {
-    // K piece staged in LDS: whole K when MM * K * 2 <= 128 KiB, else the smallest number of equal pieces (multiples of 256 chunks)
     const int kch = p.K >> 3;
-    int pieces = 1;
-    while ((size_t)MM * cdiv(cdiv(kch, pieces), 256) * 256 * 16 > 128 * 1024) ++pieces;
-    p.kp_chunks = cdiv(cdiv(kch, pieces), 256) * 256;
-    if (p.kp_chunks > kch) p.kp_chunks = kch;
-    {   // canonical segment = the piece an 8-sequence launch stages (independent of this launch's M)
-        int pc = 1;
-        while ((size_t)8 * cdiv(cdiv(kch, pc), 256) * 256 * 16 > 128 * 1024) ++pc;
-        p.canon_chunks = cdiv(cdiv(kch, pc), 256) * 256;
-        if (p.canon_chunks > kch) p.canon_chunks = kch;
-        if (p.kp_chunks < kch) p.kp_chunks = p.canon_chunks;      // staged in pieces: the pieces ARE the canonical segments
-    }
+    p.kp_chunks = lds_piece_chunks(MM, kch);
+    p.canon_chunks = lds_piece_chunks(8, kch);      // canonical segment = the piece an 8-sequence launch stages (independent of this launch's M)
+    if (p.kp_chunks < kch) p.kp_chunks = p.canon_chunks;      // staged in pieces: the pieces ARE the canonical segments
     if (p.norm_w && p.kp_chunks < kch) return set_err(FO1_ERR_ARG, "gemv_batch: fused RMSNorm needs K to fit one LDS piece (K=%d, M=%d)", p.K, MM);
-    int n_units;
-    if (mode == GB_SWIGLU) n_units = p.N / 8;
-    else if (mode == GB_QKV) n_units = (p.n_q + p.n_kv) * 16 + p.n_kv * 16;
-    else n_units = cdiv(p.N, 8);
     // every CU should stream: one unit per workgroup (K split over its 4 waves) unless that would make more than ~2048 workgroups.
     // (Decided by the shape alone: the K split fixes the fp32 sum order, which must not depend on M.)
-    const bool ks = n_units <= 1024;
+    const bool ks = gemv_units(mode, 8, p.N, p.n_q, p.n_kv) <= 1024;
     // rows per lane: many-unit matrices (gate/up, lm_head) 4 at M = 8, 2 at M = 4 (gate/up 35.6 -> 32.8 us, lm_head 139 -> 120 us
     // at M = 8); the K-split projections stay at 1 — with 2 they have half the workgroups and ran slower (down 22.7 -> 26.5 us)
-    constexpr int RA = MM >= 8 ? 4 : (MM >= 4 ? 2 : 1), RB = 1;
+    constexpr int RA = MM >= 8 ? 4 : (MM >= 4 ? 2 : 1);
     const bool one = g_gemv_rpl == 1;
     char pname[48];
     const char* name = mode == GB_SWIGLU ? "gemv_batch_swiglu" : (mode == GB_QKV ? "gemv_batch_qkv" : "gemv_batch");
     if (profile_enabled() && g_gemv_profile_shapes) {
-        snprintf(pname, sizeof pname, "gemv_b m%d %dx%d mode%d ks%d r%d", p.M, p.N, p.K, mode, (int)ks, one ? 1 : (ks ? RB : RA));
+        snprintf(pname, sizeof pname, "gemv_b m%d %dx%d mode%d ks%d r%d", p.M, p.N, p.K, mode, (int)ks, one || ks ? 1 : RA);
         name = pname;
     }
-    if (one) {
-        if (mode == GB_SWIGLU) return ks ? launch_gemv_b<MM, GB_SWIGLU, true, 1>(p, name, n_units, st) : launch_gemv_b<MM, GB_SWIGLU, false, 1>(p, name, n_units, st);
-        if (mode == GB_QKV) return launch_gemv_b<MM, GB_QKV, true, 1>(p, name, n_units, st);
-        return ks ? launch_gemv_b<MM, GB_PLAIN, true, 1>(p, name, n_units, st) : launch_gemv_b<MM, GB_PLAIN, false, 1>(p, name, n_units, st);
-    }
-    if (mode == GB_SWIGLU) return ks ? launch_gemv_b<MM, GB_SWIGLU, true, RB>(p, name, n_units, st) : launch_gemv_b<MM, GB_SWIGLU, false, RA>(p, name, n_units, st);
-    if (mode == GB_QKV) return launch_gemv_b<MM, GB_QKV, true, RB>(p, name, n_units, st);
-    return ks ? launch_gemv_b<MM, GB_PLAIN, true, RB>(p, name, n_units, st) : launch_gemv_b<MM, GB_PLAIN, false, RA>(p, name, n_units, st);
+    return one ? launch_gemv_b_mode<MM, 1>(p, mode, ks, name, st) : launch_gemv_b_mode<MM, RA>(p, mode, ks, name, st);
 }
 
 #endif   // FO1_ENABLE_AB (gemv_batch_kernel)
@@ -560,8 +528,6 @@ __global__ __launch_bounds__(256) void kv_relocate_kernel(const uint16_t* __rest
 
 extern "C" {
 
-
-
 #ifdef FO1_ENABLE_AB      // include/fo1_ab.h: test / bench build only
 // A/B hook: 1 = one unit (8 weight rows) per lane group whatever M is (the first form of this kernel); 0 = rows per lane by M.
 int fo1_gemv_batch_set_rows_per_lane(int rpl) {
@@ -590,19 +556,14 @@ int fo1_gemv_batch_bf16(const void* x, int ldx, const void* W, int ldw, const vo
                         const void* cos_table, const void* sin_table, const int32_t* state, void* kcache, long long kcache_head_stride,
                         void* vtcache, long long vt_row_stride, void* stream) {
     using namespace fo1;
-    FO1_CHECK_ARG(x && W && (C || mode == 2), "gemv_batch: NULL operand");
-    FO1_CHECK_ARG(M >= 1 && M <= 32 && N > 0 && K > 0 && K % 8 == 0 && ldx % 8 == 0 && ldw % 8 == 0, "gemv_batch: bad shape M=%d (1..32) N=%d K=%d", M, N, K);
+    if (int rc = check_gemv_operands("gemv_batch", x && W && (C || mode == 2), 32, x, ldx, W, ldw, norm_weight, M, N, K)) return rc;
     FO1_CHECK_ARG(mode >= 0 && mode <= 2, "gemv_batch: mode %d", mode);
-    FO1_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)norm_weight & 15) == 0, "gemv_batch: misaligned operand");
     if (mode == 1) FO1_CHECK_ARG(N % 32 == 0 && residual == nullptr, "gemv_batch: SwiGLU needs N %% 32 == 0 and no residual");
     if (mode == 2) {
         FO1_CHECK_ARG(n_q_heads > 0 && n_kv_heads > 0 && N == (n_q_heads + 2 * n_kv_heads) * 128, "gemv_batch: QKV mode needs N = (n_q + 2 n_kv) * 128");
         FO1_CHECK_ARG(cos_table && sin_table && state && kcache && vtcache && C && residual == nullptr, "gemv_batch: QKV mode operands");
     }
-    GemvBParams p;
-    p.X = (const uint16_t*)x; p.W = (const uint16_t*)W; p.bias = (const uint16_t*)bias; p.res = (const uint16_t*)residual; p.C = (uint16_t*)C;
-    p.M = M; p.N = N; p.K = K; p.ldx = ldx; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr;
-    p.norm_w = (const uint16_t*)norm_weight; p.norm_eps = norm_eps; p.kp_chunks = 0;
+    GemvBParams p(x, ldx, W, ldw, bias, residual, ldr, C, ldc, M, N, K, norm_weight, norm_eps);
     p.n_q = n_q_heads; p.n_kv = n_kv_heads; p.cos_t = (const uint16_t*)cos_table; p.sin_t = (const uint16_t*)sin_table; p.state = (const int*)state;
     p.kcache = (uint16_t*)kcache; p.kc_head_stride = kcache_head_stride; p.vtcache = (uint16_t*)vtcache; p.vt_row_stride = vt_row_stride;
     return gemv_b_any(p, mode, (hipStream_t)stream);
@@ -620,12 +581,8 @@ int fo1_gemv_attn_combine_bf16(const float* part, long long part_seq_stride, con
                   "gemv_attn_combine: M=%d (1..2) heads %d / %d (K = heads x 128 <= 2048) N=%d (<= 4096)", M, n_q_heads, n_kv_heads, N);
     FO1_CHECK_ARG(kv_chunk >= 64 && kv_chunk % 64 == 0 && ldw % 8 == 0 && ldw >= K && ((uintptr_t)W & 15) == 0 && ((uintptr_t)part & 7) == 0, "gemv_attn_combine: bad layout");
     FO1_CHECK_ARG(ldc >= N && (residual == nullptr || (ldr % 4 == 0 && ldr >= N && ((uintptr_t)residual & 7) == 0)), "gemv_attn_combine: residual / output layout");
-    GemvBParams p;
-    p.X = (const uint16_t*)W; p.ldx = 0;      // (the staged rows come from the partials; the plain x loads of the kernel's prologue read valid memory and are ignored)
-    p.W = (const uint16_t*)W; p.bias = nullptr; p.res = (const uint16_t*)residual; p.C = (uint16_t*)C;
-    p.M = M; p.N = N; p.K = K; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr;
-    p.norm_w = nullptr; p.norm_eps = 0.f; p.kp_chunks = 0;
-    p.n_q = p.n_kv = 0; p.cos_t = p.sin_t = nullptr; p.state = nullptr; p.kcache = p.vtcache = nullptr; p.kc_head_stride = p.vt_row_stride = 0;
+    // p.X = W, ldx 0: the staged rows come from the partials; the plain x loads of the kernel's prologue read valid memory and are ignored
+    GemvBParams p(W, 0, W, ldw, nullptr, residual, ldr, C, ldc, M, N, K, nullptr, 0.f);
     p.attn_part = part; p.attn_part_seq_stride = part_seq_stride; p.attn_state = (const int*)state;
     p.attn_chunk = kv_chunk; p.attn_n_kv = n_kv_heads; p.attn_group = n_q_heads / n_kv_heads;
     return gemv_mfma_any(p, GB_PLAIN, (hipStream_t)stream);

@@ -6,29 +6,76 @@
 
 namespace fo1 {
 
+enum { GB_PLAIN = 0, GB_SWIGLU = 1, GB_QKV = 2 };
+
 struct GemvBParams {
-    const uint16_t* X;       // [M, ldx]
-    const uint16_t* W;       // [N, ldw]
-    const uint16_t* bias;    // [N] or null
-    const uint16_t* res;     // [M, ldr] or null (plain mode)
-    uint16_t* C;             // [M, ldc]: plain out | SwiGLU out | rotated q rows (QKV mode)
-    int M, N, K, ldx, ldw, ldc, ldr;
-    const uint16_t* norm_w;  // optional fused RMSNorm on x
-    float norm_eps;
-    int kp_chunks;           // (dot2 kernel) 16-B chunks of K staged in LDS at a time
-    int canon_chunks;        // (dot2 kernel) canonical K segment (chunks)
+    const uint16_t* X = nullptr;       // [M, ldx]
+    const uint16_t* W = nullptr;       // [N, ldw]
+    const uint16_t* bias = nullptr;    // [N] or null
+    const uint16_t* res = nullptr;     // [M, ldr] or null (plain mode)
+    uint16_t* C = nullptr;             // [M, ldc]: plain out | SwiGLU out | rotated q rows (QKV mode)
+    int M = 0, N = 0, K = 0, ldx = 0, ldw = 0, ldc = 0, ldr = 0;
+    const uint16_t* norm_w = nullptr;  // optional fused RMSNorm on x
+    float norm_eps = 0.f;
+    int kp_chunks = 0;                 // (dot2 kernel) 16-B chunks of K staged in LDS at a time
+    int canon_chunks = 0;              // (dot2 kernel) canonical K segment (chunks)
     // QKV mode
-    int n_q, n_kv;           // heads (head_dim 128)
-    const uint16_t* cos_t; const uint16_t* sin_t;   // [rows, 128] bf16 tables
-    const int* state;        // [M][8]
-    uint16_t* kcache; long long kc_head_stride;      // [n_kv][rows][128]
-    uint16_t* vtcache; long long vt_row_stride;      // [n_kv*128][rows]
+    int n_q = 0, n_kv = 0;             // heads (head_dim 128)
+    const uint16_t* cos_t = nullptr; const uint16_t* sin_t = nullptr;   // [rows, 128] bf16 tables
+    const int* state = nullptr;        // [M][8]
+    uint16_t* kcache = nullptr; long long kc_head_stride = 0;      // [n_kv][rows][128]
+    uint16_t* vtcache = nullptr; long long vt_row_stride = 0;      // [n_kv*128][rows]
     // x = the decode attention's output, combined HERE from its split-KV partials (round 6: M <= 2, plain mode, K = heads x 128 <= 2048):
     // the rows attn_decode_combine_kernel would write never exist and its launch is not made
     const float* attn_part = nullptr;                // [M][chunks][n_kv][16][130] fp32 (attn_fwd_kernel PARTIAL)
     long long attn_part_seq_stride = 0;
     const int* attn_state = nullptr;                 // [M][8]: keys = state[0] + 1 - state[2], state[3] = finished
     int attn_chunk = 0, attn_n_kv = 0, attn_group = 0;
+    // what every entry fills: operands, strides, shape and the norm (the mode's own fields stay at their defaults until the entry sets them)
+    GemvBParams(const void* x, int ldx, const void* W, int ldw, const void* bias, const void* res, int ldr, void* C, int ldc, int M, int N, int K,
+                const void* norm_w, float norm_eps)
+        : X((const uint16_t*)x), W((const uint16_t*)W), bias((const uint16_t*)bias), res((const uint16_t*)res), C((uint16_t*)C), M(M), N(N), K(K),
+          ldx(ldx), ldw(ldw), ldc(ldc), ldr(ldr), norm_w((const uint16_t*)norm_w), norm_eps(norm_eps) {}
+};
+
+// Units (the weight rows one work item owns) of a launch, for kernel, dispatcher and launcher alike.  rows = weight rows per unit: plain = that many
+// consecutive features; SwiGLU = rows / 2 gate rows + their up partners (N / 2 features); QKV = rows / 2 rotary pairs of a q / k head (64 pairs per
+// head), then rows consecutive dims of the v heads (128 each).
+__host__ __device__ constexpr int gemv_units(int mode, int rows, int N, int n_q, int n_kv) {
+    return mode == GB_SWIGLU ? N / rows : mode == GB_QKV ? (n_q + n_kv) * (128 / rows) + n_kv * (128 / rows) : (N + rows - 1) / rows;
+}
+
+// What fo1_gemv_bf16 and fo1_gemv_batch_bf16 check alike (`operands`: the entry's own NULL test; max_m: the rows its kernels take)
+inline int check_gemv_operands(const char* who, bool operands, int max_m, const void* x, int ldx, const void* W, int ldw, const void* norm_weight,
+                               int M, int N, int K) {
+    FO1_CHECK_ARG(operands, "%s: NULL operand", who);
+    FO1_CHECK_ARG(M >= 1 && M <= max_m && N > 0 && K > 0 && K % 8 == 0 && ldx % 8 == 0 && ldw % 8 == 0, "%s: bad shape M=%d (1..%d) N=%d K=%d", who, M,
+                  max_m, N, K);
+    FO1_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)norm_weight & 15) == 0, "%s: misaligned operand", who);
+    return FO1_OK;
+}
+
+// Geometry of gemv_mfma_kernel<MM, MODE, NB, MP, HALF, R8> (decode_mfma.hip), read by the kernel and by its launcher.
+constexpr int GM_NW = 8;                                                 // waves per workgroup
+template <int MM, int NB, bool MP, bool HALF, bool R8>
+struct GemvMfmaGeom {
+    static constexpr int NG = MM == 32 ? 2 : 1;                          // column groups of 16 sequences
+    static constexpr bool XREG = MM == 32 && !MP;                        // x fragments live in registers (single-piece K)
+    static constexpr bool H8 = HALF || R8;                               // 8-row blocks, a stage = the k-step pair (s, s + 8)
+    static constexpr int PD = R8 ? 2 : ((HALF && !MP) ? 2 : ((MM == 32 && MP) ? 2 : 4));   // register stages per wave = stages per staged piece
+    static constexpr int SSTEP = H8 ? 16 : 8;                            // k-step distance between a wave's consecutive stages
+    static constexpr int PSTEPS = SSTEP * PD;                            // k-steps of x staged at a time: 32 (64: HALF && MP)
+    static constexpr int XPITCH = PSTEPS * 128 + 32;                     // bytes per staged x row (= 32 mod 256)
+    // XR32 (round 6): 17..26 sequences, deep K (`down`), 8-row units — 32 staged rows of a 32-k-step piece (132 KB) do not fit beside the scratch and the
+    // reduction buffers, M rows do up to M = 26: only the launch's own rows are staged, the column slots past them read the last staged row (never stored)
+    static constexpr bool XR32 = MM == 32 && MP && R8;
+    __host__ __device__ static constexpr int x_rows(int M) { return XR32 ? M : MM; }                      // staged x rows
+    static constexpr int SCRATCH_BYTES = GM_NW * NB * 2048;              // [GM_NW][NB][2048] weight scratch (wave-private)
+    static constexpr int RED_BYTES = 2 * NG * GM_NW * NB * 1024;         // [2][NG][GM_NW][NB][64][4] fp32 partial sums, double-buffered by unit parity
+    // XREG: the scratch and the reduction buffers reuse the x image once its fragments sit in registers; the 128 B hold the rows' rstd
+    static constexpr size_t lds_bytes(int M) {
+        return XREG ? (size_t)MM * XPITCH + 128 : (size_t)x_rows(M) * XPITCH + SCRATCH_BYTES + RED_BYTES + 128;
+    }
 };
 
 // The split-KV partials of the decode attention, fp32 [chunks][n_kv_heads][ATTN_PART_ROWS][head_dim + 2] per sequence: a row per query head
@@ -80,8 +127,6 @@ __device__ __forceinline__ void attn_combine_row(const float* __restrict__ pr0, 
 #pragma unroll
     for (int j = 0; j < ND; ++j) out[j] = den > 0.f ? num[j] / den : 0.f;
 }
-
-enum { GB_PLAIN = 0, GB_SWIGLU = 1, GB_QKV = 2 };
 
 // decode_mfma.hip
 #ifdef FO1_ENABLE_AB

@@ -44,26 +44,11 @@ namespace fo1 {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 gm_bf16x8;
 typedef __attribute__((ext_vector_type(4))) float gm_f32x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 gm_bf16x2;
-typedef __attribute__((ext_vector_type(4))) unsigned int gm_u32x4;
 
-constexpr int GM_NW = 8;                           // waves per workgroup
 constexpr int GM_NT = GM_NW * 64;
 constexpr int GM_D = 4;                            // k-steps in flight per wave (register stages), full variant
 constexpr int GM_PIECE = GM_NW * GM_D;             // k-steps of x staged at a time (32 x 64 = 2048 elements), full variant
 
-__device__ __forceinline__ uint4 gm_load_nt16(const uint16_t* p) {
-    const gm_u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const gm_u32x4*>(p));
-    return uint4{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ float gm_round(float v) { return bf16_to_f32(f32_to_bf16(v)); }
-__device__ __forceinline__ float gm_dot8(const uint4& a, const uint4& b, float acc) {
-    acc = __builtin_amdgcn_fdot2_f32_bf16(*reinterpret_cast<const gm_bf16x2*>(&a.x), *reinterpret_cast<const gm_bf16x2*>(&b.x), acc, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(*reinterpret_cast<const gm_bf16x2*>(&a.y), *reinterpret_cast<const gm_bf16x2*>(&b.y), acc, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(*reinterpret_cast<const gm_bf16x2*>(&a.z), *reinterpret_cast<const gm_bf16x2*>(&b.z), acc, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(*reinterpret_cast<const gm_bf16x2*>(&a.w), *reinterpret_cast<const gm_bf16x2*>(&b.w), acc, false);
-    return acc;
-}
 __device__ __forceinline__ void gm_lds_fence() {
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -79,28 +64,21 @@ __global__ __launch_bounds__(GM_NT) void gemv_mfma_kernel(const GemvBParams p, c
     static_assert(!R8 || ((MM == 16 || MM == 32) && MODE != GB_SWIGLU && !HALF), "R8: 9..32 sequences, plain or QKV");
     static_assert(MM == 8 || MM == 16 || MM == 32, "8, 16 or 32 sequence columns");
     static_assert(MM != 32 || !HALF, "32 sequences: 16-row blocks, or 8-row blocks with the k-step pair as two MFMAs (R8, single-piece K only)");
-    constexpr int NG = MM == 32 ? 2 : 1;                                 // column groups of 16 sequences
+    using G = GemvMfmaGeom<MM, NB, MP, HALF, R8>;                         // (decode_common.h: the launcher sizes the LDS from the same description)
+    constexpr int NG = G::NG, PD = G::PD, SSTEP = G::SSTEP, PSTEPS = G::PSTEPS, XPITCH = G::XPITCH;
+    constexpr bool XREG = G::XREG, H8 = G::H8, XR32 = G::XR32;
     constexpr int MR = MM == 32 ? 16 : MM;                               // sequences per group
-    constexpr bool XREG = MM == 32 && !MP;                               // x fragments live in registers (single-piece K)
-    constexpr bool H8 = HALF || R8;                                      // 8-row blocks, a stage = the k-step pair (s, s + 8)
-    constexpr int PD = R8 ? 2 : ((HALF && !MP) ? 2 : ((MM == 32 && MP) ? 2 : 4));   // register stages per wave = stages per staged piece
-    constexpr int SSTEP = H8 ? 16 : 8;                                   // k-step distance between a wave's consecutive stages
-    constexpr int PSTEPS = SSTEP * PD;                                   // k-steps of x staged at a time: 32 (64: HALF && MP)
-    constexpr int XPITCH = PSTEPS * 128 + 32;                            // bytes per staged x row (= 32 mod 256)
     constexpr int CPR = PSTEPS * 8;                                      // 16-byte chunks per staged x row
     constexpr int RPP = GM_NT / CPR;                                     // x rows per pass of the workgroup (2 or 1)
     constexpr int XL = MM / RPP;                                         // x loads per thread and piece
     constexpr int RB = H8 ? 8 : 16;                                      // weight rows per block
     extern __shared__ __attribute__((aligned(16))) unsigned char gm_smem[];
     unsigned char* const sx = gm_smem;                                   // [MM][XPITCH]
-    // XR32 (round 6): 17..26 sequences, deep K (`down`), 8-row units — 32 staged rows of a 32-k-step piece (132 KB) do not fit beside the scratch and the
-    // reduction buffers, M rows do up to M = 26: only the launch's own rows are staged, the column slots past them read the last staged row (never stored)
-    constexpr bool XR32 = MM == 32 && MP && R8;
-    const int xrows = XR32 ? p.M : MM;
+    const int xrows = G::x_rows(p.M);
     unsigned char* const sw = XREG ? gm_smem : gm_smem + xrows * XPITCH; // [GM_NW][NB][2048]  weight scratch (wave-private); XREG: over the dead x image
-    float* const sred = reinterpret_cast<float*>(sw + GM_NW * NB * 2048);   // [2][NG][GM_NW][NB][64][4]
-    float* const srstd = XREG ? reinterpret_cast<float*>(gm_smem + MM * XPITCH) : sred + 2 * NG * GM_NW * NB * 256;   // [32]
-    static_assert(!XREG || GM_NW * NB * 2048 + 2 * NG * GM_NW * NB * 1024 <= MM * XPITCH, "scratch + reduction buffers fit in the x image");
+    float* const sred = reinterpret_cast<float*>(sw + G::SCRATCH_BYTES);    // [2][NG][GM_NW][NB][64][4]
+    float* const srstd = XREG ? reinterpret_cast<float*>(gm_smem + MM * XPITCH) : sred + G::RED_BYTES / 4;   // [32]
+    static_assert(!XREG || G::SCRATCH_BYTES + G::RED_BYTES <= MM * XPITCH, "scratch + reduction buffers fit in the x image");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int kch = p.K >> 3;                                            // 16-byte chunks per row
     const int n_pieces = (nsteps + PSTEPS - 1) / PSTEPS;
@@ -147,7 +125,7 @@ __global__ __launch_bounds__(GM_NT) void gemv_mfma_kernel(const GemvBParams p, c
 #pragma unroll
         for (int b = 0; b < NB; ++b)
 #pragma unroll
-            for (int q = 0; q < 2; ++q) st[b][q] = gm_load_nt16(wp[b][q] + (long long)c[q] * 8);
+            for (int q = 0; q < 2; ++q) st[b][q] = load_nt16(wp[b][q] + (long long)c[q] * 8);
     };
     // acc: the chain this stage adds to (R8: chain A = the pair's first k-step; accb = chain B = its second)
     uint4 xf[XREG ? PD : 1][H8 ? 2 : 1][2][NG];           // XREG: B fragments of this wave's k-steps (stage d, k-step of the pair, half h, column group g)
@@ -221,26 +199,20 @@ __global__ __launch_bounds__(GM_NT) void gemv_mfma_kernel(const GemvBParams p, c
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const uint4 v = *reinterpret_cast<const uint4*>(sx + m * XPITCH + (lane + 64 * i) * 16);
-                    ss = gm_dot8(v, v, ss);
+                    ss = dot8_dot2(v, v, ss);
                 }
 #pragma unroll
                 for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
                 if (lane == 0) srstd[m] = rsqrtf(ss / (float)p.K + p.norm_eps);
             }
             __syncthreads();
-            // fp32 variance, bf16(x * rstd), * weight -> bf16 (the reference's rounding points)
 #pragma unroll
             for (int i = 0; i < XL; ++i) {             // (!MP: 256 chunks per row, two rows per pass)
                 const int m = tid / CPR + RPP * i;
                 const float rstd = srstd[m];
                 uint4* px = reinterpret_cast<uint4*>(sx + m * XPITCH + c * 16);
                 const uint4 v = *px;
-                uint4 o;
-                o.x = pack_bf16x2(bf16_lo(nw.x) * gm_round(bf16_lo(v.x) * rstd), bf16_hi(nw.x) * gm_round(bf16_hi(v.x) * rstd));
-                o.y = pack_bf16x2(bf16_lo(nw.y) * gm_round(bf16_lo(v.y) * rstd), bf16_hi(nw.y) * gm_round(bf16_hi(v.y) * rstd));
-                o.z = pack_bf16x2(bf16_lo(nw.z) * gm_round(bf16_lo(v.z) * rstd), bf16_hi(nw.z) * gm_round(bf16_hi(v.z) * rstd));
-                o.w = pack_bf16x2(bf16_lo(nw.w) * gm_round(bf16_lo(v.w) * rstd), bf16_hi(nw.w) * gm_round(bf16_hi(v.w) * rstd));
-                *px = o;
+                *px = rmsnorm_chunk(v, nw, rstd);
             }
             __syncthreads();
         }
@@ -429,7 +401,7 @@ __global__ __launch_bounds__(GM_NT) void gemv_mfma_kernel(const GemvBParams p, c
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             float x = v[b][r] + h4(e_bias[b], r);
-                            x = gm_round(x);
+                            x = round_bf16(x);
                             x += h4(e_res[b], r);
                             o[r] = f32_to_bf16(x);
                         }
@@ -449,9 +421,9 @@ __global__ __launch_bounds__(GM_NT) void gemv_mfma_kernel(const GemvBParams p, c
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         float g = v[0][r] + h4(e_bias[0], r), up = v[NB - 1][r] + h4(e_bias[NB - 1], r);
-                        g = gm_round(g);
-                        up = gm_round(up);
-                        o[r] = f32_to_bf16(gm_round(fo1_silu(g)) * up);
+                        g = round_bf16(g);
+                        up = round_bf16(up);
+                        o[r] = f32_to_bf16(round_bf16(fo1_silu(g)) * up);
                     }
                     uint16_t* cp = p.C + (long long)n_seq * p.ldc + u * 16 + fg * 4;
                     if ((p.ldc & 3) == 0) {
@@ -467,11 +439,11 @@ __global__ __launch_bounds__(GM_NT) void gemv_mfma_kernel(const GemvBParams p, c
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             float a = v[0][r] + h4(e_bias[0], r), b = v[NB - 1][r] + h4(e_bias[NB - 1], r);
-                            a = gm_round(a);                                          // the bf16 q/k the unfused path stores
-                            b = gm_round(b);
+                            a = round_bf16(a);                                          // the bf16 q/k the unfused path stores
+                            b = round_bf16(b);
                             const float c1 = h4(e_cos[0], r), s1 = h4(e_sin[0], r), c2 = h4(e_cos[1], r), s2 = h4(e_sin[1], r);
-                            oa[r] = f32_to_bf16(gm_round(a * c1) + gm_round(-b * s1));     // rotate_half, three bf16 roundings
-                            ob[r] = f32_to_bf16(gm_round(b * c2) + gm_round(a * s2));
+                            oa[r] = f32_to_bf16(round_bf16(a * c1) + round_bf16(-b * s1));     // rotate_half, three bf16 roundings
+                            ob[r] = f32_to_bf16(round_bf16(b * c2) + round_bf16(a * s2));
                         }
                         const uint2 pa = uint2{(uint32_t)oa[0] | ((uint32_t)oa[1] << 16), (uint32_t)oa[2] | ((uint32_t)oa[3] << 16)};
                         const uint2 pb = uint2{(uint32_t)ob[0] | ((uint32_t)ob[1] << 16), (uint32_t)ob[2] | ((uint32_t)ob[3] << 16)};
@@ -518,20 +490,15 @@ extern int g_gemv_profile_shapes;
 
 template <int MM, int MODE, int NB, bool MP, bool HALF, bool R8 = false>
 static int launch_gemv_mfma_mp(const GemvBParams& p, int n_units, int nsteps, const char* name, hipStream_t st) {
-    constexpr int pd = R8 ? 2 : ((HALF && !MP) ? 2 : ((MM == 32 && MP) ? 2 : 4));
-    constexpr int xpitch = ((HALF || R8) ? 16 : 8) * pd * 128 + 32;
-    constexpr int ng = MM == 32 ? 2 : 1;
-    // MM == 32, single piece: the weight scratch and the reduction buffers reuse the x image once its fragments sit in registers
-    const size_t xrows = (MM == 32 && MP && R8) ? (size_t)p.M : (size_t)MM;       // (deep-K 8-row units at 17..26 sequences: the launch's own rows only)
-    const size_t smem = (MM == 32 && !MP) ? (size_t)MM * xpitch + 128
-                                          : xrows * xpitch + (size_t)GM_NW * NB * 2048 + (size_t)2 * ng * GM_NW * NB * 1024 + 128;
+    using G = GemvMfmaGeom<MM, NB, MP, HALF, R8>;
+    const size_t smem = G::lds_bytes(p.M);
     if (smem > 156 * 1024) return set_err(FO1_ERR_ARG, "gemv_batch: %zu B of LDS for M=%d K=%d (internal dispatch error)", smem, p.M, p.K);
     FO1_DYNAMIC_LDS_ONCE(156 * 1024, gemv_mfma_kernel<MM, MODE, NB, MP, HALF, R8>);
     char pname[56];
     if (profile_enabled() && g_gemv_profile_shapes) {
         // the route: weight rows per unit, row blocks, single- / multi-piece K, h = HALF, r = R8, x = XR32 (the launch's own x rows staged)
-        snprintf(pname, sizeof pname, "gemv_mfma m%d %dx%d mode%d u%d nb%d %s %s%s%s", p.M, p.N, p.K, MODE, NB * ((HALF || R8) ? 8 : 16), NB, MP ? "mp" : "1p",
-                 HALF ? "h" : "", R8 ? "r" : "", (MM == 32 && MP && R8) ? "x" : ((HALF || R8) ? "" : "-"));
+        snprintf(pname, sizeof pname, "gemv_mfma m%d %dx%d mode%d u%d nb%d %s %s%s%s", p.M, p.N, p.K, MODE, NB * (G::H8 ? 8 : 16), NB, MP ? "mp" : "1p",
+                 HALF ? "h" : "", R8 ? "r" : "", G::XR32 ? "x" : (G::H8 ? "" : "-"));
         name = pname;
     }
     // persistent workgroups, one per CU (x is staged / normalised once per workgroup when K fits one piece)
@@ -562,31 +529,29 @@ static int dispatch_gemv_mfma(GemvBParams& p, int mode, hipStream_t st) {
         return set_err(FO1_ERR_ARG, "gemv_batch: M > 16 with K > 2048 is built for the plain few-row form only (M=%d N=%d K=%d mode=%d)", p.M, p.N, p.K, mode);
     // (under fo1_gemm_profile_shapes the launcher replaces the name by the shape and the route it instantiates)
     const char* name = mode == GB_SWIGLU ? "gemv_mfma_swiglu" : (mode == GB_QKV ? "gemv_mfma_qkv" : "gemv_mfma");
-    if (mode == GB_SWIGLU) return launch_gemv_mfma<MM, GB_SWIGLU, 2>(p, p.N / 32, nsteps, name, st);
-    if constexpr (MM == 8) {
-        // M <= 8: half of the MFMA's columns are free — 8-row units with the k-step pair in the two halves (same sums, see the header)
-        if ((g_gemv_half & 1) && mode == GB_QKV) return launch_gemv_mfma<8, GB_QKV, 2, true>(p, (p.n_q + p.n_kv) * 8 + p.n_kv * 8, nsteps, name, st);
-        if ((g_gemv_half & 1) && mode == GB_PLAIN && p.N <= 4096) return launch_gemv_mfma<8, GB_PLAIN, 1, true>(p, cdiv(p.N, 8), nsteps, name, st);
+    auto units = [&](int rows) { return gemv_units(mode, rows, p.N, p.n_q, p.n_kv); };    // rows = weight rows per unit
+    if (mode == GB_SWIGLU) return launch_gemv_mfma<MM, GB_SWIGLU, 2>(p, units(32), nsteps, name, st);
+    // The few-row projections (q/k/v; o, down: N <= 4096) have too few 16-row units to fill the chip: 8-row units (same sums, see the header), under the
+    // column class's bit of fo1_gemv_batch_set_impl's half switch — bit 0: M <= 8 (HALF), bit 1: 9..32 sequences (R8)
+    const bool qkv = mode == GB_QKV;
+    if ((qkv || p.N <= 4096) && (g_gemv_half & (MM == 8 ? 1 : 2))) {
+        if constexpr (MM == 8)      // half of the MFMA's columns are free: the k-step pair in the two halves
+            return qkv ? launch_gemv_mfma<8, GB_QKV, 2, true>(p, units(16), nsteps, name, st) : launch_gemv_mfma<8, GB_PLAIN, 1, true>(p, units(8), nsteps, name, st);
+        if constexpr (MM == 16)     // both k-steps of a pair as separate MFMAs
+            return qkv ? launch_gemv_mfma<16, GB_QKV, 2, false, true>(p, units(16), nsteps, name, st)
+                       : launch_gemv_mfma<16, GB_PLAIN, 1, false, true>(p, units(8), nsteps, name, st);
+        if constexpr (MM == 32) {
+            // single-piece K: x fragments in registers.  Deep K (`down`; QKV was refused above): x staged in 32-k-step pieces of the launch's OWN rows
+            // (M x 4 KB + 48 KB of LDS fit up to M = 26) — 256 workgroups where the 16-row units below have 128; 27..32 sequences keep the 16-row units
+            if (nsteps <= 32)
+                return qkv ? launch_gemv_mfma_mp<32, GB_QKV, 2, false, false, true>(p, units(16), nsteps, name, st)
+                           : launch_gemv_mfma_mp<32, GB_PLAIN, 1, false, false, true>(p, units(8), nsteps, name, st);
+            if (p.M <= 26 && !p.norm_w) return launch_gemv_mfma_mp<32, GB_PLAIN, 1, true, false, true>(p, units(8), nsteps, name, st);
+        }
     }
-    if constexpr (MM == 16) {
-        // 9..16 sequences: 8-row units with both k-steps of a pair as separate MFMAs (R8, see the header) — the few-row projections
-        // fill the chip like they do at M <= 8; bit 2 of fo1_gemv_batch_set_impl's half switch (g_gemv_half & 2 == 0) turns it off
-        if ((g_gemv_half & 2) && mode == GB_QKV) return launch_gemv_mfma<16, GB_QKV, 2, false, true>(p, (p.n_q + p.n_kv) * 8 + p.n_kv * 8, nsteps, name, st);
-        if ((g_gemv_half & 2) && mode == GB_PLAIN && p.N <= 4096) return launch_gemv_mfma<16, GB_PLAIN, 1, false, true>(p, cdiv(p.N, 8), nsteps, name, st);
-    }
-    if constexpr (MM == 32) {
-        // 17..32 sequences, single-piece K only (a deep-K piece of 32 x 4 KB rows does not fit next to the buffers): the same 8-row units
-        if ((g_gemv_half & 2) && nsteps <= 32 && mode == GB_QKV) return launch_gemv_mfma_mp<32, GB_QKV, 2, false, false, true>(p, (p.n_q + p.n_kv) * 8 + p.n_kv * 8, nsteps, name, st);
-        if ((g_gemv_half & 2) && nsteps <= 32 && mode == GB_PLAIN && p.N <= 4096) return launch_gemv_mfma_mp<32, GB_PLAIN, 1, false, false, true>(p, cdiv(p.N, 8), nsteps, name, st);
-        // deep K (`down`), 17..27 sequences: the same 8-row units with x staged in 32-k-step pieces of the launch's OWN rows (M x 4 KB + 48 KB of LDS fit up to
-        // M = 26) — 256 workgroups where the 16-row units below have 128, the same sums; 27..32 sequences keep the 16-row units (bit 2 of the half switch off: A/B)
-        if ((g_gemv_half & 2) && nsteps > 32 && mode == GB_PLAIN && p.N <= 4096 && p.M <= 26 && !p.norm_w)
-            return launch_gemv_mfma_mp<32, GB_PLAIN, 1, true, false, true>(p, cdiv(p.N, 8), nsteps, name, st);
-    }
-    if (mode == GB_QKV) return launch_gemv_mfma<MM, GB_QKV, 2>(p, (p.n_q + p.n_kv) * 4 + p.n_kv * 4, nsteps, name, st);
+    if (qkv) return launch_gemv_mfma<MM, GB_QKV, 2>(p, units(32), nsteps, name, st);
     // plain: 16-row units for the few-row projections (every CU should stream), 32-row units for lm_head-sized matrices
-    if (p.N >= 8192) return launch_gemv_mfma<MM, GB_PLAIN, 2>(p, cdiv(p.N, 32), nsteps, name, st);
-    return launch_gemv_mfma<MM, GB_PLAIN, 1>(p, cdiv(p.N, 16), nsteps, name, st);
+    return p.N >= 8192 ? launch_gemv_mfma<MM, GB_PLAIN, 2>(p, units(32), nsteps, name, st) : launch_gemv_mfma<MM, GB_PLAIN, 1>(p, units(16), nsteps, name, st);
 }
 
 int gemv_mfma_any(GemvBParams& p, int mode, hipStream_t st) {

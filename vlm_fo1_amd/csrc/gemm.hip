@@ -94,8 +94,6 @@ __device__ __forceinline__ float act_apply(float v, int act) {
     return v;
 }
 
-__device__ __forceinline__ float round_bf16(float v) { return bf16_to_f32(f32_to_bf16(v)); }
-
 __device__ __forceinline__ void tile_coords(const GemmParams& p, int& tm, int& tn) {
     const int nwg = p.tiles_m * p.tiles_n;
     const int bid = blockIdx.x;

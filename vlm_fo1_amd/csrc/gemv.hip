@@ -4,34 +4,33 @@
 // fp32 accumulate, wave-shuffle reduction, one lane writes.  No MFMA: at M = 1 the matrix cores would run
 // at 1/64 utilisation and the LDS round trip is pure overhead (guide: "GEMV / M <= 16: load straight to
 // VGPRs, deep unroll").  Algorithmic bytes per launch = N*K*2 (+ x, out).
-#include "common.h"
+#include "decode_common.h"
 
 namespace fo1 {
 
 struct GemvParams {
-    const uint16_t* X;     // [M, ldx]
-    const uint16_t* W;     // [N, ldw]
-    const uint16_t* bias;  // [N] or null
-    const uint16_t* res;   // [M, ldr] or null
-    uint16_t* C;           // [M, ldc]
-    int M, N, K, ldx, ldw, ldc, ldr, act;
-    const uint16_t* norm_w;  // optional fused RMSNorm on x (weight [K]); eps below
-    float norm_eps;
+    const uint16_t* X = nullptr;     // [M, ldx]
+    const uint16_t* W = nullptr;     // [N, ldw]
+    const uint16_t* bias = nullptr;  // [N] or null
+    const uint16_t* res = nullptr;   // [M, ldr] or null
+    uint16_t* C = nullptr;           // [M, ldc]
+    int M = 0, N = 0, K = 0, ldx = 0, ldw = 0, ldc = 0, ldr = 0, act = 0;
+    const uint16_t* norm_w = nullptr;  // optional fused RMSNorm on x (weight [K]); eps below
+    float norm_eps = 0.f;
+    GemvParams(const void* x, int ldx, const void* W, int ldw, const void* bias, const void* res, int ldr, void* C, int ldc, int M, int N, int K, int act,
+               const void* norm_w, float norm_eps)
+        : X((const uint16_t*)x), W((const uint16_t*)W), bias((const uint16_t*)bias), res((const uint16_t*)res), C((uint16_t*)C), M(M), N(N), K(K),
+          ldx(ldx), ldw(ldw), ldc(ldc), ldr(ldr), act(act), norm_w((const uint16_t*)norm_w), norm_eps(norm_eps) {}
 };
 
-__device__ __forceinline__ float gv_round(float v) { return bf16_to_f32(f32_to_bf16(v)); }
 __device__ __forceinline__ float gv_act(float v, int act) {
     if (act == 1) return fo1_gelu_erf(v);
     if (act == 2) return fo1_silu(v);
     if (act == 5) return fmaxf(v, 0.0f);
     return v;
 }
-__device__ __forceinline__ float gv_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float dot8(const uint4& w, const uint4& x, float acc) {
+// a chain of eight fmaf, element by element: other arithmetic than the shared dot8_dot2 (four v_dot2), so it stays here
+__device__ __forceinline__ float dot8_fma(const uint4& w, const uint4& x, float acc) {
     acc = fmaf(bf16_lo(w.x), bf16_lo(x.x), acc); acc = fmaf(bf16_hi(w.x), bf16_hi(x.x), acc);
     acc = fmaf(bf16_lo(w.y), bf16_lo(x.y), acc); acc = fmaf(bf16_hi(w.y), bf16_hi(x.y), acc);
     acc = fmaf(bf16_lo(w.z), bf16_lo(x.z), acc); acc = fmaf(bf16_hi(w.z), bf16_hi(x.z), acc);
@@ -63,21 +62,16 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvParams p) {
             float ss = 0.f;
             for (int c = tid; c < kch; c += 256) {
                 const uint4 v = *reinterpret_cast<const uint4*>(&sx[m * p.K + c * 8]);
-                ss = dot8(v, v, ss);
+                ss = dot8_fma(v, v, ss);
             }
-            ss = gv_wave_sum(ss);
+            ss = wave_sum(ss);
             if (lane == 0) s_ss[wave] = ss;
             __syncthreads();
             const float rstd = rsqrtf((s_ss[0] + s_ss[1] + s_ss[2] + s_ss[3]) / (float)p.K + p.norm_eps);
             for (int c = tid; c < kch; c += 256) {
-                uint4 v = *reinterpret_cast<const uint4*>(&sx[m * p.K + c * 8]);
+                const uint4 v = *reinterpret_cast<const uint4*>(&sx[m * p.K + c * 8]);
                 const uint4 w = *reinterpret_cast<const uint4*>(p.norm_w + c * 8);
-                uint4 o;
-                o.x = pack_bf16x2(bf16_lo(w.x) * gv_round(bf16_lo(v.x) * rstd), bf16_hi(w.x) * gv_round(bf16_hi(v.x) * rstd));
-                o.y = pack_bf16x2(bf16_lo(w.y) * gv_round(bf16_lo(v.y) * rstd), bf16_hi(w.y) * gv_round(bf16_hi(v.y) * rstd));
-                o.z = pack_bf16x2(bf16_lo(w.z) * gv_round(bf16_lo(v.z) * rstd), bf16_hi(w.z) * gv_round(bf16_hi(v.z) * rstd));
-                o.w = pack_bf16x2(bf16_lo(w.w) * gv_round(bf16_lo(v.w) * rstd), bf16_hi(w.w) * gv_round(bf16_hi(v.w) * rstd));
-                *reinterpret_cast<uint4*>(&sx[m * p.K + c * 8]) = o;
+                *reinterpret_cast<uint4*>(&sx[m * p.K + c * 8]) = rmsnorm_chunk(v, w, rstd);
             }
             __syncthreads();
         }
@@ -127,7 +121,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvParams p) {
                 for (int m = 0; m < MM; ++m) {
                     const uint4 xv = *reinterpret_cast<const uint4*>(&sx[m * p.K + c * 8]);
 #pragma unroll
-                    for (int r = 0; r < NR; ++r) acc[r][m] = dot8(w[r][u], xv, acc[r][m]);
+                    for (int r = 0; r < NR; ++r) acc[r][m] = dot8_fma(w[r][u], xv, acc[r][m]);
                 }
             }
         }
@@ -135,7 +129,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvParams p) {
 #pragma unroll
     for (int r = 0; r < NR; ++r)
 #pragma unroll
-        for (int m = 0; m < MM; ++m) acc[r][m] = gv_wave_sum(acc[r][m]);
+        for (int m = 0; m < MM; ++m) acc[r][m] = wave_sum(acc[r][m]);
     if (KSPLIT) {
         if (lane == 0) {
 #pragma unroll
@@ -163,14 +157,14 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvParams p) {
             if (SWIGLU) {
                 float g = acc[j][m], u = acc[4 + j][m];
                 if (p.bias) { g += bf16_to_f32(p.bias[rows[j]]); u += bf16_to_f32(p.bias[rows[4 + j]]); }
-                g = gv_round(g);
-                u = gv_round(u);
-                v = gv_round(fo1_silu(g)) * u;
+                g = round_bf16(g);
+                u = round_bf16(u);
+                v = round_bf16(fo1_silu(g)) * u;
             } else {
                 v = acc[j][m];
                 if (p.bias) v += bf16_to_f32(p.bias[f]);
-                v = gv_round(v);
-                if (p.act) v = gv_round(gv_act(v, p.act));
+                v = round_bf16(v);
+                if (p.act) v = round_bf16(gv_act(v, p.act));
                 if (p.res) v += bf16_to_f32(p.res[(long long)m * p.ldr + f]);
             }
             p.C[(long long)m * p.ldc + f] = f32_to_bf16(v);
@@ -205,10 +199,7 @@ static int launch_gemv(const GemvParams& p, hipStream_t st) {
 // called from gemm_dispatch's front end (gemm.hip) when M <= 4
 int gemv_dispatch(const void* A, int lda, const void* W, int ldw, const void* bias, const void* residual, int ldr, void* C, int ldc,
                   int M, int N, int K, int act, hipStream_t st, const void* norm_w, float norm_eps) {
-    GemvParams p;
-    p.norm_w = (const uint16_t*)norm_w; p.norm_eps = norm_eps;
-    p.X = (const uint16_t*)A; p.W = (const uint16_t*)W; p.bias = (const uint16_t*)bias; p.res = (const uint16_t*)residual;
-    p.C = (uint16_t*)C; p.M = M; p.N = N; p.K = K; p.ldx = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr; p.act = act;
+    const GemvParams p(A, lda, W, ldw, bias, residual, ldr, C, ldc, M, N, K, act, norm_w, norm_eps);
     if (M == 1) return launch_gemv<1>(p, st);
     if (M == 2) return launch_gemv<2>(p, st);
     return launch_gemv<4>(p, st);
@@ -223,11 +214,9 @@ extern "C" {
 int fo1_gemv_bf16(const void* x, int ldx, const void* W, int ldw, const void* bias, const void* residual, int ldr, void* C, int ldc,
                   int M, int N, int K, int act, const void* norm_weight, float norm_eps, void* stream) {
     using namespace fo1;
-    FO1_CHECK_ARG(x && W && C, "gemv: NULL operand");
-    FO1_CHECK_ARG(M >= 1 && M <= 4 && N > 0 && K > 0 && K % 8 == 0 && ldx % 8 == 0 && ldw % 8 == 0, "gemv: bad shape M=%d N=%d K=%d", M, N, K);
+    if (int rc = check_gemv_operands("gemv", x && W && C, 4, x, ldx, W, ldw, norm_weight, M, N, K)) return rc;
     FO1_CHECK_ARG((size_t)(M > 2 ? 4 : M) * K * 2 <= 150 * 1024, "gemv: x does not fit LDS (M=%d K=%d)", M, K);
     FO1_CHECK_ARG(((act >= 0 && act <= 3) || act == 5) && (act != 3 || (N % 32 == 0 && residual == nullptr)), "gemv: bad act/N");
-    FO1_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)norm_weight & 15) == 0, "gemv: misaligned operand");
     return gemv_dispatch(x, ldx, W, ldw, bias, residual, ldr, C, ldc, M, N, K, act, (hipStream_t)stream, norm_weight, norm_eps);
 }
 

@@ -9,23 +9,6 @@
 
 namespace fo1 {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ void unpack8(const uint4& u, float (&f)[8]) {
-    f[0] = bf16_lo(u.x); f[1] = bf16_hi(u.x); f[2] = bf16_lo(u.y); f[3] = bf16_hi(u.y);
-    f[4] = bf16_lo(u.z); f[5] = bf16_hi(u.z); f[6] = bf16_lo(u.w); f[7] = bf16_hi(u.w);
-}
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-    uint4 u;
-    u.x = pack_bf16x2(f[0], f[1]); u.y = pack_bf16x2(f[2], f[3]);
-    u.z = pack_bf16x2(f[4], f[5]); u.w = pack_bf16x2(f[6], f[7]);
-    return u;
-}
-
 constexpr int kMaxChunksPerLane = 8;  // D <= 64 lanes * 8 chunks * 8 elements = 4096
 
 // mode 0: RMSNorm (w only); mode 1: LayerNorm (w, b).  NPER = 16-byte chunks per lane (a template parameter: straight-line code),
@@ -107,7 +90,7 @@ __global__ __launch_bounds__(256) void rownorm_kernel(const uint16_t* __restrict
         unpack8(wv[i], wf);
         if (MODE == 0) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = wf[j] * bf16_to_f32(f32_to_bf16(f[j] * rstd));
+            for (int j = 0; j < 8; ++j) o[j] = wf[j] * round_bf16(f[j] * rstd);
         } else {
             float bf[8];
             unpack8(bv[i], bf);
@@ -158,7 +141,7 @@ __global__ __launch_bounds__(256) void splitk_residual_rmsnorm_kernel(const floa
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float t = bf16_to_f32(f32_to_bf16(bf16_to_f32(f32_to_bf16(v[j])) + r[j]));
+            const float t = round_bf16(round_bf16(v[j]) + r[j]);
             xv[i][j] = ok ? t : 0.f;
             ss = fmaf(xv[i][j], xv[i][j], ss);
         }
@@ -175,7 +158,7 @@ __global__ __launch_bounds__(256) void splitk_residual_rmsnorm_kernel(const floa
         float wf[8], o[8];
         unpack8(wv[i], wf);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = wf[j] * bf16_to_f32(f32_to_bf16(xv[i][j] * rstd));
+        for (int j = 0; j < 8; ++j) o[j] = wf[j] * round_bf16(xv[i][j] * rstd);
         *reinterpret_cast<uint4*>(xn_out + (size_t)m * ldn + c * 8) = pack8(o);
     }
 }
@@ -204,8 +187,8 @@ __global__ __launch_bounds__(256) void splitk_swiglu_kernel(const float* __restr
         float o[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float sg = bf16_to_f32(f32_to_bf16(fo1_silu(bf16_to_f32(f32_to_bf16(g[j])))));
-            o[j] = sg * bf16_to_f32(f32_to_bf16(u[j]));
+            const float sg = round_bf16(fo1_silu(round_bf16(g[j])));
+            o[j] = sg * round_bf16(u[j]);
         }
         *reinterpret_cast<uint4*>(out + (size_t)m * ldo + f0) = pack8(o);
     }
@@ -241,7 +224,7 @@ __global__ __launch_bounds__(256) void swiglu_kernel(const uint16_t* __restrict_
         unpack8(*reinterpret_cast<const uint4*>(gu + (size_t)m * ldgu + F + c * 8), u);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float s = bf16_to_f32(f32_to_bf16(fo1_silu(g[j])));
+            const float s = round_bf16(fo1_silu(g[j]));
             o[j] = s * u[j];
         }
         *reinterpret_cast<uint4*>(out + (size_t)m * ldo + c * 8) = pack8(o);
@@ -261,7 +244,7 @@ __global__ __launch_bounds__(256) void bias_act_kernel(const uint16_t* __restric
             float bf[8];
             unpack8(*reinterpret_cast<const uint4*>(bias + c * 8), bf);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) f[j] = bf16_to_f32(f32_to_bf16(f[j] + bf[j]));
+            for (int j = 0; j < 8; ++j) f[j] = round_bf16(f[j] + bf[j]);
         }
         if (act == 1) {
 #pragma unroll
@@ -403,7 +386,7 @@ __global__ __launch_bounds__(256) void rmsnorm_quant_e4m3_kernel(const uint16_t*
             unpack8(v[i], f);
             unpack8(*reinterpret_cast<const uint4*>(w + c * 8), wf);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = wf[j] * bf16_to_f32(f32_to_bf16(f[j] * rstd));
+            for (int j = 0; j < 8; ++j) o[j] = wf[j] * round_bf16(f[j] * rstd);
             v[i] = pack8(o);                              // the bf16 row rmsnorm would have written
             unpack8(v[i], o);
 #pragma unroll

@@ -10,17 +10,6 @@
 
 namespace fo1 {
 
-__device__ __forceinline__ void unpack8r(const uint4& u, float (&f)[8]) {
-    f[0] = bf16_lo(u.x); f[1] = bf16_hi(u.x); f[2] = bf16_lo(u.y); f[3] = bf16_hi(u.y);
-    f[4] = bf16_lo(u.z); f[5] = bf16_hi(u.z); f[6] = bf16_lo(u.w); f[7] = bf16_hi(u.w);
-}
-__device__ __forceinline__ uint4 pack8r(const float (&f)[8]) {
-    uint4 u;
-    u.x = pack_bf16x2(f[0], f[1]); u.y = pack_bf16x2(f[2], f[3]);
-    u.z = pack_bf16x2(f[4], f[5]); u.w = pack_bf16x2(f[6], f[7]);
-    return u;
-}
-__device__ __forceinline__ float rb(float v) { return bf16_to_f32(f32_to_bf16(v)); }
 
 // x: [L, ld] rows; heads [0, n_heads) of width HD starting at column col0 are rotated in place
 // (n_heads counts q heads + k heads when they are adjacent).  cos/sin: bf16 [L, HD].
@@ -42,18 +31,18 @@ __device__ __forceinline__ void rope_llm_body(uint16_t* __restrict__ x, int ld, 
         uint16_t* p = x + (long long)t * ld + col0 + hd * HD;
         const int d0 = c * 8;
         float a[8], b[8], ca[8], sa[8], cb[8], sb[8], oa[8], ob[8];
-        unpack8r(*reinterpret_cast<const uint4*>(p + d0), a);             // x[d],        d <  HD/2
-        unpack8r(*reinterpret_cast<const uint4*>(p + d0 + HD / 2), b);    // x[d + HD/2]
-        unpack8r(*reinterpret_cast<const uint4*>(cosb + (long long)(row0 + t) * HD + d0), ca);
-        unpack8r(*reinterpret_cast<const uint4*>(sinb + (long long)(row0 + t) * HD + d0), sa);
-        unpack8r(*reinterpret_cast<const uint4*>(cosb + (long long)(row0 + t) * HD + d0 + HD / 2), cb);
-        unpack8r(*reinterpret_cast<const uint4*>(sinb + (long long)(row0 + t) * HD + d0 + HD / 2), sb);
+        unpack8(*reinterpret_cast<const uint4*>(p + d0), a);             // x[d],        d <  HD/2
+        unpack8(*reinterpret_cast<const uint4*>(p + d0 + HD / 2), b);    // x[d + HD/2]
+        unpack8(*reinterpret_cast<const uint4*>(cosb + (long long)(row0 + t) * HD + d0), ca);
+        unpack8(*reinterpret_cast<const uint4*>(sinb + (long long)(row0 + t) * HD + d0), sa);
+        unpack8(*reinterpret_cast<const uint4*>(cosb + (long long)(row0 + t) * HD + d0 + HD / 2), cb);
+        unpack8(*reinterpret_cast<const uint4*>(sinb + (long long)(row0 + t) * HD + d0 + HD / 2), sb);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            oa[j] = rb(a[j] * ca[j]) + rb(-b[j] * sa[j]);  // rotate_half: first half pairs with -x2
-            ob[j] = rb(b[j] * cb[j]) + rb(a[j] * sb[j]);   //              second half pairs with x1
+            oa[j] = round_bf16(a[j] * ca[j]) + round_bf16(-b[j] * sa[j]);  // rotate_half: first half pairs with -x2
+            ob[j] = round_bf16(b[j] * cb[j]) + round_bf16(a[j] * sb[j]);   //              second half pairs with x1
         }
-        const uint4 ua = pack8r(oa), ub = pack8r(ob);
+        const uint4 ua = pack8(oa), ub = pack8(ob);
         *reinterpret_cast<uint4*>(p + d0) = ua;
         *reinterpret_cast<uint4*>(p + d0 + HD / 2) = ub;
         if (kcache && hd >= k_first_head) {
@@ -85,8 +74,8 @@ __device__ __forceinline__ void rope_vit_body(uint16_t* __restrict__ x, int ld, 
         uint16_t* p = x + (long long)t * ld + hd * HD;
         const int d0 = c * 8;
         float a[8], b[8], oa[8], ob[8];
-        unpack8r(*reinterpret_cast<const uint4*>(p + d0), a);
-        unpack8r(*reinterpret_cast<const uint4*>(p + d0 + HH), b);
+        unpack8(*reinterpret_cast<const uint4*>(p + d0), a);
+        unpack8(*reinterpret_cast<const uint4*>(p + d0 + HH), b);
         const float* cp = cosf_ + (long long)t * HH + d0;
         const float* sp = sinf_ + (long long)t * HH + d0;
 #pragma unroll
@@ -97,8 +86,8 @@ __device__ __forceinline__ void rope_vit_body(uint16_t* __restrict__ x, int ld, 
             oa[j] = __builtin_fmaf(a[j], cs, -(b[j] * sn));
             ob[j] = __builtin_fmaf(b[j], cs, a[j] * sn);
         }
-        *reinterpret_cast<uint4*>(p + d0) = pack8r(oa);
-        *reinterpret_cast<uint4*>(p + d0 + HH) = pack8r(ob);
+        *reinterpret_cast<uint4*>(p + d0) = pack8(oa);
+        *reinterpret_cast<uint4*>(p + d0 + HH) = pack8(ob);
     }
 }
 
@@ -207,11 +196,11 @@ __global__ __launch_bounds__(256) void decode_qkv_post_kernel(uint16_t* __restri
             float v[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
             if (bias) {
                 float bf[8];
-                unpack8r(*reinterpret_cast<const uint4*>(bias + c * 8), bf);
+                unpack8(*reinterpret_cast<const uint4*>(bias + c * 8), bf);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[j] += bf[j];
             }
-            *reinterpret_cast<uint4*>(lrow + c * 8) = pack8r(v);
+            *reinterpret_cast<uint4*>(lrow + c * 8) = pack8(v);
         }
         __syncthreads();
     }
@@ -225,18 +214,18 @@ __global__ __launch_bounds__(256) void decode_qkv_post_kernel(uint16_t* __restri
         const uint16_t* ps = PART ? lrow + hd * HD : p;
         const int d0 = c * 8;
         float a[8], b[8], ca[8], sa[8], cb[8], sb[8], oa[8], ob[8];
-        unpack8r(*reinterpret_cast<const uint4*>(ps + d0), a);
-        unpack8r(*reinterpret_cast<const uint4*>(ps + d0 + HD / 2), b);
-        unpack8r(*reinterpret_cast<const uint4*>(cosb + (long long)row * HD + d0), ca);
-        unpack8r(*reinterpret_cast<const uint4*>(sinb + (long long)row * HD + d0), sa);
-        unpack8r(*reinterpret_cast<const uint4*>(cosb + (long long)row * HD + d0 + HD / 2), cb);
-        unpack8r(*reinterpret_cast<const uint4*>(sinb + (long long)row * HD + d0 + HD / 2), sb);
+        unpack8(*reinterpret_cast<const uint4*>(ps + d0), a);
+        unpack8(*reinterpret_cast<const uint4*>(ps + d0 + HD / 2), b);
+        unpack8(*reinterpret_cast<const uint4*>(cosb + (long long)row * HD + d0), ca);
+        unpack8(*reinterpret_cast<const uint4*>(sinb + (long long)row * HD + d0), sa);
+        unpack8(*reinterpret_cast<const uint4*>(cosb + (long long)row * HD + d0 + HD / 2), cb);
+        unpack8(*reinterpret_cast<const uint4*>(sinb + (long long)row * HD + d0 + HD / 2), sb);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            oa[j] = rb(a[j] * ca[j]) + rb(-b[j] * sa[j]);
-            ob[j] = rb(b[j] * cb[j]) + rb(a[j] * sb[j]);
+            oa[j] = round_bf16(a[j] * ca[j]) + round_bf16(-b[j] * sa[j]);
+            ob[j] = round_bf16(b[j] * cb[j]) + round_bf16(a[j] * sb[j]);
         }
-        const uint4 ua = pack8r(oa), ub = pack8r(ob);
+        const uint4 ua = pack8(oa), ub = pack8(ob);
         if (!PART || hd < n_q) {
             *reinterpret_cast<uint4*>(p + d0) = ua;
             *reinterpret_cast<uint4*>(p + d0 + HD / 2) = ub;

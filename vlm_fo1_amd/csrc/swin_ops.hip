@@ -7,14 +7,6 @@
 
 namespace fo1 {
 
-__device__ __forceinline__ void sw_un8(const uint4& v, float (&f)[8]) {
-    f[0] = bf16_lo(v.x); f[1] = bf16_hi(v.x); f[2] = bf16_lo(v.y); f[3] = bf16_hi(v.y);
-    f[4] = bf16_lo(v.z); f[5] = bf16_hi(v.z); f[6] = bf16_lo(v.w); f[7] = bf16_hi(v.w);
-}
-__device__ __forceinline__ uint4 sw_pk8(const float (&f)[8]) {
-    return uint4{pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7])};
-}
-
 // xw[window (wy, wx), local (iy, ix)] = padded_x[(wy*ws + iy + shift) mod Hp][(wx*ws + ix + shift) mod Wp]   (zero outside H x W)
 __global__ __launch_bounds__(256) void swin_partition_kernel(const uint16_t* __restrict__ x, uint16_t* __restrict__ xw, int H, int W, int C, int ws,
                                                              int shift, int nWy, int nWx, int B) {
@@ -51,11 +43,11 @@ __global__ __launch_bounds__(256) void swin_reverse_add_kernel(const uint16_t* _
         wsft = wsft < 0 ? wsft + Wp : wsft;
         const int row = (img * nW + (hs / ws) * nWx + (wsft / ws)) * ws * ws + (hs % ws) * ws + (wsft % ws);
         float a[8], b[8];
-        sw_un8(*reinterpret_cast<const uint4*>(yw + (long long)row * C + c * 8), a);
-        sw_un8(*reinterpret_cast<const uint4*>(shortcut + (long long)pix * C + c * 8), b);
+        unpack8(*reinterpret_cast<const uint4*>(yw + (long long)row * C + c * 8), a);
+        unpack8(*reinterpret_cast<const uint4*>(shortcut + (long long)pix * C + c * 8), b);
 #pragma unroll
         for (int j = 0; j < 8; ++j) a[j] += b[j];
-        *reinterpret_cast<uint4*>(y + (long long)pix * C + c * 8) = sw_pk8(a);
+        *reinterpret_cast<uint4*>(y + (long long)pix * C + c * 8) = pack8(a);
     }
 }
 
@@ -90,7 +82,7 @@ __global__ __launch_bounds__(256) void groupnorm_partial_kernel(const uint16_t* 
     for (int i = threadIdx.x; i < (t1 - t0) * per; i += 256) {
         const int t = t0 + i / per, pc = i - (i / per) * per;
         float f[8];
-        sw_un8(*reinterpret_cast<const uint4*>(x + (long long)t * ld + g * cg + pc * 8), f);
+        unpack8(*reinterpret_cast<const uint4*>(x + (long long)t * ld + g * cg + pc * 8), f);
 #pragma unroll
         for (int j = 0; j < 8; ++j) { a += f[j]; b += f[j] * f[j]; }
     }
@@ -125,12 +117,12 @@ __global__ __launch_bounds__(256) void groupnorm_apply_kernel(const uint16_t* __
     for (int i = threadIdx.x; i < (t1 - t0) * per; i += 256) {
         const int t = t0 + i / per, pc = i - (i / per) * per;
         float f[8], w[8], b[8];
-        sw_un8(*reinterpret_cast<const uint4*>(x + (long long)t * ld + g * cg + pc * 8), f);
-        sw_un8(*reinterpret_cast<const uint4*>(weight + g * cg + pc * 8), w);
-        sw_un8(*reinterpret_cast<const uint4*>(bias + g * cg + pc * 8), b);
+        unpack8(*reinterpret_cast<const uint4*>(x + (long long)t * ld + g * cg + pc * 8), f);
+        unpack8(*reinterpret_cast<const uint4*>(weight + g * cg + pc * 8), w);
+        unpack8(*reinterpret_cast<const uint4*>(bias + g * cg + pc * 8), b);
 #pragma unroll
         for (int j = 0; j < 8; ++j) f[j] = (f[j] - mean) * rstd * w[j] + b[j];
-        *reinterpret_cast<uint4*>(y + (long long)t * ldy + g * cg + pc * 8) = sw_pk8(f);
+        *reinterpret_cast<uint4*>(y + (long long)t * ldy + g * cg + pc * 8) = pack8(f);
     }
 }
 

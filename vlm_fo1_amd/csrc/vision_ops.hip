@@ -12,17 +12,6 @@
 
 namespace fo1 {
 
-__device__ __forceinline__ void un8(const uint4& u, float (&f)[8]) {
-    f[0] = bf16_lo(u.x); f[1] = bf16_hi(u.x); f[2] = bf16_lo(u.y); f[3] = bf16_hi(u.y);
-    f[4] = bf16_lo(u.z); f[5] = bf16_hi(u.z); f[6] = bf16_lo(u.w); f[7] = bf16_hi(u.w);
-}
-__device__ __forceinline__ uint4 pk8(const float (&f)[8]) {
-    uint4 u;
-    u.x = pack_bf16x2(f[0], f[1]); u.y = pack_bf16x2(f[2], f[3]);
-    u.z = pack_bf16x2(f[4], f[5]); u.w = pack_bf16x2(f[6], f[7]);
-    return u;
-}
-__device__ __forceinline__ float rbf(float v) { return bf16_to_f32(f32_to_bf16(v)); }
 
 // Ragged image batches (images of DIFFERENT sizes packed row-wise into one map, include/fo1.h fo1_img_seg): when `segs` is given,
 // workgroup column blockIdx.y works on image blockIdx.y alone — its own H x W, its rows starting at in_row0 / out_row0 — with exactly
@@ -41,7 +30,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const uint16_t* __restri
         const int img0 = (pix / HW) * HW, lp = pix - img0;
         const int h = lp / W, w = lp - h * W;
         float acc[8], ctr[8];
-        un8(*reinterpret_cast<const uint4*>(bias + c * 8), acc);
+        unpack8(*reinterpret_cast<const uint4*>(bias + c * 8), acc);
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
             const int hh = h + ky - 1;
@@ -51,8 +40,8 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const uint16_t* __restri
                 const int ww = w + kx - 1;
                 if (ww < 0 || ww >= W) continue;
                 float xv[8], wv[8];
-                un8(*reinterpret_cast<const uint4*>(x + ((long long)img0 + hh * W + ww) * C + c * 8), xv);
-                un8(*reinterpret_cast<const uint4*>(wt + (ky * 3 + kx) * C + c * 8), wv);
+                unpack8(*reinterpret_cast<const uint4*>(x + ((long long)img0 + hh * W + ww) * C + c * 8), xv);
+                unpack8(*reinterpret_cast<const uint4*>(wt + (ky * 3 + kx) * C + c * 8), wv);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) acc[j] = fmaf(xv[j], wv[j], acc[j]);
                 if (ky == 1 && kx == 1) {
@@ -62,8 +51,8 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const uint16_t* __restri
             }
         }
 #pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = ctr[j] + rbf(acc[j]);
-        *reinterpret_cast<uint4*>(y + (long long)pix * C + c * 8) = pk8(acc);
+        for (int j = 0; j < 8; ++j) acc[j] = ctr[j] + round_bf16(acc[j]);
+        *reinterpret_cast<uint4*>(y + (long long)pix * C + c * 8) = pack8(acc);
     }
 }
 
@@ -73,11 +62,6 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const uint16_t* __restri
 // One wave per pixel: lane l owns channel chunks l, l+64, ... (8 channels each), so the taps are 1 KB-contiguous reads and the
 // row statistics are one wave reduction.  Arithmetic order matches the two separate kernels bit for bit.
 constexpr int kDwLnChunks = 4;   // C <= 64 * 4 * 8 = 2048
-__device__ __forceinline__ float dw_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 // PPW pixels per wave (C = 256 fills only half a wave's lanes with one pixel).  All 18 loads of a chunk are issued together: taps outside
 // the map read a clamped (valid) address and meet a zero weight — fmaf(x, 0, acc) leaves acc as it was, so the sums are the ones the
 // branchy form produced (a load under a branch costs a vmcnt(0) at the join: nine dependent L2 round trips per pixel, 3 TB/s).
@@ -109,7 +93,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_ln_kernel(const uint16_t* __res
         const int c = sub + i * LPP;
         if (c < chunks) {
             float acc[8], ctr[8];
-            un8(*reinterpret_cast<const uint4*>(bias + c * 8), acc);
+            unpack8(*reinterpret_cast<const uint4*>(bias + c * 8), acc);
             uint4 xr[9], wr[9];
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky)
@@ -125,8 +109,8 @@ __global__ __launch_bounds__(256) void dwconv3x3_ln_kernel(const uint16_t* __res
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
                 float xv[8], wv[8];
-                un8(xr[t], xv);
-                un8(wr[t], wv);
+                unpack8(xr[t], xv);
+                unpack8(wr[t], wv);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) acc[j] = fmaf(xv[j], wv[j], acc[j]);
                 if (t == 4) {
@@ -135,10 +119,10 @@ __global__ __launch_bounds__(256) void dwconv3x3_ln_kernel(const uint16_t* __res
                 }
             }
 #pragma unroll
-            for (int j = 0; j < 8; ++j) acc[j] = ctr[j] + rbf(acc[j]);
-            const uint4 packed = pk8(acc);
+            for (int j = 0; j < 8; ++j) acc[j] = ctr[j] + round_bf16(acc[j]);
+            const uint4 packed = pack8(acc);
             if (live) *reinterpret_cast<uint4*>(y + (long long)pix * C + c * 8) = packed;
-            un8(packed, val[i]);              // LayerNorm sees the bf16 values that were stored
+            unpack8(packed, val[i]);              // LayerNorm sees the bf16 values that were stored
 #pragma unroll
             for (int j = 0; j < 8; ++j) s += val[i][j];
         }
@@ -166,11 +150,11 @@ __global__ __launch_bounds__(256) void dwconv3x3_ln_kernel(const uint16_t* __res
         const int c = sub + i * LPP;
         if (c < chunks && live) {
             float wf[8], bf[8], o[8];
-            un8(*reinterpret_cast<const uint4*>(ln_w + c * 8), wf);
-            un8(*reinterpret_cast<const uint4*>(ln_b + c * 8), bf);
+            unpack8(*reinterpret_cast<const uint4*>(ln_w + c * 8), wf);
+            unpack8(*reinterpret_cast<const uint4*>(ln_b + c * 8), bf);
 #pragma unroll
             for (int j = 0; j < 8; ++j) o[j] = fmaf((val[i][j] - mean) * rstd, wf[j], bf[j]);
-            *reinterpret_cast<uint4*>(hout + (long long)pix * C + c * 8) = pk8(o);
+            *reinterpret_cast<uint4*>(hout + (long long)pix * C + c * 8) = pack8(o);
         }
     }
 }
@@ -251,14 +235,14 @@ __global__ __launch_bounds__(256) void dwconv3x3_ln_run_kernel(const uint16_t* _
             __builtin_amdgcn_sched_barrier(0);   // the next column is requested BEFORE this pixel's taps (hipcc would sink the loads to their use)
             const bool lok = w > 0, rgt = w + 1 < W;
             float acc[8], ctr[8];
-            un8(bq, acc);
+            unpack8(bq, acc);
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
                 const int ky = t / 3, kx = t % 3;
                 float xv[8], wv[8];
-                un8(win[ky][(s + kx + 3) & 3], xv);
+                unpack8(win[ky][(s + kx + 3) & 3], xv);
                 const uint4 wsel = kx == 0 ? (lok ? wq[t] : zero4) : (kx == 2 ? (rgt ? wq[t] : zero4) : wq[t]);
-                un8(wsel, wv);
+                unpack8(wsel, wv);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) acc[j] = fmaf(xv[j], wv[j], acc[j]);
                 if (t == 4) {
@@ -267,8 +251,8 @@ __global__ __launch_bounds__(256) void dwconv3x3_ln_run_kernel(const uint16_t* _
                 }
             }
 #pragma unroll
-            for (int j = 0; j < 8; ++j) acc[j] = ctr[j] + rbf(acc[j]);
-            const uint4 pv = pk8(acc);
+            for (int j = 0; j < 8; ++j) acc[j] = ctr[j] + round_bf16(acc[j]);
+            const uint4 pv = pack8(acc);
             pk[i][s] = pv;
             const uint32_t soff = run_live && w < W ? row_off + (uint32_t)w * (uint32_t)C * 2u : 0xC0000000u;
             __builtin_amdgcn_raw_buffer_store_b128(v4u{pv.x, pv.y, pv.z, pv.w}, rs_y, soff + (uint32_t)(i * LPP * 16), 0, 0);
@@ -288,7 +272,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_ln_run_kernel(const uint16_t* _
         float sm = 0.f;
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
-            un8(pk[i][s], val[i]);
+            unpack8(pk[i][s], val[i]);
 #pragma unroll
             for (int j = 0; j < 8; ++j) sm += val[i][j];
         }
@@ -305,11 +289,11 @@ __global__ __launch_bounds__(256) void dwconv3x3_ln_run_kernel(const uint16_t* _
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
             float wf[8], bf[8], o[8];
-            un8(lw[i], wf);
-            un8(lb[i], bf);
+            unpack8(lw[i], wf);
+            unpack8(lb[i], bf);
 #pragma unroll
             for (int j = 0; j < 8; ++j) o[j] = fmaf((val[i][j] - mean) * rstd, wf[j], bf[j]);
-            const uint4 po = pk8(o);
+            const uint4 po = pack8(o);
             __builtin_amdgcn_raw_buffer_store_b128(v4u{po.x, po.y, po.z, po.w}, rs_h, soff + (uint32_t)(i * LPP * 16), 0, 0);
         }
     }
@@ -387,11 +371,11 @@ __global__ __launch_bounds__(256) void window_reverse_add_kernel(const uint16_t*
         const int h = lp / W, w = lp - h * W;
         const int row = (img * nW + (h / ws) * nWx + (w / ws)) * ws * ws + (h % ws) * ws + (w % ws);
         float a[8], b[8];
-        un8(*reinterpret_cast<const uint4*>(yw + (long long)row * C + c * 8), a);
-        un8(*reinterpret_cast<const uint4*>(shortcut + (long long)pix * C + c * 8), b);
+        unpack8(*reinterpret_cast<const uint4*>(yw + (long long)row * C + c * 8), a);
+        unpack8(*reinterpret_cast<const uint4*>(shortcut + (long long)pix * C + c * 8), b);
 #pragma unroll
         for (int j = 0; j < 8; ++j) a[j] += b[j];
-        *reinterpret_cast<uint4*>(y + (long long)pix * C + c * 8) = pk8(a);
+        *reinterpret_cast<uint4*>(y + (long long)pix * C + c * 8) = pack8(a);
     }
 }
 
@@ -423,7 +407,7 @@ __global__ __launch_bounds__(256) void chattn_gram_kernel(const uint16_t* __rest
             const int which = t >> 8, r = (t & 255) >> 2, cc = t & 3;
             float f[8];
             if (n0 + r < n_end) {
-                un8(*reinterpret_cast<const uint4*>(qkv + (long long)(n0 + r) * ld + which * C + g * 32 + cc * 8), f);
+                unpack8(*reinterpret_cast<const uint4*>(qkv + (long long)(n0 + r) * ld + which * C + g * 32 + cc * 8), f);
             } else {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) f[j] = 0.f;
@@ -557,7 +541,7 @@ __global__ __launch_bounds__(1024) void chattn_softmax_kernel(const float* __res
         s3 += p[(long long)(k + 3) * stride];
     }
     for (; k < n_chunks; ++k) s0 += p[(long long)k * stride];
-    float s = rbf(((s0 + s1) + (s2 + s3)) * scale);
+    float s = round_bf16(((s0 + s1) + (s2 + s3)) * scale);
     float m = s;
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
@@ -565,7 +549,7 @@ __global__ __launch_bounds__(1024) void chattn_softmax_kernel(const float* __res
     float sum = e;
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    A[((long long)g * 32 + r) * 32 + c] = rbf(e / sum);
+    A[((long long)g * 32 + r) * 32 + c] = round_bf16(e / sum);
 }
 
 // Phase 3: out[n, g*32 + c] = bf16( sum_c' A[g][c][c'] * v[n, g*32 + c'] )
@@ -739,14 +723,14 @@ __global__ __launch_bounds__(256) void maxpool2_kernel(const uint16_t* __restric
         const int oy = lp / Wo, ox = lp - oy * Wo;
         const long long ib = (long long)img * H * W;
         float m[8], t[8];
-        un8(*reinterpret_cast<const uint4*>(x + (ib + (long long)(2 * oy) * W + 2 * ox) * C + c * 8), m);
+        unpack8(*reinterpret_cast<const uint4*>(x + (ib + (long long)(2 * oy) * W + 2 * ox) * C + c * 8), m);
 #pragma unroll
         for (int q = 1; q < 4; ++q) {
-            un8(*reinterpret_cast<const uint4*>(x + (ib + (long long)(2 * oy + (q >> 1)) * W + 2 * ox + (q & 1)) * C + c * 8), t);
+            unpack8(*reinterpret_cast<const uint4*>(x + (ib + (long long)(2 * oy + (q >> 1)) * W + 2 * ox + (q & 1)) * C + c * 8), t);
 #pragma unroll
             for (int j = 0; j < 8; ++j) m[j] = fmaxf(m[j], t[j]);
         }
-        *reinterpret_cast<uint4*>(y + (long long)pix * C + c * 8) = pk8(m);
+        *reinterpret_cast<uint4*>(y + (long long)pix * C + c * 8) = pack8(m);
     }
 }
 
@@ -762,7 +746,7 @@ __global__ __launch_bounds__(256) void nchw_to_hwc8_kernel(const T* __restrict__
             if constexpr (sizeof(T) == 2) f[c] = bf16_to_f32(((const uint16_t*)img)[(b * 3 + c) * HW + lp]);
             else f[c] = ((const float*)img)[(b * 3 + c) * HW + lp];
         }
-        *reinterpret_cast<uint4*>(out + i * 8) = pk8(f);
+        *reinterpret_cast<uint4*>(out + i * 8) = pack8(f);
     }
 }
 

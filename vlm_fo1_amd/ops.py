@@ -34,6 +34,21 @@ def _rows(t: torch.Tensor, name: str):
     return t.data_ptr(), t.stride(0), t.shape[0], t.shape[1]
 
 
+def _ptr(t: Optional[torch.Tensor]):
+    """Optional tensor -> device pointer, or None (a NULL operand)."""
+    return None if t is None else t.data_ptr()
+
+
+def _residual(residual: Optional[torch.Tensor], check: bool = False):
+    """Optional residual rows -> (pointer, row stride), (None, 0) without one."""
+    if residual is None:
+        return None, 0
+    if check:
+        _chk(residual, "residual")
+    pr, ldr, _, _ = _rows(residual, "residual")
+    return pr, ldr
+
+
 def _out_rows(out: Optional[torch.Tensor], rows: int, cols: int, device) -> torch.Tensor:
     """A new [rows, cols] bf16 output, or the caller's `out` checked to be such a row-major view (its row stride may be padded)."""
     if out is None:
@@ -219,11 +234,8 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
         out = torch.empty(M, n_out, dtype=torch.float32 if out_f32 else torch.bfloat16, device=a.device)
     po, ldc, Mo, No = _rows(out, "out")
     assert (Mo, No) == (M, n_out)
-    pr, ldr = (None, 0)
-    if residual is not None:
-        _chk(residual, "residual")
-        pr, ldr, Mr, Nr = _rows(residual, "residual")
-        assert (Mr, Nr) == (M, N)
+    pr, ldr = _residual(residual, check=True)
+    assert residual is None or tuple(residual.shape) == (M, N)
     if bias is not None:
         _chk(bias, "bias")
         assert bias.numel() == N and bias.is_contiguous()
@@ -233,7 +245,7 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
             aq, sa = quantize_rows_fp8(a)
             return gemm_fp8(aq, sa, fw, bias, residual, act, out)
     ws = _gemm_workspace(a.device)
-    rc = _L.load().fo1_gemm_bf16_ws(pa, lda, pw, ldw, bias.data_ptr() if bias is not None else None, pr, ldr, po, ldc,
+    rc = _L.load().fo1_gemm_bf16_ws(pa, lda, pw, ldw, _ptr(bias), pr, ldr, po, ldc,
                                     M, N, K, act, 1 if out_f32 else 0, ws.data_ptr(), ws.numel(), _stream())
     _L.check(rc, "fo1_gemm_bf16_ws")
     return out
@@ -277,16 +289,13 @@ def gemm_fp8(aq: torch.Tensor, sa: torch.Tensor, w: Fp8Weight, bias: Optional[to
         out = torch.empty(M, n_out, dtype=torch.bfloat16, device=aq.device)
     po, ldc, Mo, No = _rows(out, "out")
     assert (Mo, No) == (M, n_out)
-    pr, ldr = (None, 0)
-    if residual is not None:
-        _chk(residual, "residual")
-        pr, ldr, Mr, Nr = _rows(residual, "residual")
-        assert (Mr, Nr) == (M, N)
+    pr, ldr = _residual(residual, check=True)
+    assert residual is None or tuple(residual.shape) == (M, N)
     if bias is not None:
         _chk(bias, "bias")
         assert bias.numel() == N and bias.is_contiguous()
     rc = _L.load().fo1_gemm_fp8(aq.data_ptr(), aq.stride(0), sa.data_ptr(), w.q.data_ptr(), w.q.stride(0), w.scale.data_ptr(),
-                                bias.data_ptr() if bias is not None else None, pr, ldr, po, ldc, M, N, K, act, _stream())
+                                _ptr(bias), pr, ldr, po, ldc, M, N, K, act, _stream())
     _L.check(rc, "fo1_gemm_fp8")
     return out
 
@@ -461,7 +470,7 @@ def conv3x3_gemm(xpad: torch.Tensor, plan: Conv3x3Plan, w: torch.Tensor, bias: O
     pw, ldw, N, K = _rows(w, "w")
     assert K == 9 * plan.cin
     out = torch.empty(plan.M_out, N, dtype=torch.bfloat16, device=xpad.device)
-    rc = _L.load().fo1_conv3x3_gemm_bf16(xpad.data_ptr(), plan.a_rows.data_ptr(), plan.Wp, plan.cin, pw, ldw, bias.data_ptr() if bias is not None else None,
+    rc = _L.load().fo1_conv3x3_gemm_bf16(xpad.data_ptr(), plan.a_rows.data_ptr(), plan.Wp, plan.cin, pw, ldw, _ptr(bias),
                                          out.data_ptr(), N, plan.M_out, N, int(act), _stream())
     _L.check(rc, "fo1_conv3x3_gemm_bf16")
     return out
@@ -494,7 +503,7 @@ def bias_act(x: torch.Tensor, bias: Optional[torch.Tensor], act: int, out: Optio
     if out is None:
         out = torch.empty(M, D, dtype=torch.bfloat16, device=x.device)
     po, ldo, _, _ = _rows(out, "out")
-    _L.check(_L.load().fo1_bias_act_bf16(p, ld, bias.data_ptr() if bias is not None else None, po, ldo, M, D, act, _stream()),
+    _L.check(_L.load().fo1_bias_act_bf16(p, ld, _ptr(bias), po, ldo, M, D, act, _stream()),
              "fo1_bias_act_bf16")
     return out
 
@@ -562,7 +571,7 @@ def rope_llm(qkv: torch.Tensor, n_heads: int, head_dim: int, cos: torch.Tensor, 
         assert kcache.dim() == 3 and kcache.shape[2] == head_dim and kcache.stride(2) == 1 and kcache.stride(1) == head_dim
         kc_ptr, kc_stride = kcache.data_ptr(), kcache.stride(0)
     _L.check(_L.load().fo1_rope_llm_bf16(p, ld, col0, n_heads, head_dim, cos.data_ptr(), sin.data_ptr(), L, kc_ptr,
-                                         k_first_head, kc_stride, pos0, dyn_state.data_ptr() if dyn_state is not None else None,
+                                         k_first_head, kc_stride, pos0, _ptr(dyn_state),
                                          _stream()), "fo1_rope_llm_bf16")
 
 
@@ -634,7 +643,7 @@ def qkv_proj_rope(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]
         _chk(cos, "cos", torch.float32); _chk(sin, "sin", torch.float32)
         assert cos.shape == (M, 40) and cos.is_contiguous() and sin.shape == (M, 40) and sin.is_contiguous()
         pk, ks = None, 0
-    rc = _L.load().fo1_qkv_proj_rope_bf16(px, ldx, pw, ldw, bias.data_ptr() if bias is not None else None, po, ldo, M, N, K, int(mode), int(n_q), int(n_kv),
+    rc = _L.load().fo1_qkv_proj_rope_bf16(px, ldx, pw, ldw, _ptr(bias), po, ldo, M, N, K, int(mode), int(n_q), int(n_kv),
                                           cos.data_ptr(), sin.data_ptr(), pk, ks, int(pos0), pv, ldv, _stream())
     _L.check(rc, "fo1_qkv_proj_rope_bf16")
     return out
@@ -658,27 +667,34 @@ def transpose_into(src: torch.Tensor, dst: torch.Tensor, col0: int = 0, dyn_col0
     p, ld, M, C = _rows(src, "src")
     pd, ldd, Cd, _ = _rows(dst, "dst")
     assert Cd == C
-    _L.check(_L.load().fo1_transpose_bf16(p, ld, pd, ldd, col0, dyn_col0.data_ptr() if dyn_col0 is not None else None, M, C,
+    _L.check(_L.load().fo1_transpose_bf16(p, ld, pd, ldd, col0, _ptr(dyn_col0), M, C,
                                           _stream()), "fo1_transpose_bf16")
+
+
+def _gemv_operands(x: Optional[torch.Tensor], w: torch.Tensor, residual: Optional[torch.Tensor], out: Optional[torch.Tensor], M: int, n_out,
+                   max_m: int):
+    """What the decode-step linears share: x [M, K] (None: the rows come from elsewhere, M is given) and w [N, K] checked, `out` [M, n_out(N)]
+    allocated unless given -> ((px, ldx), (pw, ldw), (pr, ldr), (po, ldc), (M, N, K), out)."""
+    _chk(w, "w")
+    pw, ldw, N, K = _rows(w, "w")
+    px, ldx = None, 0
+    if x is not None:
+        _chk(x, "x")
+        px, ldx, M, Kx = _rows(x, "x")
+        assert K == Kx
+    assert M <= max_m
+    if out is None:
+        out = torch.empty(M, n_out(N), dtype=torch.bfloat16, device=w.device)
+    po, ldc, _, _ = _rows(out, "out")
+    return (px, ldx), (pw, ldw), _residual(residual), (po, ldc), (M, N, K), out
 
 
 def gemv(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
          act: int = ACT_NONE, norm_weight: Optional[torch.Tensor] = None, norm_eps: float = 0.0,
          out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Decode-step projection: out[M<=4, N] = epilogue(rmsnorm?(x) @ w^T) (fo1_gemv_bf16)."""
-    _chk(x, "x"); _chk(w, "w")
-    px, ldx, M, K = _rows(x, "x")
-    pw, ldw, N, K2 = _rows(w, "w")
-    assert K == K2 and M <= 4
-    n_out = N // 2 if act == ACT_SWIGLU16 else N
-    if out is None:
-        out = torch.empty(M, n_out, dtype=torch.bfloat16, device=x.device)
-    po, ldc, _, _ = _rows(out, "out")
-    pr, ldr = (None, 0)
-    if residual is not None:
-        pr, ldr, _, _ = _rows(residual, "residual")
-    rc = _L.load().fo1_gemv_bf16(px, ldx, pw, ldw, bias.data_ptr() if bias is not None else None, pr, ldr, po, ldc, M, N, K, act,
-                                 norm_weight.data_ptr() if norm_weight is not None else None, float(norm_eps), _stream())
+    xs, ws, rs, os_, shape, out = _gemv_operands(x, w, residual, out, 0, lambda N: N // 2 if act == ACT_SWIGLU16 else N, 4)
+    rc = _L.load().fo1_gemv_bf16(*xs, *ws, _ptr(bias), *rs, *os_, *shape, act, _ptr(norm_weight), float(norm_eps), _stream())
     _L.check(rc, "fo1_gemv_bf16")
     return out
 
@@ -692,17 +708,7 @@ def gemv_batch(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = 
                out: Optional[torch.Tensor] = None, qkv: Optional[dict] = None) -> torch.Tensor:
     """Decode-step projection for M <= 32 sequences (fo1_gemv_batch_bf16).  qkv (mode GB_QKV): dict(n_q, n_kv, cos, sin, state,
     kcache [n_kv, rows, 128], vtcache [n_kv*128, rows]) — `out` then receives only the rotated q rows [M, n_q*128]."""
-    _chk(x, "x"); _chk(w, "w")
-    px, ldx, M, K = _rows(x, "x")
-    pw, ldw, N, K2 = _rows(w, "w")
-    assert K == K2 and M <= 32
-    n_out = N // 2 if mode == GB_SWIGLU else (qkv["n_q"] * 128 if mode == GB_QKV else N)
-    if out is None:
-        out = torch.empty(M, n_out, dtype=torch.bfloat16, device=x.device)
-    po, ldc, _, _ = _rows(out, "out")
-    pr, ldr = (None, 0)
-    if residual is not None:
-        pr, ldr, _, _ = _rows(residual, "residual")
+    xs, ws, rs, os_, shape, out = _gemv_operands(x, w, residual, out, 0, lambda N: N // 2 if mode == GB_SWIGLU else (qkv["n_q"] * 128 if mode == GB_QKV else N), 32)
     if mode == GB_QKV:
         kc, vt = qkv["kcache"], qkv["vtcache"]
         _chk(kc, "kcache"); _chk(vt, "vtcache")
@@ -711,8 +717,7 @@ def gemv_batch(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = 
         extra = (qkv["n_q"], qkv["n_kv"], qkv["cos"].data_ptr(), qkv["sin"].data_ptr(), qkv["state"].data_ptr(), kc.data_ptr(), kc.stride(0), pv, ldv)
     else:
         extra = (0, 0, None, None, None, None, 0, None, 0)
-    rc = _L.load().fo1_gemv_batch_bf16(px, ldx, pw, ldw, bias.data_ptr() if bias is not None else None, pr, ldr, po, ldc, M, N, K, mode,
-                                       norm_weight.data_ptr() if norm_weight is not None else None, float(norm_eps), *extra, _stream())
+    rc = _L.load().fo1_gemv_batch_bf16(*xs, *ws, _ptr(bias), *rs, *os_, *shape, mode, _ptr(norm_weight), float(norm_eps), *extra, _stream())
     _L.check(rc, "fo1_gemv_batch_bf16")
     return out
 
@@ -749,18 +754,10 @@ def attention_decode_batch_partials(q: torch.Tensor, kcache: torch.Tensor, vtcac
 def gemv_attn_combine(part: torch.Tensor, part_seq_stride: int, state: torch.Tensor, kv_chunk: int, n_q_heads: int, n_kv_heads: int, w: torch.Tensor,
                       residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """o-projection of a decode step at <= 2 sequences, the attention combine in its prologue (fo1_gemv_attn_combine_bf16)."""
-    _chk(w, "w")
-    pw, ldw, N, K = _rows(w, "w")
-    M = state.shape[0]
-    assert K == n_q_heads * 128 and M <= 2 and state.dtype == torch.int32 and state.is_contiguous()
-    if out is None:
-        out = torch.empty(M, N, dtype=torch.bfloat16, device=w.device)
-    po, ldc, _, _ = _rows(out, "out")
-    pr, ldr = (None, 0)
-    if residual is not None:
-        pr, ldr, _, _ = _rows(residual, "residual")
-    rc = _L.load().fo1_gemv_attn_combine_bf16(part.data_ptr(), int(part_seq_stride), state.data_ptr(), int(kv_chunk), n_q_heads, n_kv_heads, pw, ldw, pr, ldr,
-                                              po, ldc, M, N, _stream())
+    _, ws, rs, os_, (M, N, K), out = _gemv_operands(None, w, residual, out, state.shape[0], lambda N: N, 2)
+    assert K == n_q_heads * 128 and state.dtype == torch.int32 and state.is_contiguous()
+    rc = _L.load().fo1_gemv_attn_combine_bf16(part.data_ptr(), int(part_seq_stride), state.data_ptr(), int(kv_chunk), n_q_heads, n_kv_heads, *ws, *rs,
+                                              *os_, M, N, _stream())
     _L.check(rc, "fo1_gemv_attn_combine_bf16")
     return out
 
@@ -821,7 +818,7 @@ def splitk_residual_rmsnorm(part: torch.Tensor, splits: int, residual: torch.Ten
     px, ldx, _, _ = _rows(x_out, "x_out")
     pn, ldn, _, _ = _rows(xn_out, "xn_out")
     assert part.dtype == torch.float32 and part.numel() >= splits * M * N and norm_weight.numel() == N
-    rc = _L.load().fo1_splitk_residual_rmsnorm_bf16(part.data_ptr(), int(splits), M, N, bias.data_ptr() if bias is not None else None, pr, ldr, px, ldx,
+    rc = _L.load().fo1_splitk_residual_rmsnorm_bf16(part.data_ptr(), int(splits), M, N, _ptr(bias), pr, ldr, px, ldx,
                                                     norm_weight.data_ptr(), float(eps), pn, ldn, _stream())
     _L.check(rc, "fo1_splitk_residual_rmsnorm_bf16")
 
@@ -844,11 +841,8 @@ def gemm_wtiled(a: torch.Tensor, w_tiled: torch.Tensor, bias: Optional[torch.Ten
     N = w_tiled.shape[0] * 128
     out = _out_rows(out, M, N // 2 if act == ACT_SWIGLU16 else N, a.device)
     po, ldc, _, _ = _rows(out, "out")
-    pr, ldr = (None, 0)
-    if residual is not None:
-        _chk(residual, "residual")
-        pr, ldr, _, _ = _rows(residual, "residual")
-    rc = _L.load().fo1_gemm_bf16_wtiled(pa, lda, w_tiled.data_ptr(), bias.data_ptr() if bias is not None else None, pr, ldr, po, ldc, M, N, K, int(act), _stream())
+    pr, ldr = _residual(residual, check=True)
+    rc = _L.load().fo1_gemm_bf16_wtiled(pa, lda, w_tiled.data_ptr(), _ptr(bias), pr, ldr, po, ldc, M, N, K, int(act), _stream())
     _L.check(rc, "fo1_gemm_bf16_wtiled")
     return out
 
@@ -872,7 +866,7 @@ def pool_qkv_post_partials(part: torch.Tensor, splits: int, bias: Optional[torch
     assert kcache.dim() == 3 and state.dtype == torch.int32 and state.is_contiguous() and state.shape[0] >= P
     assert part.dtype == torch.float32 and part.numel() >= splits * P * (n_q + 2 * n_kv) * head_dim
     pv, ldv, _, _ = _rows(vtcache, "vtcache")
-    rc = _L.load().fo1_pool_qkv_post_partials_bf16(part.data_ptr(), int(splits), bias.data_ptr() if bias is not None else None, p, ld, P, n_q, n_kv, head_dim,
+    rc = _L.load().fo1_pool_qkv_post_partials_bf16(part.data_ptr(), int(splits), _ptr(bias), p, ld, P, n_q, n_kv, head_dim,
                                                    cos_table.data_ptr(), sin_table.data_ptr(), state.data_ptr(), kcache.data_ptr(), kcache.stride(0), pv, ldv,
                                                    _stream())
     _L.check(rc, "fo1_pool_qkv_post_partials_bf16")
@@ -895,7 +889,7 @@ def decode_argmax_accept(logits: Optional[torch.Tensor], first_tokens: Optional[
     else:
         pl, ldl, V = None, 0, 0
         assert first_tokens is not None and first_tokens.dtype == torch.int32 and first_tokens.numel() == B
-    rc = _L.load().fo1_decode_argmax_accept(pl, ldl, V, B, first_tokens.data_ptr() if first_tokens is not None else None, state.data_ptr(),
+    rc = _L.load().fo1_decode_argmax_accept(pl, ldl, V, B, _ptr(first_tokens), state.data_ptr(),
                                             plan.data_ptr(), ids_out.data_ptr(), ids_out.shape[1], stop_ids.data_ptr() if n_stop else None, n_stop,
                                             done.data_ptr(), sc.data_ptr(), _stream())
     _L.check(rc, "fo1_decode_argmax_accept")
@@ -1332,7 +1326,7 @@ def attention_strided(q: torch.Tensor, q_row0: int, k: torch.Tensor, vt: torch.T
         _L.check(lib.fo1_attention_prefix_bf16(*operands, prefix_ranges.data_ptr(), items.shape[0], *shape, float(flops), _stream()), "fo1_attention_prefix_bf16")
     else:
         _L.check(lib.fo1_attention_bf16(*operands, n_items if n_items is not None else items.shape[0], *shape,
-                                        q_row_base.data_ptr() if q_row_base is not None else None, float(flops), _stream()), "fo1_attention_bf16")
+                                        _ptr(q_row_base), float(flops), _stream()), "fo1_attention_bf16")
     return out
 
 
