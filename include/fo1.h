@@ -26,7 +26,7 @@ extern "C" {
 #pragma GCC visibility push(default) /* libfo1hip*.so are built with -fvisibility=hidden: exactly the declarations of this header are exported */
 #endif
 
-#define FO1_ABI_VERSION 9   /* 9: fo1_window_attention_bf16 (DaViT window attention on the q/k/v rows: no V^T copy), fo1_window_attention_map_bf16 / _var (the same on un-partitioned pixel rows: no window partition / reverse), fo1_attention_windows_bf16 (single-tile work lists in a software pipeline; fo1_vit_plan_t.q_block_win 0 selects it); 8: fo1_attention_decode_batch_partials_bf16 + fo1_gemv_attn_combine_bf16 (decode step at <= 2 sequences: the o-projection sums the split-KV partials in its prologue, no combine launch); 7: fo1_vit_block_t gained wqkv_hm / bqkv_hm (optional head-major q/k/v copy: fo1_vit_forward then takes the fused q/k/v epilogue); 6: attention q_block 128 / 256 (32x32-MFMA prefill kernel); fo1_qkv_proj_rope_bf16 (q/k/v projection with RoPE / K append / V^T in the GEMM epilogue); fo1_gemm_bf16_wtiled, fo1_splitk_swiglu_bf16 (measured no-gain forms), fo1_mfma_clock_probe, fo1_gemm_profile_shapes (instruments) moved to fo1_ab.h; 5: split-K planes consumed by fused kernels in the decode pool (fo1_gemm_bf16_partials, fo1_splitk_residual_rmsnorm_bf16, fo1_pool_qkv_post_partials_bf16, fo1_splitk_swiglu_bf16), fo1_gemm_bf16_wtiled, fo1_mfma_clock_probe; 4: decode pool (fo1_pool_qkv_post_bf16; fo1_decode_argmax_accept up to 256 rows): continuous batching of 33..128 sequences; 3: fo1_hfre_opts_t grew out_bf16 / out_bf16_ld; fo1_img_seg + the *_var spatial entry points */
+#define FO1_ABI_VERSION 9   /* 9: (additive: fo1_sample_params_t, fo1_sample_rows_workspace_bytes, fo1_sample_rows_bf16, fo1_decode_sample_accept — the sampled decode head) fo1_window_attention_bf16 (DaViT window attention on the q/k/v rows: no V^T copy), fo1_window_attention_map_bf16 / _var (the same on un-partitioned pixel rows: no window partition / reverse), fo1_attention_windows_bf16 (single-tile work lists in a software pipeline; fo1_vit_plan_t.q_block_win 0 selects it); 8: fo1_attention_decode_batch_partials_bf16 + fo1_gemv_attn_combine_bf16 (decode step at <= 2 sequences: the o-projection sums the split-KV partials in its prologue, no combine launch); 7: fo1_vit_block_t gained wqkv_hm / bqkv_hm (optional head-major q/k/v copy: fo1_vit_forward then takes the fused q/k/v epilogue); 6: attention q_block 128 / 256 (32x32-MFMA prefill kernel); fo1_qkv_proj_rope_bf16 (q/k/v projection with RoPE / K append / V^T in the GEMM epilogue); fo1_gemm_bf16_wtiled, fo1_splitk_swiglu_bf16 (measured no-gain forms), fo1_mfma_clock_probe, fo1_gemm_profile_shapes (instruments) moved to fo1_ab.h; 5: split-K planes consumed by fused kernels in the decode pool (fo1_gemm_bf16_partials, fo1_splitk_residual_rmsnorm_bf16, fo1_pool_qkv_post_partials_bf16, fo1_splitk_swiglu_bf16), fo1_gemm_bf16_wtiled, fo1_mfma_clock_probe; 4: decode pool (fo1_pool_qkv_post_bf16; fo1_decode_argmax_accept up to 256 rows): continuous batching of 33..128 sequences; 3: fo1_hfre_opts_t grew out_bf16 / out_bf16_ld; fo1_img_seg + the *_var spatial entry points */
 #define FO1_OK 0
 #define FO1_ERR_ARG (-1)       /* bad argument / unsupported shape */
 #define FO1_ERR_WORKSPACE (-2) /* workspace too small */
@@ -478,6 +478,33 @@ int fo1_decode_argmax_accept(const void* logits, long long ld_logits, int n_voca
                              int n_stop, int32_t* done, void* scratch, void* stream);
 int fo1_argmax_rows_bf16(const void* logits, long long ld_logits, int n_vocab, int B, int32_t* out /* [B] */, void* scratch,
                          void* stream);
+/* Sampled decode head: temperature / top-k / top-p on the device (HF's TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper ->
+ * softmax -> multinomial, which the reference's generate runs whenever temperature != 0: mm_utils.py:632-650).  For a bf16 logits row l[0..V):
+ * m = the largest finite l_i, w_i = exp((l_i - m) / T) (a non-finite entry has weight 0 and is never kept; a row without a finite entry gives id 0),
+ *   K1 = { i : top_k == 0 or #{ j : l_j > l_i } < top_k },   K = { i in K1 : top_p >= 1 or sum_{j in K1, l_j > l_i} w_j < top_p sum_K1 w },
+ *   id = the smallest i in K, in vocabulary order, with sum_{j in K, j <= i} w_j > u sum_K w (else the last index of K).
+ * Tokens tied at a cut-off are all kept.  u = ((x0 >> 8) + 0.5) 2^-24, x0 = word 0 of Philox4x32-10 with ctr = {counter, stream, 0, 0} and
+ * key = {seed_lo, seed_hi}: the same (row, parameters, seed, stream, counter) gives the same id whatever row b or batch B it sits in.
+ * A temperature that is not a positive finite number (or whose fp32 reciprocal is not one: a denormal) makes the row top_k = 1; top_p outside (0, 1) and top_k <= 0 switch that cut off.
+ * One launch of one workgroup per row, no host read, capturable; B <= 256.  DESIGN.md section 14.
+ *   fo1_sample_rows_bf16       ids only: the head of a prefill (counter NULL = 0) and of the single-sequence loop (counter = device word,
+ *                              element b * counter_stride for row b); u != NULL: explicit draws, device fp32 [B], instead of Philox
+ *   fo1_decode_sample_accept   the sampled form of fo1_decode_argmax_accept: counter = state[b][4], same bookkeeping, same contract for a
+ *                              finished row (nothing recorded, state untouched, plan[1] = 0 whatever its logits hold)
+ * params: DEVICE table, one row per sequence. */
+typedef struct fo1_sample_params {
+    float temperature, top_p;
+    int32_t top_k;                      /* 0 = off */
+    uint32_t seed_lo, seed_hi, stream;  /* Philox key and counter word 1 */
+    uint32_t reserved[2];
+} fo1_sample_params_t;                  /* 32 bytes */
+size_t fo1_sample_rows_workspace_bytes(int n_vocab, int B);
+int fo1_sample_rows_bf16(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params,
+                         const int32_t* counter /* NULL = 0 */, int counter_stride, const float* u /* device [B]; NULL = Philox */,
+                         int32_t* out /* [B] */, void* workspace, size_t workspace_bytes, void* stream);
+int fo1_decode_sample_accept(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params,
+                             int32_t* state, int32_t* plan, int32_t* ids_out, int ids_ld, const int32_t* stop_ids, int n_stop,
+                             int32_t* done, void* workspace, size_t workspace_bytes, void* stream);
 int fo1_kv_relocate(const void* ksrc, void* kdst, long long ks_layer, long long ks_head, long long kd_layer,
                     long long kd_head, const void* vsrc, void* vdst, long long vs_layer, long long vs_row,
                     long long vd_layer, long long vd_row, const int32_t* seqs, int B, int max_len, int n_kv_heads,

@@ -202,23 +202,62 @@ class FO1ForCausalLM:
         from vlm_fo1_amd.llm import BatchDecoder
         return int(max_new_tokens) <= BatchDecoder.IDS_CAP
 
+    @staticmethod
+    def _sampling_plan(kwargs: dict, generation_config: Optional[dict] = None) -> Optional[dict]:
+        """generate()'s sampling arguments -> None (greedy) or dict(temperature, top_p, top_k, seed) for the device sampler.  Sampling is on
+        iff do_sample, as in HF generate: do_sample=False with a temperature decodes greedily.  top_k defaults to the checkpoint's
+        generation_config.json, else 50 (HF's default); seed is the `seed` kwarg, else 63 bits drawn from torch's default CPU generator at
+        call time — torch.manual_seed makes a run reproducible, as under HF.  The generator itself is Philox, not torch's: the ids are not
+        HF's ids, the distribution is."""
+        if not kwargs.get("do_sample"):
+            return None
+        import math
+        gen = generation_config or {}
+        t = kwargs.get("temperature")
+        try:      # any real scalar HF accepts (Python and numpy numbers, 0-d tensors); a bool is not a temperature
+            tv = None if t is None or isinstance(t, bool) else float(t)
+        except (TypeError, ValueError):
+            tv = None
+        # (the device holds it as fp32 and multiplies by its reciprocal: both must be positive finite numbers there)
+        t32 = None if tv is None else torch.tensor(tv, dtype=torch.float32)
+        if tv is None or not (tv > 0 and math.isfinite(float(t32)) and math.isfinite(float(t32.reciprocal()))):
+            raise ValueError(f"do_sample=True needs a positive finite temperature (got {t!r})")
+        top_p = kwargs.get("top_p")
+        top_p = 1.0 if top_p is None else float(top_p)
+        if not 0.0 < top_p <= 1.0:
+            raise ValueError(f"top_p must be in (0, 1] (got {top_p!r})")
+        top_k = kwargs.get("top_k")
+        if top_k is None:
+            top_k = gen.get("top_k")
+        top_k = 50 if top_k is None else int(top_k)
+        if top_k < 0:
+            raise ValueError(f"top_k must be >= 0, 0 switches it off (got {top_k!r})")
+        seed = kwargs.get("seed")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        return dict(temperature=tv, top_p=top_p, top_k=top_k, seed=int(seed) & (2 ** 64 - 1))
+
     def _batch_plan(self, requests_kwargs: List[dict]):
-        """Validation shared by generate_many / generate_many_async -> (engine requests, max_new_tokens, device stop ids), or None when
-        the batch must take the one-by-one host loop (a stop criterion the device rule cannot express, a budget beyond its id buffer)."""
+        """Validation shared by generate_many / generate_many_async -> (engine requests, max_new_tokens, device stop ids, sampling), or None
+        when the batch must take the one-by-one host loop (a stop criterion the device rule cannot express, a budget beyond its id buffer)."""
         k0 = requests_kwargs[0]
-        if k0.get("do_sample") or (k0.get("temperature") not in (0, 0.0, None)):
-            raise NotImplementedError("sampling is not built; every reference caller decodes greedily (temperature=0)")
         stop = self._device_stop_ids(k0.get("stopping_criteria"))
         if stop is None or not self._fits_device_loop(k0.get("max_new_tokens", 512)):
             return None
-        for kw in requests_kwargs[1:]:       # one budget and one stop rule per packed batch: refuse a mixed batch rather than apply the first's
+        sampling = self._sampling_plan(k0, getattr(self.config, "_gen", None))
+        values = None if sampling is None else (sampling["temperature"], sampling["top_p"], sampling["top_k"])
+        for kw in requests_kwargs[1:]:       # one budget, one stop rule and one sampling per packed batch: refuse a mixed batch rather than apply the first's
             if int(kw.get("max_new_tokens", 512)) != int(k0.get("max_new_tokens", 512)) or \
-                    self._device_stop_ids(kw.get("stopping_criteria")) != stop or kw.get("do_sample") or \
-                    (kw.get("temperature") not in (0, 0.0, None)):
-                raise ValueError("generate_many: every request of a batch must share max_new_tokens, stopping criteria and greedy decoding")
+                    self._device_stop_ids(kw.get("stopping_criteria")) != stop:
+                raise ValueError("generate_many: every request of a batch must share max_new_tokens and stopping criteria")
+            other = self._sampling_plan(dict(kw, seed=0), getattr(self.config, "_gen", None))
+            if (None if other is None else (other["temperature"], other["top_p"], other["top_k"])) != values:
+                raise ValueError("generate_many: every request of a batch must share do_sample, temperature, top_p and top_k")
+            if other is not None and kw.get("seed") != k0.get("seed"):      # one seed per batch: request i draws on stream i of it
+                raise ValueError("generate_many: every request of a sampled batch must share seed (request i draws on stream i of the one seed)")
         reqs = [self._request(kw.get("inputs"), kw.get("images"), kw.get("images_aux"), kw.get("image_grid_thws"), kw.get("bbox_list"))
                 for kw in requests_kwargs]
-        return reqs, int(k0.get("max_new_tokens", 512)), stop
+        return reqs, int(k0.get("max_new_tokens", 512)), stop, sampling
 
     @staticmethod
     def _assemble(requests_kwargs, reqs, new) -> List[torch.LongTensor]:
@@ -235,14 +274,18 @@ class FO1ForCausalLM:
         """Greedy generation for several prepare_inputs(...) kwargs sets at once: the images go through ONE packed prefill pass and
         the sequences decode together (weights streamed once per step, stop rule on the device).  Each result is [1, L_in + new]
         exactly as generate() returns it.  max_new_tokens / stopping criteria are taken from the first request (the eval drivers use
-        the same for every item)."""
+        the same for every item).  With do_sample=True the batch shares temperature, top_p, top_k and seed (drawn from torch's generator
+        once when none is given), and request i draws on stream i of that seed — also when the batch has to be decoded one by one."""
         if not requests_kwargs:
             return []
         plan = self._batch_plan(requests_kwargs)
         if plan is None:
-            return [self.generate(**kw) for kw in requests_kwargs]
-        reqs, max_new, stop = plan
-        new = self.engine.generate_batch(reqs, max_new_tokens=max_new, stop_ids=stop, use_graph=self.use_graph)
+            sampling = self._sampling_plan(requests_kwargs[0], getattr(self.config, "_gen", None))
+            if sampling is None:
+                return [self.generate(**kw) for kw in requests_kwargs]
+            return [self.generate(**dict(kw, seed=sampling["seed"]), _stream=i) for i, kw in enumerate(requests_kwargs)]
+        reqs, max_new, stop, sampling = plan
+        new = self.engine.generate_batch(reqs, max_new_tokens=max_new, stop_ids=stop, use_graph=self.use_graph, sampling=sampling)
         return self._assemble(requests_kwargs, reqs, new)
 
     @torch.no_grad()
@@ -262,9 +305,9 @@ class FO1ForCausalLM:
             return _Ready([])
         eng = self.engine
         plan = self._batch_plan(requests_kwargs) if getattr(eng, "_pool_svc", None) is not None else None
-        if plan is None:
+        if plan is None or plan[3] is not None:      # (the decode pool stays greedy: a sampled batch decodes in its own groups, now)
             return _Ready(self.generate_many(requests_kwargs))
-        reqs, max_new, stop = plan
+        reqs, max_new, stop, _ = plan
         handles = [eng.submit_batch(grp, max_new, stop, self.use_graph) for grp in eng.split_passes(reqs)]      # <= 32 requests and <= 64k ViT rows per pass
         model = self
 
@@ -275,22 +318,63 @@ class FO1ForCausalLM:
 
         return _Pending()
 
+    def _generate_sampled_host_loop(self, req, inputs, sampling, n_max, streamer, stopping_criteria, stream=0) -> torch.LongTensor:
+        """Sampled decoding with the tokens handed to the host one by one (a streamer, or stop criteria the device rule cannot express): a
+        BatchDecoder of ONE sequence stepped token by token — the kernels of the device loop, so the same seed draws the same ids whether or
+        not a streamer listens (the single-sequence step of QwenLLM runs other GEMV / attention kernels: its logits differ in last bits, and
+        a draw near an interval's end would then fall on the neighbouring token)."""
+        from vlm_fo1_amd import ops
+        eng, dev = self.engine, self.device
+        eng.prefill_batch([req], use_graph=self.use_graph)
+        hp = eng._last_batch
+        with ops.workspace_scope(eng._ws_owner):
+            tok = ops.sample_rows(eng._last_logits[:1], ops.sample_params([(sampling["temperature"], sampling["top_p"], sampling["top_k"],
+                                                                            sampling["seed"], stream)], dev))
+        dec = eng._decoder()
+        dec.start(hp["seqs"], hp["delta"], tok, n_max, (), sampling=dict(sampling, streams=[stream]))
+        eos = set(self.config.eos_ids())
+        all_ids = inputs.to(dev)
+        if streamer is not None:
+            streamer.put(inputs.cpu())
+        for i in range(n_max):
+            t = tok.to(torch.long).reshape(1, 1)
+            all_ids = torch.cat([all_ids, t.to(all_ids.dtype)], dim=1)
+            if streamer is not None:
+                streamer.put(t.cpu())
+            stop_now = int(t.item()) in eos
+            if not stop_now and stopping_criteria:
+                stop_now = any(bool(c(all_ids, None)) for c in stopping_criteria)
+            if stop_now or i + 1 == n_max:
+                break
+            dec.step(self.use_graph)
+            tok = dec.plan[0, 1:2]          # the id the step accepted (its next embedding-gather entry)
+        if streamer is not None:
+            streamer.end()
+        return all_ids.to(inputs.device)
+
     @torch.no_grad()
     def generate(self, inputs=None, images=None, images_aux=None, image_grid_thws=None, bbox_list=None, do_sample=False,
                  temperature=0.0, max_new_tokens=512, streamer=None, top_p=1.0, use_cache=True, stopping_criteria=None,
-                 pad_token_id=None, **unused) -> torch.LongTensor:
-        """Greedy decoding of one prompt.  Returns [1, L_in + new] like HF generate (the reference slices
-        `output_ids[0, inputs.shape[1]:]`, inference.py:47-48).  Without a streamer and with id-set stop criteria the whole loop
-        runs on the device (BatchDecoder, no per-token host read); otherwise tokens are handed to the host one by one."""
-        if do_sample or (temperature not in (0, 0.0, None)):
-            raise NotImplementedError("sampling is not built; every reference caller decodes greedily (temperature=0)")
+                 pad_token_id=None, top_k=None, seed=None, _stream=0, **unused) -> torch.LongTensor:
+        """Decoding of one prompt: greedy, or with do_sample=True temperature / top-k / top-p sampling on the device (_sampling_plan).
+        Returns [1, L_in + new] like HF generate (the reference slices `output_ids[0, inputs.shape[1]:]`, inference.py:47-48).  Without a
+        streamer and with id-set stop criteria the whole loop runs on the device (BatchDecoder, no per-token host read); otherwise tokens
+        are handed to the host one by one — the picks are made on the device either way, and both loops draw the same ids.  A sampled
+        generation records its ids in the BatchDecoder's buffer: max_new_tokens beyond BatchDecoder.IDS_CAP is a ValueError.  _stream: the
+        Philox stream of the draws (generate_many's one-by-one loop passes the request's index)."""
+        sampling = self._sampling_plan(dict(do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k, seed=seed), getattr(self.config, "_gen", None))
         req = self._request(inputs, images, images_aux, image_grid_thws, bbox_list)
         dev = self.device
         stop = self._device_stop_ids(stopping_criteria) if streamer is None else None
-        if stop is not None and self._fits_device_loop(max_new_tokens):
-            ids = self.engine.generate_batch([req], max_new_tokens=int(max_new_tokens), stop_ids=stop, use_graph=self.use_graph)[0]
+        if sampling is not None and not self._fits_device_loop(max_new_tokens):
+            from vlm_fo1_amd.llm import BatchDecoder
+            raise ValueError(f"do_sample=True draws at most {BatchDecoder.IDS_CAP} tokens per request (max_new_tokens={int(max_new_tokens)})")
+        if stop is not None and (sampling is None or _stream == 0) and self._fits_device_loop(max_new_tokens):
+            ids = self.engine.generate_batch([req], max_new_tokens=int(max_new_tokens), stop_ids=stop, use_graph=self.use_graph, sampling=sampling)[0]
             return torch.cat([inputs.to(dev), torch.tensor([ids], dtype=inputs.dtype, device=dev)], dim=1).to(inputs.device)
         eng = self.engine
+        if sampling is not None:
+            return self._generate_sampled_host_loop(req, inputs, sampling, int(max_new_tokens), streamer, stopping_criteria, int(_stream))
         out = eng.prefill(req["ids"], req["pix"], req["grid"], req["aux"], req["boxes"], use_graph=self.use_graph)
         eng.llm.reserve(eng.llm.kv_len + int(max_new_tokens))
         tok = out["next_token"]

@@ -409,31 +409,6 @@ __global__ __launch_bounds__(256) void argmax_rows_partial_kernel(const uint16_t
     }
 }
 
-// Greedy-search bookkeeping for sequence b given its next token: record it, test the stop rule (EOS / keyword ids, or the
-// max_new_tokens budget: HF stops AFTER appending the stop token), advance the device state, publish the token as the next
-// step's embedding-gather plan entry.  A finished sequence keeps its state frozen: later steps recompute harmlessly in place.
-__device__ __forceinline__ void accept_token(int tok, int* st, int* plan, int* ids_out, int ids_ld, const int* stop_ids, int n_stop, int* done) {
-    plan[0] = 0;
-    // a finished (or never-started) slot keeps stepping with whatever its rows hold: publish a valid embedding row for it — its
-    // logits may be stale or non-finite (the pool skips its attention), and an argmax over NaN rows leaves the index at INT_MAX
-    plan[1] = st[3] ? 0 : tok;
-    if (st[3]) return;
-    const int n = st[4];
-    ids_out[n] = tok;
-    st[4] = n + 1;
-    bool stop = (n + 1 >= st[5]) || (n + 1 >= ids_ld);
-    if (n_stop < 0) {       // per-sequence stop sets (the decode pool admits submissions with different sets): row st[6] of a table [sets][1 + 16] = {n, ids...}
-        stop_ids += st[6] * 17;
-        n_stop = min(stop_ids[0], 16);
-        ++stop_ids;
-    }
-    for (int i = 0; i < n_stop; ++i) stop = stop || (tok == stop_ids[i]);
-    if (stop) {
-        st[3] = 1;
-        atomicAdd(done, 1);
-    }
-}
-
 // stage 2 of the argmax (one workgroup per row) + accept.  first != 0: the tokens come from `tok_in` (the prefill's argmax)
 // instead of the partials, and the state is NOT advanced past the prompt (the first generated token sits at row pos).
 __global__ __launch_bounds__(128) void argmax_rows_accept_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int np,

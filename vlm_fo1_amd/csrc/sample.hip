@@ -1,0 +1,422 @@
+// sample.hip — temperature / top-k / top-p sampling of one token per bf16 logits row, on the device.
+//
+// Reference: HF's TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper -> softmax -> multinomial, which the reference's
+// generate runs whenever temperature != 0 (mm_utils.py:632-650).  Definition (the same distribution; ties at a cut-off are all kept, the
+// generator is Philox4x32-10): with m the largest finite logit and w_i = exp((l_i - m) / T) (0 for a non-finite entry, which is never kept),
+//   K1 = { i : top_k == 0 or #{ j : l_j > l_i } < top_k },  Z1 = sum_K1 w,
+//   K  = { i in K1 : top_p >= 1 or sum_{j in K1, l_j > l_i} w_j < top_p Z1 },  Z2 = sum_K w,
+//   pick = the smallest i in K, in vocabulary order, with sum_{j in K, j <= i} w_j > u Z2 (else the last index of K).
+//
+// One workgroup of 1024 threads (16 waves of 64) per row, everything in LDS, no float atomics, no host read, one launch whatever the data:
+//   1. one pass over the row: the largest finite key, and a count per order-preserving 16-bit key of the non-negative half (LDS integer atomics;
+//      bf16 has 65 536 values, one sign half = 32 768 counters = 128 KB of the 160 KB);
+//   2. key scan from the top key down: thread t owns 32 consecutive keys, mass of a key = count x exp((value - m) / T) (the count is an exact
+//      integer, one exp per key), fixed-order sums (32 keys in a thread, shuffle scan over the 64 threads of a wave, the 16 waves in order) — the
+//      top-k cut-off key falls out of the counts exactly, and the exclusive mass in front of every 32-key range is kept;
+//   3. unless the top-k cut-off already fell in the upper half: the same for the negative half (second pass over the row);
+//   4. the top-p cut-off: the 32-key range whose masses straddle top_p Z1, then the key inside it (from the counts still in LDS, or from a
+//      32-counter pass over the row when they belong to the half that was overwritten);
+//   5. the pick, in vocabulary order: wave w owns a contiguous region, walks it in slices of 512 tokens (8 per lane), sums the kept weights
+//      (8 in a lane in order, shuffle scan over the lanes, slices in order), the 16 regions in order give Z2; the wave whose region straddles
+//      u Z2 walks it again to the slice, the lane and the token.  Prefixes are fp32, the comparison against u Z2 is made in fp64 (u has 25
+//      significant bits: its product with an fp32 Z2 is exact there), so flat rows reproduce floor(u V) bit for bit.
+// top_k == 0 and top_p >= 1 skip 1's counters and 2-4 altogether.
+#include "decode_common.h"
+
+namespace fo1 {
+
+constexpr int SP_NT = 1024;                 // threads per workgroup
+constexpr int SP_NW = SP_NT / 64;           // waves
+constexpr int SP_HALF = 32768;              // keys per sign half
+constexpr int SP_KPT = SP_HALF / SP_NT;     // keys per thread in the key scan (32)
+constexpr int SP_SLICE = 512;               // tokens per wave slice of the pick: 8 per lane
+constexpr int SP_SMEM = SP_HALF * 4 + (2 * SP_NT + 4) * 4;      // counters + the exclusive mass in front of every 32-key range (+ the total)
+
+// bf16 bits -> order-preserving key 0 .. 65535 (larger value = larger key; -0 = +0), -1 for inf / NaN
+__device__ __forceinline__ int sp_key(uint32_t b) {
+    if ((b & 0x7f80u) == 0x7f80u) return -1;
+    if (b == 0x8000u) b = 0;
+    return (int)((b & 0x8000u) ? (b ^ 0xffffu) : (b | 0x8000u));
+}
+__device__ __forceinline__ float sp_val(int key) {
+    const uint32_t b = key >= 0x8000 ? (uint32_t)(key & 0x7fff) : ((uint32_t)key ^ 0xffffu);
+    return __uint_as_float(b << 16);
+}
+// counter slot of a half's key: rotated inside each thread's 32-key range, so the 64 threads of a wave walking their ranges hit 32 banks
+__device__ __forceinline__ int sp_slot(int local) { return (local & ~31) | ((local + (local >> 5)) & 31); }
+
+__device__ __forceinline__ float sp_weight(int key, float m, float inv_t) { return expf((sp_val(key) - m) * inv_t); }
+
+// tokens [i0, i0 + 8) of the row as bf16 bits; past the row's end: NaN (no key).  `vec`: the row is 16-byte aligned.
+__device__ __forceinline__ void sp_load8(const uint16_t* __restrict__ row, int i0, int V, bool vec, uint32_t (&e)[8]) {
+    if (vec && i0 + 8 <= V) {
+        const uint4 v = *reinterpret_cast<const uint4*>(row + i0);
+        e[0] = v.x & 0xffffu; e[1] = v.x >> 16; e[2] = v.y & 0xffffu; e[3] = v.y >> 16;
+        e[4] = v.z & 0xffffu; e[5] = v.z >> 16; e[6] = v.w & 0xffffu; e[7] = v.w >> 16;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) e[j] = i0 + j < V ? (uint32_t)row[i0 + j] : 0x7fc0u;
+    }
+}
+
+// every key of the row, 8 tokens per thread and step (any order: the callers count or take a maximum)
+template <class F>
+__device__ __forceinline__ void sp_for_row(const uint16_t* __restrict__ row, int V, bool vec, F f) {
+    for (int i0 = threadIdx.x * 8; i0 < V; i0 += SP_NT * 8) {
+        uint32_t e[8];
+        sp_load8(row, i0, V, vec, e);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f(sp_key(e[j]));
+    }
+}
+
+// inclusive scan over the 64 lanes of a wave, lane order (Hillis-Steele: a fixed tree, the same bits every run)
+__device__ __forceinline__ float sp_scan_f(float v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float t = __shfl_up(v, o, 64);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+__device__ __forceinline__ int sp_scan_i(int v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(v, o, 64);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+__device__ __forceinline__ int sp_wave_max(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// word 0 of Philox4x32-10 (Salmon et al., SC'11) for ctr = {c0, c1, 0, 0}, key = {k0, k1}
+__device__ __forceinline__ uint32_t sp_philox_x0(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1) {
+    uint32_t c2 = 0, c3 = 0;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return c0;
+}
+
+struct SampleArgs {
+    const uint16_t* logits; long long ld; int V;
+    const fo1_sample_params_t* params;
+    const int* counter; int counter_stride;     // rows form: NULL = 0
+    const float* u;                             // rows form: explicit draws, NULL = Philox
+    int* out;                                   // rows form: [B]
+    int* state; int* plan; int* ids_out; int ids_ld; const int* stop_ids; int n_stop; int* done;     // accept form
+};
+
+// Key scan of the half whose counters sit in `hist` (keys key0 .. key0 + 32767), top key down.  carry_c / carry_m: tokens and mass of the
+// keys above this half.  Writes the exclusive mass in front of every thread's 32-key range to summ[0 .. 1024); at a top-k crossing (the key
+// where the token count reaches top_k) its thread writes the key and the mass down to and including it.  Returns the half's totals.
+__device__ __forceinline__ void sp_key_scan(const uint32_t* hist, int key0, int carry_c, float carry_m, float m, float inv_t, int top_k,
+                                            float* summ, int* s_wc, float* s_wm, int* s_kcut_k, float* s_z1, int& tot_c, float& tot_m) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int top = SP_HALF - 1 - tid * SP_KPT;     // this thread's largest local key
+    int cnt = 0;
+    float mass = 0.f;
+    for (int j = 0; j < SP_KPT; ++j) {
+        const uint32_t c = hist[sp_slot(top - j)];
+        if (c) { cnt += (int)c; mass += (float)c * sp_weight(key0 + top - j, m, inv_t); }
+    }
+    const int ic = sp_scan_i(cnt, lane);
+    const float im = sp_scan_f(mass, lane);
+    float pm = __shfl_up(im, 1, 64);
+    if (lane == 0) pm = 0.f;
+    if (lane == 63) { s_wc[wave] = ic; s_wm[wave] = im; }
+    __syncthreads();
+    int oc = carry_c;
+    float om = carry_m;
+    for (int w = 0; w < wave; ++w) { oc += s_wc[w]; om += s_wm[w]; }
+    const int ex_c = oc + (ic - cnt);
+    const float ex_m = om + pm;
+    summ[tid] = ex_m;
+    tot_c = carry_c;
+    tot_m = carry_m;
+    for (int w = 0; w < SP_NW; ++w) { tot_c += s_wc[w]; tot_m += s_wm[w]; }
+    if (top_k > 0 && ex_c < top_k && ex_c + cnt >= top_k) {      // one thread at most: the counts are exact
+        int n = ex_c;
+        float M = ex_m;
+        for (int j = 0; j < SP_KPT; ++j) {
+            const uint32_t c = hist[sp_slot(top - j)];
+            if (!c) continue;
+            M += (float)c * sp_weight(key0 + top - j, m, inv_t);
+            n += (int)c;
+            if (n >= top_k) { *s_kcut_k = key0 + top - j; *s_z1 = M; break; }
+        }
+    }
+    __syncthreads();
+}
+
+template <bool ACCEPT>
+__global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
+    extern __shared__ __align__(16) unsigned char sp_smem[];
+    uint32_t* hist = reinterpret_cast<uint32_t*>(sp_smem);
+    float* summ = reinterpret_cast<float*>(sp_smem + SP_HALF * 4);      // [2][1024] + total
+    __shared__ int s_wi[SP_NW], s_wl[SP_NW], s_wc[SP_NW];
+    __shared__ float s_wm[SP_NW];
+    __shared__ int s_kcut_k, s_range, s_kcut_p, s_tok;
+    __shared__ float s_z1;
+
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int V = a.V;
+    int* st = ACCEPT ? a.state + b * 8 : nullptr;
+    if (ACCEPT && st[3]) {      // a finished row: nothing recorded, state untouched, a valid embedding row published (whatever its logits hold)
+        if (tid == 0) accept_token(0, st, a.plan + 2 * b, a.ids_out + (long long)b * a.ids_ld, a.ids_ld, a.stop_ids, a.n_stop, a.done);
+        return;
+    }
+    const uint16_t* row = a.logits + (long long)b * a.ld;
+    const bool vec = ((uintptr_t)row & 15) == 0;
+    const fo1_sample_params_t P = a.params[b];
+    float T = P.temperature;
+    int top_k = P.top_k < 0 ? 0 : P.top_k;
+    if (!(T > 0.f) || !(T < INFINITY) || !(1.0f / T < INFINITY)) { T = 1.f; top_k = 1; }      // not a temperature (or one so small that 1 / T overflows): the greedy pick
+    const bool use_p = P.top_p > 0.f && P.top_p < 1.f;               // anything else (NaN included): no nucleus cut
+    const float inv_t = 1.0f / T;
+    const bool cut = top_k > 0 || use_p;
+
+    // 1. largest finite key (+ the non-negative half's counters)
+    if (tid == 0) { s_kcut_k = -1; s_range = 0x7fffffff; s_kcut_p = 0; s_tok = 0; s_z1 = 0.f; }
+    if (cut)
+        for (int i = tid; i < SP_HALF; i += SP_NT) hist[i] = 0;
+    __syncthreads();
+    int kmax = -1;
+    if (cut)
+        sp_for_row(row, V, vec, [&](int k) {
+            kmax = max(kmax, k);
+            if (k >= 0x8000) atomicAdd(&hist[sp_slot(k & 0x7fff)], 1u);
+        });
+    else
+        sp_for_row(row, V, vec, [&](int k) { kmax = max(kmax, k); });
+    kmax = sp_wave_max(kmax);
+    if (lane == 0) s_wi[wave] = kmax;
+    __syncthreads();
+    kmax = s_wi[0];
+    for (int w = 1; w < SP_NW; ++w) kmax = max(kmax, s_wi[w]);
+    int tok = 0;
+    if (kmax >= 0) {      // (a row without a finite entry: id 0)
+        const float m = sp_val(kmax);
+        int kcut = 0;
+        if (cut) {
+            // 2. / 3. key scans, upper half first
+            int tot_c = 0;
+            float tot_m = 0.f;
+            int built = 1;      // the half whose counters are in LDS
+            sp_key_scan(hist, 0x8000, 0, 0.f, m, inv_t, top_k, summ, s_wc, s_wm, &s_kcut_k, &s_z1, tot_c, tot_m);
+            if (s_kcut_k < 0) {      // no top-k cut-off yet: the negative half (uniform: shared value read after the scan's barrier)
+                for (int i = tid; i < SP_HALF; i += SP_NT) hist[i] = 0;
+                __syncthreads();
+                sp_for_row(row, V, vec, [&](int k) {
+                    if (k >= 0 && k < 0x8000) atomicAdd(&hist[sp_slot(k)], 1u);
+                });
+                __syncthreads();
+                sp_key_scan(hist, 0, tot_c, tot_m, m, inv_t, top_k, summ + SP_NT, s_wc, s_wm, &s_kcut_k, &s_z1, tot_c, tot_m);
+                built = 0;
+            } else {
+                summ[SP_NT + tid] = tot_m;      // (never straddled: top_p Z1 < Z1 <= the upper half's mass)
+            }
+            if (tid == 0) summ[2 * SP_NT] = tot_m;
+            __syncthreads();
+            const int kcut_k = max(s_kcut_k, 0);
+            const float z1 = s_kcut_k < 0 ? tot_m : s_z1;
+            // 4. top-p: the first 32-key range (top down) whose end mass reaches top_p Z1, then the key inside it
+            if (use_p) {
+                const float thr = P.top_p * z1;
+                for (int r = tid; r < 2 * SP_NT; r += SP_NT)
+                    if (summ[r + 1] >= thr && !(summ[r] >= thr)) atomicMin(&s_range, r);
+                __syncthreads();
+                const int r = s_range;
+                if (r != 0x7fffffff) {
+                    const int half = r < SP_NT ? 1 : 0;
+                    const int lo = SP_HALF - SP_KPT - (r & (SP_NT - 1)) * SP_KPT;      // the range's lowest local key
+                    const int key_lo = (half ? 0x8000 : 0) + lo;
+                    const bool resident = half == built;
+                    uint32_t* mini = hist;      // 32 counters, plain order
+                    if (!resident) {
+                        if (tid < SP_KPT) mini[tid] = 0;
+                        __syncthreads();
+                        sp_for_row(row, V, vec, [&](int k) {
+                            if (k >= key_lo && k < key_lo + SP_KPT) atomicAdd(&mini[k - key_lo], 1u);
+                        });
+                        __syncthreads();
+                    }
+                    if (tid == 0) {
+                        float M = summ[r];
+                        int kp = key_lo;      // (a range without a token, picked by a last-bit step of the scan: every key above it)
+                        for (int j = SP_KPT - 1; j >= 0; --j) {
+                            const uint32_t c = resident ? hist[sp_slot(lo + j)] : mini[j];
+                            if (!c) continue;
+                            if (!(M < thr)) break;
+                            kp = key_lo + j;
+                            M += (float)c * sp_weight(key_lo + j, m, inv_t);
+                        }
+                        s_kcut_p = kp;
+                    }
+                    __syncthreads();
+                }
+            }
+            kcut = max(kcut_k, s_kcut_p);
+        }
+
+        // 5. the pick.  u: explicit, or word 0 of Philox(counter, stream; seed)
+        double u;
+        if (!ACCEPT && a.u) {
+            u = (double)a.u[b];
+        } else {
+            const uint32_t ctr = ACCEPT ? (uint32_t)st[4] : (a.counter ? (uint32_t)a.counter[(long long)b * a.counter_stride] : 0u);
+            u = ((double)(sp_philox_x0(ctr, P.stream, P.seed_lo, P.seed_hi) >> 8) + 0.5) * (1.0 / 16777216.0);
+        }
+        const int region = (((V + SP_NW - 1) / SP_NW) + SP_SLICE - 1) / SP_SLICE * SP_SLICE;      // tokens per wave: whole slices
+        const int r0 = wave * region;
+        float run = 0.f;
+        int lastm = -1;
+        for (int s0 = r0; s0 < r0 + region && s0 < V; s0 += SP_SLICE) {
+            uint32_t e[8];
+            const int i0 = s0 + lane * 8;
+            sp_load8(row, i0, V, vec, e);
+            float s = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int k = sp_key(e[j]);
+                if (k >= kcut) { s += sp_weight(k, m, inv_t); lastm = i0 + j; }
+            }
+            run += __shfl(sp_scan_f(s, lane), 63, 64);
+        }
+        lastm = sp_wave_max(lastm);
+        if (lane == 0) { s_wm[wave] = run; s_wl[wave] = lastm; }
+        __syncthreads();
+        float z2 = 0.f;
+        for (int w = 0; w < SP_NW; ++w) z2 += s_wm[w];
+        const double target = u * (double)z2;
+        int wsel = -1;
+        float before = 0.f, acc = 0.f;
+        int last_all = -1;
+        for (int w = 0; w < SP_NW; ++w) {
+            last_all = max(last_all, s_wl[w]);
+            if (wsel < 0) {
+                before = acc;
+                acc += s_wm[w];
+                if ((double)acc > target) wsel = w;
+            }
+        }
+        if (wsel < 0) {
+            if (tid == 0) s_tok = last_all;      // u Z2 rounds to Z2 (u = 1 - 2^-25 given as fp32): the last index of K
+        } else if (wave == wsel) {
+            int pick = -1;
+            run = 0.f;
+            for (int s0 = r0; s0 < r0 + region && s0 < V && pick < 0; s0 += SP_SLICE) {
+                uint32_t e[8];
+                const int i0 = s0 + lane * 8;
+                sp_load8(row, i0, V, vec, e);
+                float wj[8], s = 0.f;
+                int lm = -1;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int k = sp_key(e[j]);
+                    wj[j] = k >= kcut ? sp_weight(k, m, inv_t) : -1.f;
+                    if (k >= kcut) { s += wj[j]; lm = i0 + j; }
+                }
+                const float q = sp_scan_f(s, lane);
+                const float total = __shfl(q, 63, 64);
+                if ((double)(before + (run + total)) > target) {      // this slice (the same sums as above: the last slice ends at `acc`)
+                    float qp = __shfl_up(q, 1, 64);
+                    if (lane == 0) qp = 0.f;
+                    const unsigned long long hit = __ballot((double)(before + (run + q)) > target);
+                    if (hit == 0) {
+                        pick = sp_wave_max(lm);      // (a rounding gap between the scan's last lane and `total`: none by construction)
+                    } else {
+                        const int l0 = __ffsll((long long)hit) - 1;
+                        int mine = -1;
+                        if (lane == l0) {
+                            float r8 = 0.f;
+#pragma unroll
+                            for (int j = 0; j < 8; ++j) {
+                                if (wj[j] < 0.f || mine >= 0) continue;
+                                r8 += wj[j];
+                                if ((double)(before + (run + (qp + r8))) > target) mine = i0 + j;
+                            }
+                            if (mine < 0) mine = lm;      // the lane's sum and the scan's value differ in the last bit: its last kept token
+                        }
+                        pick = __shfl(mine, l0, 64);
+                    }
+                }
+                run += total;
+            }
+            if (pick < 0) pick = s_wl[wave];
+            if (lane == 0) s_tok = pick;
+        }
+        __syncthreads();
+        tok = s_tok;
+    }
+    if (tid == 0) {
+        if (ACCEPT) {
+            // the step that produced this token consumed row `pos`: the NEXT fed token goes one row further (as the greedy head does)
+            st[0] += 1; st[1] += 1;
+            accept_token(tok, st, a.plan + 2 * b, a.ids_out + (long long)b * a.ids_ld, a.ids_ld, a.stop_ids, a.n_stop, a.done);
+        } else {
+            a.out[b] = tok;
+        }
+    }
+}
+
+constexpr size_t SP_WORKSPACE = 256;      // the one-workgroup-per-row kernel keeps everything in LDS; the argument stays for a split form
+
+template <bool ACCEPT>
+static int launch_sample(const SampleArgs& a, int B, hipStream_t st) {
+    FO1_DYNAMIC_LDS_ONCE(SP_SMEM, sample_rows_kernel<ACCEPT>);
+    FO1_LAUNCH(ACCEPT ? "sample_accept" : "sample_rows", (double)B * a.V * 2.0, sample_rows_kernel<ACCEPT>, dim3(B), dim3(SP_NT), SP_SMEM, st, a);
+    return FO1_OK;
+}
+
+static int check_sample(const char* who, const void* logits, long long ld, int V, int B, const void* params, const void* ws, size_t ws_bytes) {
+    FO1_CHECK_ARG(logits && params, "%s: NULL operand", who);
+    FO1_CHECK_ARG(B >= 1 && B <= 256, "%s: B=%d (1..256)", who, B);
+    FO1_CHECK_ARG(V >= 1 && ld >= V, "%s: n_vocab=%d ld_logits=%lld", who, V, ld);
+    if (!ws || ws_bytes < SP_WORKSPACE) return set_err(FO1_ERR_WORKSPACE, "%s: workspace %zu bytes < %zu", who, ws ? ws_bytes : (size_t)0, SP_WORKSPACE);
+    return FO1_OK;
+}
+
+}  // namespace fo1
+
+extern "C" {
+
+size_t fo1_sample_rows_workspace_bytes(int n_vocab, int B) { return n_vocab >= 1 && B >= 1 && B <= 256 ? fo1::SP_WORKSPACE : 0; }
+
+// One sampled id per logits row (see the head of this file).  counter: device int32, element b * counter_stride (NULL = 0);
+// u: device fp32 [B] explicit draws instead of Philox (tests).
+int fo1_sample_rows_bf16(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params, const int32_t* counter,
+                         int counter_stride, const float* u, int32_t* out, void* workspace, size_t workspace_bytes, void* stream) {
+    using namespace fo1;
+    if (int rc = check_sample("sample_rows", logits, ld_logits, n_vocab, B, params, workspace, workspace_bytes)) return rc;
+    FO1_CHECK_ARG(out != nullptr, "sample_rows: NULL out");
+    SampleArgs a{};
+    a.logits = (const uint16_t*)logits; a.ld = ld_logits; a.V = n_vocab; a.params = params; a.counter = (const int*)counter;
+    a.counter_stride = counter_stride; a.u = u; a.out = (int*)out;
+    return launch_sample<false>(a, B, (hipStream_t)stream);
+}
+
+// The sampled head of a decode step: pick (counter = state[b][4], the number of tokens generated so far) + the bookkeeping of
+// fo1_decode_argmax_accept (accept_token).  A finished row records nothing, leaves its state alone and publishes plan[1] = 0.
+int fo1_decode_sample_accept(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params, int32_t* state,
+                             int32_t* plan, int32_t* ids_out, int ids_ld, const int32_t* stop_ids, int n_stop, int32_t* done, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    using namespace fo1;
+    if (int rc = check_sample("decode_sample_accept", logits, ld_logits, n_vocab, B, params, workspace, workspace_bytes)) return rc;
+    FO1_CHECK_ARG(state && plan && ids_out && done && ids_ld > 0 && n_stop >= -1 && (n_stop == 0 || stop_ids), "decode_sample_accept: bad arguments");
+    SampleArgs a{};
+    a.logits = (const uint16_t*)logits; a.ld = ld_logits; a.V = n_vocab; a.params = params;
+    a.state = (int*)state; a.plan = (int*)plan; a.ids_out = (int*)ids_out; a.ids_ld = ids_ld; a.stop_ids = (const int*)stop_ids; a.n_stop = n_stop;
+    a.done = (int*)done;
+    return launch_sample<true>(a, B, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -180,6 +180,8 @@ class QwenLLM:
         self.dplan = torch.zeros(1, 2, dtype=torch.int32, device=self.dev)     # gather plan of the one new token: (0, token id)
         self._dgraph = None
         self._dstate_keep = None
+        self._sampled = False       # sampled head of the single-sequence step (set_sampling)
+        self._sbuf = None
         self.rope_epoch = 0         # bumped whenever the rope tables are re-allocated (grow_rope): step graphs key on it
         self._rope_retired = []     # replaced tables, never freed (shared by the replicas: see grow_rope)
         self._ws_owner = ops.new_owner(self)   # scratch-buffer key (ops.workspace_scope); FO1Engine overrides it with its own token
@@ -240,6 +242,7 @@ class QwenLLM:
         r.dplan = torch.zeros_like(self.dplan)
         r._dgraph = None
         r._dstate_keep = None
+        r._sampled, r._sbuf = False, None
         r._item_cache = {}
         r._ws_owner = ops.new_owner(r)
         # the zero-fills above ran on the creating thread's current stream; the replica is used from another thread / stream
@@ -578,20 +581,55 @@ class QwenLLM:
             a = ops.gemv(x, w["wgu"], act=ops.ACT_SWIGLU16, norm_weight=w["ln2"], norm_eps=c.rms_norm_eps)
             x = ops.gemv(a, w["wdown"], residual=x)
         logits = ops.gemv(x, self.lm_head, norm_weight=self.norm, norm_eps=c.rms_norm_eps)
-        ops.argmax(logits[0], out=self.dplan.view(-1)[1:2])    # next token id lands in the gather plan of the next step
+        if self._sampled:
+            # sampled head: the draw's counter is the sampler's own device word (sstate[4], one more per step), the id lands in the plan
+            sb = self._sbuf
+            ops.decode_sample_accept(logits, sb["params"], sb["state"], self.dplan, sb["ids"], None, sb["done"])
+        else:
+            ops.argmax(logits[0], out=self.dplan.view(-1)[1:2])    # next token id lands in the gather plan of the next step
         ops.decode_advance(self.dstate)
         return logits
+
+    SAMPLE_IDS = 1 << 16      # tokens one sampled single-sequence generation may draw (the sampler's bookkeeping records them)
+
+    def set_sampling(self, sampling: Optional[dict], stream: int = 0, counter: int = 1) -> None:
+        """Head of decode_step / decode_step_graph: None = greedy; dict(temperature, top_p, top_k, seed) = the device sampler
+        (fo1_decode_sample_accept at B = 1) drawing Philox(counter, stream; seed), the counter starting at `counter` (the first token of a
+        request is drawn from the prefill's logits with counter 0) and advancing on the device with every step."""
+        if sampling is None:
+            self._sampled = False
+            return
+        if self._sbuf is None:
+            with torch.inference_mode(False):      # persistent, updated in place (see BatchDecoder.__init__)
+                z = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=self.dev)      # noqa: E731
+                self._sbuf = dict(params=z(1, 8), state=z(1, 8), ids=z(1, self.SAMPLE_IDS), done=z(1))
+        params = ops.sample_params([(sampling["temperature"], sampling["top_p"], sampling["top_k"], sampling["seed"], stream)])
+        state = torch.tensor([[0, 0, 0, 0, int(counter), 1 << 30, 0, 0]], dtype=torch.int32)
+        self._sbuf["params"].copy_(params, non_blocking=True)
+        self._sbuf["state"].copy_(state, non_blocking=True)
+        self._sbuf["keep"] = (params, state)
+        self._sample_left = self.SAMPLE_IDS - 1 - int(counter)
+        self._sampled = True
+
+    def _sample_room(self):
+        if self._sampled:
+            if self._sample_left <= 0:
+                raise ValueError(f"a sampled generation draws at most {self.SAMPLE_IDS - 1} tokens")
+            self._sample_left -= 1
 
     def decode_step_graph(self, token_id: Optional[torch.Tensor] = None):
         """Greedy step via one replayed hipGraph.  `token_id` (device int32 [1]) seeds the plan on the first step
         after a prefill; later steps reuse the id the previous replay wrote.  Returns (logits, next id tensor)."""
         self._check_room()
+        self._sample_room()
         if token_id is not None:
             self.dplan.view(-1)[1:2].copy_(token_id.to(torch.int32).view(1), non_blocking=True)
-        if self._dgraph is None:
+        if self._dgraph is None or self._sampled not in self._dgraph:      # one graph per head (greedy / sampled); the sampling values are data
             with ops.graph_lock.capture(), torch.inference_mode(False):   # exclusive (see ops._CaptureLock); mode: see FO1Engine._capture
                 snap = self.dstate.clone()
                 plan = self.dplan.clone()
+                sb = [self._sbuf[k] for k in ("state", "ids", "done")] if self._sampled else []
+                sb_snap = [t.clone() for t in sb]
                 s = torch.cuda.Stream()
                 s.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(s):
@@ -600,13 +638,16 @@ class QwenLLM:
                 torch.cuda.synchronize()
                 self.dstate.copy_(snap)
                 self.dplan.copy_(plan)
+                for t, t0 in zip(sb, sb_snap):
+                    t.copy_(t0)
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):   # RCCL watchdog threads may touch the runtime meanwhile
                     logits = self._decode_device()
                 self.dstate.copy_(snap)            # the capture itself does not execute, but keep the state exact
                 self.dplan.copy_(plan)
-                self._dgraph = (g, logits)
-        g, logits = self._dgraph
+                self._dgraph = dict(self._dgraph or {})
+                self._dgraph[self._sampled] = (g, logits)
+        g, logits = self._dgraph[self._sampled]
         with ops.graph_lock.replay():
             g.replay()
         self.kv_len += 1
@@ -617,6 +658,7 @@ class QwenLLM:
         bit-identical): token_id int32 [1] on device -> (last hidden placeholder, logits [1, V], next id tensor).
         Position = cache_position + rope_delta on all three axes (reference :1848-1860)."""
         self._check_room()
+        self._sample_room()
         self.dplan.view(-1)[1:2].copy_(token_id.to(torch.int32).view(1), non_blocking=True)
         self.sync_decode_state()
         logits = self._decode_device()
@@ -663,6 +705,8 @@ class BatchDecoder:
             self.done = torch.zeros(1, dtype=torch.int32, device=dev)
             self.stop = torch.zeros(self.MAX_STOP, dtype=torch.int32, device=dev)
             self.reloc = torch.zeros(2 * B, 4, dtype=torch.int32, device=dev)      # (a shared-prefix sequence moves in two pieces)
+            self.sparams = torch.zeros(B, 8, dtype=torch.int32, device=dev)        # fo1_sample_params_t per sequence (sampled head)
+        self.sampled = False
         self.n_stop = 0
         self.dk = self.dvt = None
         self.rows = 0
@@ -688,9 +732,12 @@ class BatchDecoder:
             self.llm.grow_rope(slot)
             self._graphs = {}
 
-    def start(self, seqs, deltas, first_tokens: torch.Tensor, max_new_tokens: int, stop_ids: Sequence[int] = ()):
+    def start(self, seqs, deltas, first_tokens: torch.Tensor, max_new_tokens: int, stop_ids: Sequence[int] = (), sampling: Optional[dict] = None):
         """seqs: [(cache row offset, L, ...)] of the packed prefill that just ran on llm.kcache / llm.vtcache; first_tokens: device
-        int32 [B] (the prefill's greedy picks).  Moves every sequence to its own slot and accepts the first tokens on the device."""
+        int32 [B] (the prefill's picks: greedy, or drawn with counter 0).  Moves every sequence to its own slot and accepts the first tokens
+        on the device.  sampling: None = greedy steps; dict(temperature, top_p, top_k, seed[, streams]) = every step ends in the device
+        sampler (fo1_decode_sample_accept), sequence b drawing Philox(tokens generated so far, streams[b]; seed) — streams defaults to
+        0 .. B - 1, the sequence's index in its request list."""
         llm = self.llm
         B = len(seqs)
         if B > self.MAX_BATCH:
@@ -723,6 +770,13 @@ class BatchDecoder:
         self.state[:B].copy_(state, non_blocking=True)
         self.stop.copy_(stop, non_blocking=True)
         self._keep = [reloc, state, stop]                 # sources of the async uploads stay alive
+        self.sampled = sampling is not None
+        if self.sampled:
+            streams = list(sampling.get("streams") or range(B))
+            assert len(streams) == B
+            sp = ops.sample_params([(sampling["temperature"], sampling["top_p"], sampling["top_k"], sampling["seed"], s) for s in streams])
+            self.sparams[:B].copy_(sp, non_blocking=True)
+            self._keep.append(sp)
         self.done.zero_()
         with ops.workspace_scope(self._ws_owner):
             ops.kv_relocate(llm.kcache, self.dk, llm.vtcache, self.dvt, self.reloc[:nr], max(L for _, L, *_ in seqs))
@@ -745,7 +799,7 @@ class BatchDecoder:
         scale = 1.0 / math.sqrt(HD)
         st = self.state[:B]
         from . import stage_abi
-        if stage_abi.enabled():      # the same launches, sequenced by fo1_llm_decode_step (csrc/stages.hip)
+        if stage_abi.enabled() and not self.sampled:      # the same launches, sequenced by fo1_llm_decode_step (csrc/stages.hip: the greedy head)
             with ops.workspace_scope(self._ws_owner):
                 return stage_abi.llm_stage(llm).decode_step(self)
         with ops.workspace_scope(self._ws_owner):
@@ -764,7 +818,10 @@ class BatchDecoder:
                 a = ops.gemv_batch(x, w["wgu"], mode=ops.GB_SWIGLU, norm_weight=w["ln2"], norm_eps=c.rms_norm_eps)
                 x = ops.gemv_batch(a, w["wdown"], residual=x)
             logits = ops.gemv_batch(x, llm.lm_head, norm_weight=llm.norm, norm_eps=c.rms_norm_eps)
-            ops.decode_argmax_accept(logits, None, st, self.plan[:B], self.ids[:B], self.stop[:self.n_stop], self.done)
+            if self.sampled:
+                ops.decode_sample_accept(logits, self.sparams[:B], st, self.plan[:B], self.ids[:B], self.stop[:self.n_stop], self.done)
+            else:
+                ops.decode_argmax_accept(logits, None, st, self.plan[:B], self.ids[:B], self.stop[:self.n_stop], self.done)
             return logits
 
     def step(self, use_graph: bool = True):
@@ -775,7 +832,7 @@ class BatchDecoder:
             return out
         # the rope tables' identity is part of the key: QwenLLM.reserve() on a larger later batch or a sibling decoder may re-allocate
         # them (grow_rope) while this decoder's graphs survive — a replay would read the freed table
-        key = (self.B, self.slot, self.n_stop, self.kv_bucket(), self.llm.rope_epoch, self.llm.rope_cos.data_ptr())
+        key = (self.B, self.slot, self.n_stop, self.kv_bucket(), self.llm.rope_epoch, self.llm.rope_cos.data_ptr(), self.sampled)
         ent = self._graphs.get(key)
         if ent is None:
             with ops.graph_lock.capture(), torch.inference_mode(False):

@@ -515,18 +515,23 @@ class FO1Engine:
                              cache_rows=(o, L)))
         self._last_batch = hp
         self._last_next_tokens = res["next_tokens"]
+        self._last_logits = res["logits"]
         if B == 1:                                   # the single request sits at cache position 0: decode can continue in place
             self.llm.kv_len = hp["seqs"][0][1]
             self.llm.rope_delta = hp["delta"][0]
         return outs
 
-    def generate_batch(self, requests: Sequence[dict], max_new_tokens: int = 512, stop_ids: Sequence[int] = (), use_graph: bool = True) -> List[List[int]]:
-        """Greedy generation for a batch of requests: one packed prefill, then the batched decode loop (vlm_fo1_amd.llm.BatchDecoder):
+    def generate_batch(self, requests: Sequence[dict], max_new_tokens: int = 512, stop_ids: Sequence[int] = (), use_graph: bool = True,
+                       sampling: Optional[dict] = None) -> List[List[int]]:
+        """Generation for a batch of requests: one packed prefill, then the batched decode loop (vlm_fo1_amd.llm.BatchDecoder):
         weights streamed once per step for all sequences, stop rule and bookkeeping on the device.  Returns the new ids per request
-        (stop token included, like HF generate)."""
+        (stop token included, like HF generate).  sampling: None = greedy; dict(temperature, top_p, top_k, seed) = temperature / top-k / top-p
+        sampling on the device (csrc/sample.hip): request i draws Philox(tokens generated so far, i; seed) — the first token from the prefill's
+        logits with counter 0.  Sampled batches take the BatchDecoder groups; the decode pool stays greedy."""
         from .llm import BatchDecoder, run_decoders
         out: List[List[int]] = []
-        if getattr(self, "_pool_svc", None) is not None:
+        base = 0      # index of the pass's first request in the request list (the sampler's stream ids)
+        if sampling is None and getattr(self, "_pool_svc", None) is not None:
             # decode pool: every pass's sequences join the shared pool; this call's later passes prefill while its earlier ones decode
             handles = [self.submit_batch(grp, max_new_tokens, stop_ids, use_graph) for grp in self.split_passes(requests)]
             for h in handles:
@@ -537,10 +542,19 @@ class FO1Engine:
             hp = self._last_batch
             first = self._last_next_tokens
             n = len(grp)
+
+            def samp(a, b, b0=base):      # the sampling of sequences a .. b of this pass
+                return None if sampling is None else dict(sampling, streams=list(range(b0 + a, b0 + b)))
+            if sampling is not None:
+                with ops.workspace_scope(self._ws_owner):
+                    s0 = samp(0, n)
+                    table = ops.sample_params([(s0["temperature"], s0["top_p"], s0["top_k"], s0["seed"], s) for s in s0["streams"]], self.dev)
+                    first = ops.sample_rows(self._last_logits[:n], table)
+            base += n
             gmax = min(BatchDecoder.MAX_BATCH, self.DECODE_MAX_GROUP)
             if n <= gmax:
                 dec = self._decoder()
-                dec.start(hp["seqs"], hp["delta"], first[:n], max_new_tokens, stop_ids)
+                dec.start(hp["seqs"], hp["delta"], first[:n], max_new_tokens, stop_ids, sampling=samp(0, n))
                 out += dec.run(max_new_tokens, use_graph=use_graph)
                 continue
             # more sequences than one decode group carries (32 = two 16-column MFMA groups per weight fragment; DECODE_MAX_GROUP = 16
@@ -552,7 +566,7 @@ class FO1Engine:
                 dec = self._decoder()
                 for j in range(k):
                     a, b = cuts[j], cuts[j + 1]
-                    dec.start(hp["seqs"][a:b], hp["delta"][a:b], first[a:b], max_new_tokens, stop_ids)
+                    dec.start(hp["seqs"][a:b], hp["delta"][a:b], first[a:b], max_new_tokens, stop_ids, sampling=samp(a, b))
                     out += dec.run(max_new_tokens, use_graph=use_graph)
                 continue
             decs, streams = self._decoders(k)
@@ -561,7 +575,7 @@ class FO1Engine:
                 a, b = cuts[j], cuts[j + 1]
                 streams[j].wait_stream(cur)                       # the prefill (and its first tokens) are on the caller's stream
                 with torch.cuda.stream(streams[j]):
-                    decs[j].start(hp["seqs"][a:b], hp["delta"][a:b], first[a:b], max_new_tokens, stop_ids)
+                    decs[j].start(hp["seqs"][a:b], hp["delta"][a:b], first[a:b], max_new_tokens, stop_ids, sampling=samp(a, b))
             for ids in run_decoders(decs[:k], streams[:k], max_new_tokens, use_graph=use_graph):
                 out += ids
             for j in range(k):

@@ -895,6 +895,59 @@ def decode_argmax_accept(logits: Optional[torch.Tensor], first_tokens: Optional[
     _L.check(rc, "fo1_decode_argmax_accept")
 
 
+def sample_params(rows: Sequence[Sequence], device=None) -> torch.Tensor:
+    """The fo1_sample_params_t table (int32 [B, 8] = 32 bytes per sequence) from rows of (temperature, top_p, top_k, seed, stream): seed is an
+    integer of up to 64 bits (the Philox key), stream the sequence's index in its request list.  On `device` when given, else a host tensor."""
+    import struct
+    buf = b"".join(struct.pack("<ffiIIIII", float(t), float(p), int(k), int(seed) & 0xffffffff, (int(seed) >> 32) & 0xffffffff,
+                               int(stream) & 0xffffffff, 0, 0) for t, p, k, seed, stream in rows)
+    tab = torch.frombuffer(bytearray(buf), dtype=torch.int32).view(-1, 8)
+    return tab if device is None else tab.to(device)
+
+
+def _sample_operands(logits: torch.Tensor, params: torch.Tensor):
+    _chk(logits, "logits")
+    pl, ld, B, V = _rows(logits, "logits")
+    _chk(params, "params", torch.int32)
+    assert params.is_contiguous() and params.dim() == 2 and params.shape[1] == 8 and params.shape[0] >= B
+    n = _L.load().fo1_sample_rows_workspace_bytes(V, B)
+    ws = _workspace("sample_rows", logits.device, max(int(n), 1))
+    return (pl, ld, V, B, params.data_ptr()), (ws.data_ptr(), ws.numel(), _stream())
+
+
+def sample_rows(logits: torch.Tensor, params: torch.Tensor, counter: Optional[torch.Tensor] = None, counter_stride: int = 1,
+                u: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 [B]: one sampled id per row of logits [B, V] bf16 (fo1_sample_rows_bf16): temperature / top-k / top-p per row from `params`
+    (sample_params), draw = Philox(counter, stream; seed) with counter = counter[b * counter_stride] (device int32; None = 0), or the explicit
+    u [B] fp32."""
+    head, tail = _sample_operands(logits, params)
+    B = head[3]
+    if out is None:
+        out = torch.empty(B, dtype=torch.int32, device=logits.device)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == B
+    if counter is not None:
+        assert counter.dtype == torch.int32 and counter.is_cuda and counter.numel() > (B - 1) * counter_stride
+    if u is not None:
+        assert u.dtype == torch.float32 and u.is_cuda and u.is_contiguous() and u.numel() == B
+    rc = _L.load().fo1_sample_rows_bf16(*head, _ptr(counter), int(counter_stride), _ptr(u), out.data_ptr(), *tail)
+    _L.check(rc, "fo1_sample_rows_bf16")
+    return out
+
+
+def decode_sample_accept(logits: torch.Tensor, params: torch.Tensor, state: torch.Tensor, plan: torch.Tensor, ids_out: torch.Tensor,
+                         stop_ids: Optional[torch.Tensor], done: torch.Tensor) -> None:
+    """The sampled head of a decode step (fo1_decode_sample_accept): decode_argmax_accept's bookkeeping around a draw whose counter is
+    state[b, 4]."""
+    B = state.shape[0]
+    assert state.dtype == plan.dtype == ids_out.dtype == done.dtype == torch.int32 and ids_out.is_contiguous() and plan.is_contiguous()
+    assert state.is_contiguous() and logits.shape[0] == B
+    head, tail = _sample_operands(logits, params)
+    n_stop = int(stop_ids.numel()) if stop_ids is not None else 0
+    rc = _L.load().fo1_decode_sample_accept(*head, state.data_ptr(), plan.data_ptr(), ids_out.data_ptr(), ids_out.shape[1],
+                                            stop_ids.data_ptr() if n_stop else None, n_stop, done.data_ptr(), *tail)
+    _L.check(rc, "fo1_decode_sample_accept")
+
+
 def kv_relocate(ksrc: torch.Tensor, kdst: torch.Tensor, vsrc: torch.Tensor, vdst: torch.Tensor, seqs: torch.Tensor, max_len: int) -> None:
     """k*: [layers, n_kv, rows, 128]; v*: [layers, n_kv*128, rows]; seqs int32 [B, 4] = (src0, dst0, len, 0) on the device."""
     for t in (ksrc, kdst, vsrc, vdst):
