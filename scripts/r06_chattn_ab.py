@@ -36,8 +36,8 @@ def main():
         res, outs = {}, {}
         for impl in (0, 1):
             L.fo1_channel_attention_set_impl(impl)
-            outs[impl] = ops.channel_attention(qkv, C, batch=B)
-            res["mfma" if impl else "fma"] = round(timed(lambda: ops.channel_attention(qkv, C, batch=B), flush), 2)
+            outs[impl] = ops.channel_attention(qkv, C, ops.Grid(N, 1, B))
+            res["mfma" if impl else "fma"] = round(timed(lambda: ops.channel_attention(qkv, C, ops.Grid(N, 1, B)), flush), 2)
         d = (outs[0].float() - outs[1].float()).abs()
         res["fraction_equal"] = round(float((d == 0).float().mean()), 5)
         res["max_abs_diff"] = float(d.max())

@@ -41,8 +41,8 @@ def main():
         outs = {}
         for form in (0, 2):
             L.fo1_dwconv_ln_set_form(form)
-            outs[form] = ops.dwconv3x3_res_ln(x, w9, b, H, W, lw, lb, 1e-5, batch=B)
-            res["run" if form else "pixel"] = round(timed(lambda: ops.dwconv3x3_res_ln(x, w9, b, H, W, lw, lb, 1e-5, batch=B), flush), 2)
+            outs[form] = ops.dwconv3x3_res_ln(x, w9, b, ops.Grid(H, W, B), lw, lb, 1e-5)
+            res["run" if form else "pixel"] = round(timed(lambda: ops.dwconv3x3_res_ln(x, w9, b, ops.Grid(H, W, B), lw, lb, 1e-5), flush), 2)
         res["bitwise"] = bool(torch.equal(outs[0][0], outs[2][0]) and torch.equal(outs[0][1], outs[2][1]))
         res["algorithmic_MB"] = round(3 * B * H * W * C * 2 / 1e6, 1)
         res["run_GBps"] = round(res["algorithmic_MB"] / res["run"] * 1e3 / 1e3, 1)

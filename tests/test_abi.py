@@ -282,6 +282,207 @@ def test_decode_linear_argument_errors():
     rejected(combine(ldc=1024), b"gemv_attn_combine", b"residual / output layout")
 
 
+def test_vision_argument_errors():
+    """The spatial operators of the towers, uniform and ragged (`_var`) entry of each, and the window-attention map pair: every bad call is
+    rejected before any HIP call (fake 4096-aligned integers stand for device pointers) with the documented return code, the entry's own
+    prefix (the `_var` entries say `_var`) and a word of the cause.  Where several checks could fire, the order is pinned."""
+    lib = L.load()
+    X, W9, B, Y, LW, LB, Hh, SG, WS = [4096 * (i + 1) for i in range(9)]
+    TABLE = b"need a device fo1_img_seg table"
+
+    def rejected(rc, prefix, *words, want=-1):
+        msg = lib.fo1_last_error()
+        assert rc == want, (rc, msg)
+        assert msg.startswith(prefix + b":") and all(w in msg for w in words), msg
+
+    def segs_checks(call, prefix):      # every ragged entry: NULL table, no image, more images than a grid dimension holds
+        rejected(call(segs=None), prefix, TABLE)
+        rejected(call(n=0), prefix, TABLE, b"1..65535")
+        rejected(call(n=65536), prefix, TABLE, b"1..65535")
+
+    def dwln(**kw):     # fo1_dwconv3x3_ln_bf16
+        a = dict(x=X, w=W9, b=B, y=Y, lw=LW, lb=LB, h=Hh, H=5, W=7, C=64, batch=2)
+        a.update(kw)
+        return lib.fo1_dwconv3x3_ln_bf16(a["x"], a["w"], a["b"], a["y"], a["lw"], a["lb"], 1e-5, a["h"], a["H"], a["W"], a["C"], a["batch"], None)
+
+    for missing in ("x", "w", "b", "y", "lw", "lb", "h"):
+        rejected(dwln(**{missing: None}), b"dwconv_ln", b"NULL")
+    rejected(dwln(y=X), b"dwconv_ln", b"aliased")
+    rejected(dwln(h=X), b"dwconv_ln", b"aliased")
+    rejected(dwln(h=Y), b"dwconv_ln", b"aliased")
+    rejected(dwln(x=None, C=12), b"dwconv_ln", b"NULL")           # operands before shape
+    rejected(dwln(C=12), b"dwconv_ln", b"bad shape", b"5x7x12")
+    rejected(dwln(C=2056), b"dwconv_ln", b"bad shape", b"C <= 2048")
+    rejected(dwln(C=0), b"dwconv_ln", b"bad shape")
+    rejected(dwln(H=0), b"dwconv_ln", b"bad shape")
+    rejected(dwln(W=0), b"dwconv_ln", b"bad shape")
+    rejected(dwln(batch=0), b"dwconv_ln", b"bad shape")
+    rejected(dwln(H=1 << 20, W=1 << 14, C=256, batch=1), b"dwconv_ln", b"too many pixel runs")
+
+    def dwln_var(**kw):     # fo1_dwconv3x3_ln_var_bf16
+        a = dict(x=X, w=W9, b=B, y=Y, lw=LW, lb=LB, h=Hh, segs=SG, n=2, max=35, total=60, C=64)
+        a.update(kw)
+        return lib.fo1_dwconv3x3_ln_var_bf16(a["x"], a["w"], a["b"], a["y"], a["lw"], a["lb"], 1e-5, a["h"], a["segs"], a["n"], a["max"], a["total"],
+                                             a["C"], None)
+
+    for missing in ("x", "w", "b", "y", "lw", "lb", "h"):
+        rejected(dwln_var(**{missing: None}), b"dwconv_ln_var", b"NULL")
+    rejected(dwln_var(y=X), b"dwconv_ln_var", b"aliased")
+    rejected(dwln_var(h=X), b"dwconv_ln_var", b"aliased")
+    rejected(dwln_var(h=Y), b"dwconv_ln_var", b"aliased")
+    rejected(dwln_var(x=None, segs=None), b"dwconv_ln_var", b"NULL operand")      # operands, then the table, then the shape
+    segs_checks(dwln_var, b"dwconv_ln_var")
+    rejected(dwln_var(segs=None, C=12), b"dwconv_ln_var", TABLE)
+    rejected(dwln_var(C=12), b"dwconv_ln_var", b"bad shape")
+    rejected(dwln_var(C=2056), b"dwconv_ln_var", b"bad shape", b"C <= 2048")
+    rejected(dwln_var(max=0), b"dwconv_ln_var", b"bad shape")
+
+    def im2col(**kw):       # fo1_im2col_bf16: a 3 x 3 / stride 2 / pad 1 embed of a 9 x 11 x 16 map
+        a = dict(x=X, col=Y, H=9, W=11, C=16, KH=3, KW=3, stride=2, pad=1, ld=144, batch=2)
+        a.update(kw)
+        return lib.fo1_im2col_bf16(a["x"], a["col"], a["H"], a["W"], a["C"], a["KH"], a["KW"], a["stride"], a["pad"], a["ld"], a["batch"], None)
+
+    rejected(im2col(x=None), b"im2col", b"NULL")
+    rejected(im2col(col=None), b"im2col", b"NULL")
+    rejected(im2col(x=None, C=12), b"im2col", b"NULL")
+    rejected(im2col(C=12), b"im2col", b"bad parameters")
+    rejected(im2col(stride=0), b"im2col", b"bad parameters")
+    rejected(im2col(KH=0), b"im2col", b"bad parameters")
+    rejected(im2col(pad=-1), b"im2col", b"bad parameters")
+    rejected(im2col(C=12, ld=8), b"im2col", b"bad parameters")          # parameters before the output shape
+    rejected(im2col(ld=136), b"im2col", b"bad output shape")            # smaller than KH * KW * C
+    rejected(im2col(ld=148), b"im2col", b"bad output shape")            # not a multiple of 8
+    rejected(im2col(batch=0), b"im2col", b"bad output shape")
+    rejected(im2col(H=0, pad=0), b"im2col", b"bad output shape")
+
+    def im2col_var(**kw):   # fo1_im2col_var_bf16
+        a = dict(x=X, col=Y, segs=SG, n=2, max=30, total=50, C=16, KH=3, KW=3, stride=2, pad=1, ld=144)
+        a.update(kw)
+        return lib.fo1_im2col_var_bf16(a["x"], a["col"], a["segs"], a["n"], a["max"], a["total"], a["C"], a["KH"], a["KW"], a["stride"], a["pad"],
+                                       a["ld"], None)
+
+    rejected(im2col_var(x=None), b"im2col_var", b"NULL")
+    rejected(im2col_var(col=None), b"im2col_var", b"NULL")
+    rejected(im2col_var(x=None, segs=None), b"im2col_var", b"NULL")
+    segs_checks(im2col_var, b"im2col_var")
+    rejected(im2col_var(segs=None, C=12), b"im2col_var", TABLE)
+    rejected(im2col_var(C=12), b"im2col_var", b"bad parameters")
+    rejected(im2col_var(stride=0), b"im2col_var", b"bad parameters")
+    rejected(im2col_var(ld=136), b"im2col_var", b"bad parameters")
+    rejected(im2col_var(ld=148), b"im2col_var", b"bad parameters")
+    rejected(im2col_var(max=0), b"im2col_var", b"bad parameters")
+
+    def one_check(entry, var_entry, prefix, operands, extent):
+        """The copy-like operators make one check of the operands and the shape, the ragged twin then the table.
+        -> (uniform(**kw), ragged(**kw)); `extent` = the uniform entry's trailing shape arguments after (H, W)."""
+        def uni(**kw):
+            a = dict(p=list(operands), H=13, W=17, C=64, ws=12, batch=2)
+            a.update(kw)
+            return getattr(lib, entry)(*a["p"], a["H"], a["W"], *[a[k] for k in extent], a["batch"], None)
+
+        def var(**kw):
+            a = dict(p=list(operands), segs=SG, n=2, max=288, total=576, C=64, ws=12)
+            a.update(kw)
+            return getattr(lib, var_entry)(*a["p"], a["segs"], a["n"], a["max"], a["total"], *[a[k] for k in extent], None)
+
+        for i in range(len(operands)):
+            nulled = [None if j == i else p for j, p in enumerate(operands)]
+            rejected(uni(p=nulled), prefix, b"bad arguments")
+            rejected(var(p=nulled), prefix + b"_var", b"bad arguments")
+        rejected(uni(C=12), prefix, b"bad arguments")
+        rejected(uni(batch=0), prefix, b"bad arguments")
+        rejected(var(C=12), prefix + b"_var", b"bad arguments")
+        rejected(var(max=0), prefix + b"_var", b"bad arguments")
+        rejected(var(C=12, segs=None), prefix + b"_var", b"bad arguments")      # operands and shape before the table
+        segs_checks(var, prefix + b"_var")
+        return uni, var
+
+    uni, var = one_check("fo1_window_partition_bf16", "fo1_window_partition_var_bf16", b"window_partition", (X, Y), ("C", "ws"))
+    rejected(uni(ws=0), b"window_partition", b"bad arguments")
+    rejected(var(ws=0), b"window_partition_var", b"bad arguments")
+    uni, var = one_check("fo1_window_reverse_add_bf16", "fo1_window_reverse_add_var_bf16", b"window_reverse", (X, B, Y), ("C", "ws"))
+    rejected(uni(ws=0), b"window_reverse", b"bad arguments")
+    rejected(var(ws=0), b"window_reverse_var", b"bad arguments")
+    uni, var = one_check("fo1_pixel_shuffle2_bf16", "fo1_pixel_shuffle2_var_bf16", b"pixel_shuffle", (X, Y), ("C",))
+    rejected(uni(C=0), b"pixel_shuffle", b"bad arguments")
+    rejected(var(C=0), b"pixel_shuffle_var", b"bad arguments")
+    uni, var = one_check("fo1_maxpool2_bf16", "fo1_maxpool2_var_bf16", b"maxpool", (X, Y), ("C",))
+    rejected(uni(H=1), b"maxpool", b"bad arguments")
+    rejected(uni(W=1), b"maxpool", b"bad arguments")
+
+    def chattn(**kw):       # fo1_channel_attention_bf16: 2 images of 221 tokens, 64 channels
+        a = dict(qkv=X, ld=192, N=221, C=64, out=Y, ldo=64, batch=2, ws=WS, bytes=lib.fo1_channel_attention_workspace_bytes(221, 64, 2))
+        a.update(kw)
+        return lib.fo1_channel_attention_bf16(a["qkv"], a["ld"], a["N"], a["C"], a["out"], a["ldo"], a["batch"], a["ws"], a["bytes"], None)
+
+    def chattn_var(**kw):   # fo1_channel_attention_var_bf16: 2 images, the larger of 300 tokens
+        a = dict(qkv=X, ld=192, segs=SG, n=2, max=300, total=521, C=64, out=Y, ldo=64, ws=WS,
+                 bytes=lib.fo1_channel_attention_var_workspace_bytes(300, 64, 2))
+        a.update(kw)
+        return lib.fo1_channel_attention_var_bf16(a["qkv"], a["ld"], a["segs"], a["n"], a["max"], a["total"], a["C"], a["out"], a["ldo"], a["ws"],
+                                                  a["bytes"], None)
+
+    assert lib.fo1_channel_attention_workspace_bytes(221, 64, 2) > 0
+    assert lib.fo1_channel_attention_var_workspace_bytes(300, 64, 2) == lib.fo1_channel_attention_workspace_bytes(300, 64, 2)
+    for call, prefix, size in ((chattn, b"channel_attention", "N"), (chattn_var, b"channel_attention_var", "max")):
+        for missing in ("qkv", "out", "ws"):
+            rejected(call(**{missing: None}), prefix, b"NULL")
+        rejected(call(qkv=None, C=48), prefix, b"NULL")
+        rejected(call(C=48, ld=144, ldo=48), prefix, b"bad shape")          # C % 32
+        rejected(call(C=0), prefix, b"bad shape")
+        rejected(call(**{size: 0}), prefix, b"bad shape")
+        rejected(call(ld=184), prefix, b"bad shape")                        # ld < 3 C
+        rejected(call(ld=196), prefix, b"bad shape")                        # ld % 8
+        rejected(call(ldo=56), prefix, b"bad shape")                        # ldo < C
+        rejected(call(C=48, ldo=68), prefix, b"bad shape")                  # the shape before the alignment
+        rejected(call(ldo=68), prefix, b"16-byte aligned", b"ldo % 8")
+        rejected(call(qkv=X + 8), prefix, b"16-byte aligned")
+        rejected(call(out=Y + 8), prefix, b"16-byte aligned")
+        rejected(call(ldo=68, bytes=16), prefix, b"16-byte aligned")        # the alignment before the workspace
+        rejected(call(bytes=0), prefix, b"workspace too small", want=-2)
+    rejected(chattn(bytes=lib.fo1_channel_attention_workspace_bytes(221, 64, 2) - 1), b"channel_attention", b"workspace too small", want=-2)
+    rejected(chattn_var(bytes=lib.fo1_channel_attention_var_workspace_bytes(300, 64, 2) - 1), b"channel_attention_var", b"workspace too small",
+             want=-2)
+    rejected(chattn(batch=0), b"channel_attention", b"bad shape", b"N=221 C=64")
+    rejected(chattn_var(qkv=None, segs=None), b"channel_attention_var", b"NULL")     # operands, the table, the shape
+    segs_checks(chattn_var, b"channel_attention_var")
+    rejected(chattn_var(segs=None, C=48), b"channel_attention_var", TABLE)
+
+    def wmap(**kw):         # fo1_window_attention_map_bf16: 2 images of 13 x 17 pixels, 2 heads
+        a = dict(qkv=X, ld=192, C=64, heads=2, window=12, H=13, W=17, batch=2, pad=B, out=Y, ldo=64)
+        a.update(kw)
+        return lib.fo1_window_attention_map_bf16(a["qkv"], a["ld"], a["C"], a["heads"], a["window"], a["H"], a["W"], a["batch"], a["pad"], a["out"],
+                                                 a["ldo"], 0.1, None)
+
+    def wmap_var(**kw):     # fo1_window_attention_map_var_bf16
+        a = dict(qkv=X, ld=192, C=64, heads=2, window=12, segs=SG, n=2, max=4, total=521, pad=B, out=Y, ldo=64)
+        a.update(kw)
+        return lib.fo1_window_attention_map_var_bf16(a["qkv"], a["ld"], a["C"], a["heads"], a["window"], a["segs"], a["n"], a["max"], a["total"],
+                                                     a["pad"], a["out"], a["ldo"], 0.1, None)
+
+    rejected(wmap(H=0), b"window_attention_map", b"bad shape 0x17 x2")
+    rejected(wmap(batch=0), b"window_attention_map", b"bad shape")
+    rejected(wmap(batch=0, qkv=None), b"window_attention_map", b"bad shape")         # the entry's own shape check comes first
+    rejected(wmap_var(segs=None), b"window_attention_map_var", b"fo1_img_seg table")
+    rejected(wmap_var(segs=None, qkv=None), b"window_attention_map_var", b"fo1_img_seg table")
+    assert wmap_var(n=0, qkv=None) == 0 and wmap_var(total=0, qkv=None) == 0         # nothing to do is not an error
+    rejected(wmap_var(n=65536), b"window_attention_map_var", b"65536 images")
+    rejected(wmap_var(max=0), b"window_attention_map_var", b"0 windows per image")
+    for call, prefix in ((wmap, b"window_attention_map"), (wmap_var, b"window_attention_map_var")):
+        for missing in ("qkv", "out", "pad"):
+            rejected(call(**{missing: None}), prefix, b"NULL")
+        rejected(call(qkv=None, heads=3), prefix, b"NULL")
+        rejected(call(heads=3), prefix, b"head dim 32", b"C=64, 3 heads")
+        rejected(call(heads=3, window=7), prefix, b"head dim 32")
+        rejected(call(window=7), prefix, b"12 x 12 windows", b"got 7")
+        rejected(call(ld=184), prefix, b"16-byte aligned")
+        rejected(call(ldo=68), prefix, b"16-byte aligned")
+        rejected(call(pad=B + 8), prefix, b"16-byte aligned")
+    rejected(wmap(batch=70000), b"window_attention_map", b"70000 images")
+    rejected(wmap(H=4000, W=4000), b"window_attention_map", b"windows per image")
+    rejected(wmap(H=12 * 255, W=12 * 255, batch=600, ldo=1 << 16), b"window_attention_map", b"2 GiB")
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(L, "_lib", None)
     monkeypatch.setattr(L, "LIB_PATH", str(tmp_path / "nope.so"))

@@ -829,7 +829,7 @@ def test_conv3x3_implicit_gemm_equals_im2col_gemm(ab_library, cfg):
     L.load().fo1_gemm_set_variant(0, 5)
     try:
         y = ops.layernorm(x, nw, nb, 1e-6)
-        col, Ho, Wo = ops.im2col(y, H, W, 3, 3, s, 1, batch=B)
+        col, (Ho, Wo) = ops.im2col(y, ops.Grid(H, W, B), 3, 3, s, 1), ops.Grid(H, W).conv_out(3, 3, s, 1).sizes[0]
         ref = ops.gemm(col, w, b, act=cfg["act"])
         pl = ops.conv3x3_plan(((H, W),) * B, s, Cin, "cuda")
         assert pl.out_hw == [(Ho, Wo)] * B and pl.M_out == B * Ho * Wo

@@ -95,7 +95,7 @@ def _launch(d, dev, items=None, prefix="case", q_block=None, plain_base=False):
         ops.window_attention(dev["qkv"], c.Hq * c.HD, c.Hq, c.segs[0], scale, out=out)
     elif r == "davit_map":
         (H, W), B = c.sizes[0], len(c.sizes)
-        ops.window_attention_map(dev["qkv"], c.Hq * c.HD, c.Hq, C.MAP_WS, H, W, B, dev["pad_row"], scale, out=out)
+        ops.window_attention_map(dev["qkv"], c.Hq * c.HD, c.Hq, C.MAP_WS, ops.Grid(H, W, B), dev["pad_row"], scale, out=out)
     elif r == "davit_var":
         ws, rows, r0, w0 = C.MAP_WS, [], 0, 0
         for H, W in c.sizes:
@@ -104,7 +104,7 @@ def _launch(d, dev, items=None, prefix="case", q_block=None, plain_base=False):
             r0 += H * W
             w0 += nwy * nwx * ws * ws
         sg = ops.ImgSegs(rows, "cuda", max(H * W for H, W in c.sizes), r0, max(a[4] * a[5] * ws * ws for a in rows), w0)
-        ops.window_attention_map_var(dev["qkv"], c.Hq * c.HD, c.Hq, ws, sg, dev["pad_row"], scale, out=out)
+        ops.window_attention_map(dev["qkv"], c.Hq * c.HD, c.Hq, ws, sg, dev["pad_row"], scale, out=out)
     else:
         raise ValueError(r)
     torch.cuda.synchronize()

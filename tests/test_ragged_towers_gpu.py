@@ -98,7 +98,7 @@ def test_fpn_ragged_pass_equals_one_image_passes(towers):
 def test_ragged_passes_take_the_implicit_convolution_bitwise(towers, monkeypatch):
     """Ragged packs big enough for the 256 x 256 GEMM kernel (unpinned): DaViT's pre-norm ConvEmbed of stage 1 and the 3x3 output convolutions of
     the finer FPN levels run as implicit GEMMs over ONE zero-framed buffer with a common row pitch (ops.Conv3x3Plan over images of different
-    sizes) — the same bits as layernorm + im2col_var + gemm (FO1_CONV_IMPLICIT=0)."""
+    sizes) — the same bits as layernorm + im2col + gemm (FO1_CONV_IMPLICIT=0)."""
     from vlm_fo1_amd import ops
     davit, fpn = towers
     g = torch.Generator().manual_seed(8)
@@ -124,9 +124,9 @@ def test_ragged_passes_take_the_implicit_convolution_bitwise(towers, monkeypatch
     monkeypatch.setenv("FO1_CONV_IMPLICIT", "0")
     m0, f0 = run()
     for l, (a, b) in enumerate(zip(m1, m0)):
-        assert torch.equal(a, b), f"DaViT level {l}: implicit vs im2col_var"
+        assert torch.equal(a, b), f"DaViT level {l}: implicit vs im2col"
     for l, (a, b) in enumerate(zip(f1, f0)):
-        assert torch.equal(a, b), f"FPN level {l}: implicit vs im2col_var"
+        assert torch.equal(a, b), f"FPN level {l}: implicit vs im2col"
 
 
 def test_ragged_spatial_kernels_against_torch_references():
@@ -146,7 +146,7 @@ def test_ragged_spatial_kernels_against_torch_references():
     o0 = [0, out_sizes[0][0] * out_sizes[0][1]]
     sg = ops.ImgSegs([(r, h, w, o, a, b) for r, (h, w), o, (a, b) in zip(row0, sizes, o0, out_sizes)], "cuda", max(npx), sum(npx),
                      max(a * b for a, b in out_sizes), sum(a * b for a, b in out_sizes))
-    y = ops.maxpool2_var(x, sg).cpu()
+    y = ops.maxpool2(x, sg).cpu()
     for b, (h, w) in enumerate(sizes):
         ref = F.max_pool2d(xs[b].float().reshape(h, w, C).permute(2, 0, 1)[None], 2)[0].permute(1, 2, 0).reshape(-1, C).bfloat16()
         a, bb = out_sizes[b]
@@ -154,7 +154,66 @@ def test_ragged_spatial_kernels_against_torch_references():
     # channel attention: per-image softmax((q N^-1/2)^T k) per 32-channel group
     qkv = torch.randn(sum(npx), 3 * C, generator=g).bfloat16()
     tok = ops.ImgSegs([(r, n) for r, n in zip(row0, npx)], "cuda", max(npx), sum(npx), max(npx), sum(npx))
-    got = ops.channel_attention_var(qkv.cuda(), C, tok).cpu()
+    got = ops.channel_attention(qkv.cuda(), C, tok).cpu()
     for b, n in enumerate(npx):
-        one = ops.channel_attention(qkv[row0[b]:row0[b] + n].cuda().contiguous(), C).cpu()
+        one = ops.channel_attention(qkv[row0[b]:row0[b] + n].cuda().contiguous(), C, ops.Grid(n, 1)).cpu()
         assert torch.equal(got[row0[b]:row0[b] + n], one), f"channel attention image {b}: table path differs from the one-image call"
+
+
+# {pass: {profile row: (launches, total_work)}} of the four passes below, recorded before the uniform and the ragged spatial-operator paths were
+# folded into one (a host-code refactor: same kernels, same launches, same work figures)
+TOWER_PROFILE_ROWS = {
+    'davit_uniform': {
+        'nchw_to_hwc8': (1, 168960.0), 'im2col': (4, 2817024.0), 'gemm_bt_ring<64,64,3>': (78, 14270070784.0), 'layernorm': (4, 1376256.0),
+        'dwconv3x3_ln': (48, 11993088.0), 'win_attn32': (12, 2123366400.0), 'chattn_gram': (12, 1998848.0), 'chattn_softmax': (12, 3080192.0),
+        'chattn_apply': (12, 1998848.0), 'gemm_bt_ring<64,128,3>': (22, 5972688896.0), 'gemm_splitk_reduce': (22, 21495808.0)
+    },
+    'davit_ragged': {
+        'nchw_to_hwc8': (2, 581702.0), 'im2col': (4, 10430560.0), 'gemm_bt_ring<64,64,3>': (78, 53944680448.0), 'layernorm': (4, 4937728.0),
+        'dwconv3x3_ln': (48, 44648448.0), 'win_attn32': (12, 4544004096.0), 'chattn_gram': (12, 7441408.0), 'chattn_softmax': (12, 3538944.0),
+        'chattn_apply': (12, 7441408.0), 'gemm_bt_ring<64,128,3>': (22, 23187161088.0), 'gemm_splitk_reduce': (22, 82411520.0)
+    },
+    'fpn_uniform': {
+        'gemm_bt_ring<64,64,3>': (7, 933232640.0), 'pixel_shuffle2': (3, 1310720.0), 'layernorm': (9, 3112960.0), 'bias_act': (1, 327680.0),
+        'im2col': (4, 12533760.0), 'gemm_bt_ring<64,128,3>': (4, 3208642560.0), 'gemm_splitk_reduce': (4, 11141120.0), 'maxpool2': (1, 102400.0)
+    },
+    'fpn_ragged': {
+        'gemm_bt_ring<64,64,3>': (7, 3266314240.0), 'pixel_shuffle2': (3, 4587520.0), 'layernorm': (9, 10895360.0), 'bias_act': (1, 1146880.0),
+        'im2col': (4, 43868160.0), 'gemm_bt_ring<64,128,3>': (4, 11230248960.0), 'gemm_splitk_reduce': (4, 20643840.0), 'maxpool2': (1, 358400.0)
+    },
+}
+
+
+def test_tower_profile_rows(towers):
+    """One launcher and one front end per spatial operator serve both batch kinds: each tower pass must launch exactly the rows it launched
+    when the uniform and the ragged paths were written out twice — same row names, same launch counts, and the same `total_work` (host
+    arithmetic on the shapes, compared exactly).  The shapes are the smallest that run every spatial operator, pad the 12 x 12 windows and
+    include odd extents."""
+    from vlm_fo1_amd import lib as L
+    davit, fpn = towers
+    g = torch.Generator().manual_seed(6)
+
+    def img(H, W):
+        return torch.randn(3, H, W, generator=g).bfloat16().cuda()
+
+    def tokens(n):
+        return torch.randn(n, 1280, generator=g).bfloat16().cuda()
+
+    passes = {
+        "davit_uniform": lambda a=torch.stack([img(60, 64), img(60, 64)]): davit.forward(a),
+        "davit_ragged": lambda a=[img(60, 64), img(97, 233)]: davit.forward_ragged(a),
+        "fpn_uniform": lambda a=tokens(2 * 16): fpn.forward(a, 4, 4, batch=2),
+        "fpn_ragged": lambda a=tokens(16 + 96): fpn.forward_ragged(a, [(4, 4), (6, 16)], [0, 16]),
+    }
+    got = {}
+    for name, run in passes.items():
+        L.profile_rows()
+        L.profile(True)
+        try:
+            run()
+            torch.cuda.synchronize()
+            got[name] = {r["name"]: (r["calls"], r["total_work"]) for r in L.profile_rows()}
+        finally:
+            L.profile(False)
+        print(f'        "{name}": {got[name]!r},')
+    assert got == TOWER_PROFILE_ROWS

@@ -39,7 +39,7 @@ def test_im2col_conv_equivalence(H, W, C, K, s, p):
     w = (torch.randn(Co, C, K, K) * 0.05).to(BF)
     b = (torch.randn(Co) * 0.1).to(BF)
     ref = rb(F.conv2d(x.float(), w.float(), b.float(), stride=s, padding=p))
-    col, Ho, Wo = ops.im2col(tm(x).cuda(), H, W, K, K, s, p)
+    col, (Ho, Wo) = ops.im2col(tm(x).cuda(), ops.Grid(H, W), K, K, s, p), ops.Grid(H, W).conv_out(K, K, s, p).sizes[0]
     assert (Ho, Wo) == tuple(ref.shape[2:])
     unf = F.unfold(x.float(), K, padding=p, stride=s)[0].t().reshape(Ho * Wo, C, K * K).permute(0, 2, 1).reshape(Ho * Wo, -1)
     assert torch.equal(col.float().cpu(), unf), "im2col is a pure copy: must be bit exact"
@@ -58,12 +58,12 @@ def test_window_partition_reverse():
         xp = F.pad(x, (0, 0, 0, pad_r, 0, pad_b))
         Hp, Wp = xp.shape[:2]
         ref = xp.view(Hp // ws, ws, Wp // ws, ws, C).permute(0, 2, 1, 3, 4).reshape(-1, C)
-        got = ops.window_partition(x.reshape(-1, C).cuda(), H, W, ws)
+        got = ops.window_partition(x.reshape(-1, C).cuda(), ops.Grid(H, W), ws)
         assert torch.equal(got.cpu(), ref)
         yw = torch.randn_like(ref)
         y = yw.view(Hp // ws, Wp // ws, ws, ws, C).permute(0, 2, 1, 3, 4).reshape(Hp, Wp, C)[:H, :W]
         refo = rb(x.float() + y.float())
-        goto = ops.window_reverse_add(yw.cuda(), x.reshape(-1, C).cuda(), H, W, ws)
+        goto = ops.window_reverse_add(yw.cuda(), x.reshape(-1, C).cuda(), ops.Grid(H, W), ws)
         assert torch.equal(goto.float().cpu(), refo.reshape(-1, C))
 
 
@@ -77,7 +77,7 @@ def test_channel_attention():
         q, k, v = x[0], x[1], x[2]
         att = rb(rb(rb(q * (float(N) ** -0.5)).transpose(-1, -2) @ k).softmax(-1))
         ref = rb((att @ v.transpose(-1, -2)).transpose(-1, -2)).transpose(1, 2).reshape(N, C)
-        got = ops.channel_attention(qkv.cuda(), C)
+        got = ops.channel_attention(qkv.cuda(), C, ops.Grid(N, 1))
         err = (got.float().cpu() - ref).abs().max()
         assert err < 0.03 * ref.abs().max() + 2e-3, f"channel attention N={N} C={C}: max err {err:.4g} (scale {ref.abs().max():.3g})"
 
@@ -90,11 +90,11 @@ def test_channel_attention_matrix_core_kernels_against_the_fp32_fma_kernels():
     torch.manual_seed(33)
     for (B, N, C) in [(1, 1200, 1024), (3, 300, 256), (2, 37, 64), (1, 513, 32), (2, 4800, 512)]:
         qkv = torch.randn(B * N, 3 * C).to(BF).cuda()
-        new = ops.channel_attention(qkv, C, batch=B)
+        new = ops.channel_attention(qkv, C, ops.Grid(N, 1, B))
         with _L.use_ab():
             _L.load().fo1_channel_attention_set_impl(0)
             try:
-                old = ops.channel_attention(qkv, C, batch=B)
+                old = ops.channel_attention(qkv, C, ops.Grid(N, 1, B))
             finally:
                 _L.load().fo1_channel_attention_set_impl(1)
         d = (new.float() - old.float()).abs()
@@ -102,7 +102,7 @@ def test_channel_attention_matrix_core_kernels_against_the_fp32_fma_kernels():
         assert frac_equal > 0.97, f"B={B} N={N} C={C}: only {frac_equal:.4f} of the elements equal"
         assert float(d.max()) <= 0.02 * float(old.float().abs().max()) + 1e-3, f"B={B} N={N} C={C}: max diff {float(d.max()):.4g}"
         # run to run: bitwise
-        assert torch.equal(new, ops.channel_attention(qkv, C, batch=B))
+        assert torch.equal(new, ops.channel_attention(qkv, C, ops.Grid(N, 1, B)))
 
 
 def test_window_attention_on_the_qkv_rows_against_a_torch_reference_and_the_general_kernel():
@@ -153,12 +153,12 @@ def test_window_attention_on_unpartitioned_rows_equals_partition_attention_rever
                 wq, bq = (torch.randn(3 * C, C) * 0.08).to(BF).cuda(), (torch.randn(3 * C) * 0.3).to(BF).cuda()
                 wp, bp = (torch.randn(C, C) * 0.08).to(BF).cuda(), (torch.randn(C) * 0.1).to(BF).cuda()
                 # partition form
-                hw = ops.window_partition(h, H, W, ws, batch=B)
+                hw = ops.window_partition(h, ops.Grid(H, W, B), ws)
                 att_w = ops.window_attention(ops.gemm(hw, wq, bq), C, heads, ws * ws, 32 ** -0.5)
-                ref = ops.window_reverse_add(ops.gemm(att_w, wp, bp), x, H, W, ws, batch=B)
+                ref = ops.window_reverse_add(ops.gemm(att_w, wp, bp), x, ops.Grid(H, W, B), ws)
                 # map form
                 qkv = ops.gemm(h, wq, bq)
-                att = ops.window_attention_map(qkv, C, heads, ws, H, W, B, bq, 32 ** -0.5)
+                att = ops.window_attention_map(qkv, C, heads, ws, ops.Grid(H, W, B), bq, 32 ** -0.5)
                 got = ops.gemm(att, wp, bp, residual=x)
                 assert torch.equal(got, ref), f"{B} x {H}x{W} x {heads} heads: {int((got != ref).sum())} elements differ"
             # ragged: three images of different sizes in one call == the per-image calls
@@ -173,10 +173,10 @@ def test_window_attention_on_unpartitioned_rows_equals_partition_attention_rever
                 r0 += a * b
                 w0 += nwy * nwx * ws * ws
             sg = ops.ImgSegs(rows, "cuda", max(a * b for a, b in sizes), r0, max(r[4] * r[5] * ws * ws for r in rows), w0)
-            got = ops.window_attention_map_var(torch.cat(qs, 0), C, heads, ws, sg, bq, 32 ** -0.5)
+            got = ops.window_attention_map(torch.cat(qs, 0), C, heads, ws, sg, bq, 32 ** -0.5)
             r = 0
             for (a, b), q in zip(sizes, qs):
-                one = ops.window_attention_map(q, C, heads, ws, a, b, 1, bq, 32 ** -0.5)
+                one = ops.window_attention_map(q, C, heads, ws, ops.Grid(a, b), bq, 32 ** -0.5)
                 assert torch.equal(got[r:r + a * b], one), f"ragged image {a}x{b}"
                 r += a * b
         finally:
@@ -196,13 +196,13 @@ def test_pixel_shuffle_maxpool_nchw_gather():
     a = torch.zeros(H * W, Cip, dtype=BF); a[:, :Ci] = tm(x)
     wgp = torch.zeros(4 * Co, Cip, dtype=BF); wgp[:, :Ci] = wg
     y4 = ops.gemm(a.cuda(), wgp.cuda(), b.repeat(4).cuda())
-    got = ops.pixel_shuffle2(y4, H, W, Co)
+    got = ops.pixel_shuffle2(y4, ops.Grid(H, W), Co)
     err = (got.float().cpu() - tm(ref)).abs().max()
     assert err < 2e-2, f"convT via gemm+pixel_shuffle: {err:.4g}"
     # maxpool
     xm = torch.randn(1, 32, 7, 10).to(BF)
     refm = F.max_pool2d(xm.float(), 2, 2)
-    gotm = ops.maxpool2(tm(xm).cuda(), 7, 10)
+    gotm = ops.maxpool2(tm(xm).cuda(), ops.Grid(7, 10))
     assert torch.equal(gotm.float().cpu(), tm(refm))
     # nchw -> hwc8
     img = torch.randn(3, 11, 13)
@@ -230,7 +230,7 @@ def test_dwconv_layernorm_fused_equals_separate_kernels():
         lb = (0.1 * torch.randn(C)).to(torch.bfloat16).cuda()
         y_ref = ops.dwconv3x3_res(x, w9, b, H, W)
         h_ref = ops.layernorm(y_ref, lw, lb, 1e-5)
-        y, h = ops.dwconv3x3_res_ln(x, w9, b, H, W, lw, lb, 1e-5)
+        y, h = ops.dwconv3x3_res_ln(x, w9, b, ops.Grid(H, W), lw, lb, 1e-5)
         assert torch.equal(y, y_ref), f"{H}x{W}x{C}: conv output differs"
         assert torch.equal(h, h_ref), f"{H}x{W}x{C}: LayerNorm output differs ({int((h != h_ref).sum())} elements)"
 
@@ -252,7 +252,7 @@ def test_dwconv_layernorm_run_form_batched_and_ragged_equal_the_separate_kernels
     w9, b = (torch.randn(9, C) * 0.2).to(BF).cuda(), (torch.randn(C) * 0.1).to(BF).cuda()
     lw, lb = (1 + 0.1 * torch.randn(C)).to(BF).cuda(), (0.1 * torch.randn(C)).to(BF).cuda()
     y_ref = ops.dwconv3x3_res(x, w9, b, H, W, batch=B)
-    y, h = ops.dwconv3x3_res_ln(x, w9, b, H, W, lw, lb, 1e-5, batch=B)
+    y, h = ops.dwconv3x3_res_ln(x, w9, b, ops.Grid(H, W, B), lw, lb, 1e-5)
     assert torch.equal(y, y_ref) and torch.equal(h, ops.layernorm(y_ref, lw, lb, 1e-5))
 
 
@@ -266,7 +266,7 @@ def _run_form_cases(ops):
         lb = (0.1 * torch.randn(C)).to(BF).cuda()
         y_ref = ops.dwconv3x3_res(x, w9, b, H, W, batch=B)
         h_ref = ops.layernorm(y_ref, lw, lb, 1e-5)
-        y, h = ops.dwconv3x3_res_ln(x, w9, b, H, W, lw, lb, 1e-5, batch=B)
+        y, h = ops.dwconv3x3_res_ln(x, w9, b, ops.Grid(H, W, B), lw, lb, 1e-5)
         assert torch.equal(y, y_ref) and torch.equal(h, h_ref), f"batch {B} x {H}x{W}x{C}"
     # ragged pack: three images of different sizes, per-image results
     C = 512
@@ -281,10 +281,10 @@ def _run_form_cases(ops):
         rows.append((r0, h_, w_, r0, h_, w_))
         r0 += h_ * w_
     sg = ops.ImgSegs(rows, "cuda", max(h_ * w_ for h_, w_ in sizes), r0, max(h_ * w_ for h_, w_ in sizes), r0)
-    y, h = ops.dwconv3x3_res_ln_var(torch.cat(xs, 0), w9, b, sg, lw, lb, 1e-5)
+    y, h = ops.dwconv3x3_res_ln(torch.cat(xs, 0), w9, b, sg, lw, lb, 1e-5)
     r = 0
     for (h_, w_), xi in zip(sizes, xs):
-        y1, h1 = ops.dwconv3x3_res_ln(xi, w9, b, h_, w_, lw, lb, 1e-5)
+        y1, h1 = ops.dwconv3x3_res_ln(xi, w9, b, ops.Grid(h_, w_), lw, lb, 1e-5)
         n = h_ * w_
         assert torch.equal(y[r:r + n], y1) and torch.equal(h[r:r + n], h1), f"ragged image {h_}x{w_}"
         r += n
@@ -300,36 +300,36 @@ def test_batched_spatial_ops_equal_per_image_calls():
     w9, b9 = (torch.randn(9, C) * 0.2).to(BF).cuda(), (torch.randn(C) * 0.1).to(BF).cuda()
     lw, lb = (1 + 0.1 * torch.randn(C)).to(BF).cuda(), (0.1 * torch.randn(C)).to(BF).cuda()
     per = lambda t, n: [t[i * n:(i + 1) * n].contiguous() for i in range(B)]
-    yb, hb = ops.dwconv3x3_res_ln(x, w9, b9, H, W, lw, lb, 1e-5, batch=B)
+    yb, hb = ops.dwconv3x3_res_ln(x, w9, b9, ops.Grid(H, W, B), lw, lb, 1e-5)
     assert torch.equal(ops.dwconv3x3_res(x, w9, b9, H, W, batch=B), yb)
     for i, xi in enumerate(per(x, H * W)):
-        y1, h1 = ops.dwconv3x3_res_ln(xi, w9, b9, H, W, lw, lb, 1e-5)
+        y1, h1 = ops.dwconv3x3_res_ln(xi, w9, b9, ops.Grid(H, W), lw, lb, 1e-5)
         assert torch.equal(y1, yb[i * H * W:(i + 1) * H * W]) and torch.equal(h1, hb[i * H * W:(i + 1) * H * W]), f"dwconv_ln image {i}"
     for (k, s, p) in ((3, 2, 1), (3, 1, 1), (7, 4, 3)):
-        colb, Ho, Wo = ops.im2col(x, H, W, k, k, s, p, batch=B)
+        colb, (Ho, Wo) = ops.im2col(x, ops.Grid(H, W, B), k, k, s, p), ops.Grid(H, W).conv_out(k, k, s, p).sizes[0]
         for i, xi in enumerate(per(x, H * W)):
-            c1, _, _ = ops.im2col(xi, H, W, k, k, s, p)
+            c1 = ops.im2col(xi, ops.Grid(H, W), k, k, s, p)
             assert torch.equal(c1, colb[i * Ho * Wo:(i + 1) * Ho * Wo]), f"im2col k{k} image {i}"
     ws = 12
-    xw = ops.window_partition(x, H, W, ws, batch=B)
+    xw = ops.window_partition(x, ops.Grid(H, W, B), ws)
     nrow = xw.shape[0] // B
     yw = torch.randn_like(xw)
-    back = ops.window_reverse_add(yw, x, H, W, ws, batch=B)
+    back = ops.window_reverse_add(yw, x, ops.Grid(H, W, B), ws)
     for i, xi in enumerate(per(x, H * W)):
-        assert torch.equal(ops.window_partition(xi, H, W, ws), xw[i * nrow:(i + 1) * nrow]), f"window_partition image {i}"
-        assert torch.equal(ops.window_reverse_add(yw[i * nrow:(i + 1) * nrow].contiguous(), xi, H, W, ws), back[i * H * W:(i + 1) * H * W])
+        assert torch.equal(ops.window_partition(xi, ops.Grid(H, W), ws), xw[i * nrow:(i + 1) * nrow]), f"window_partition image {i}"
+        assert torch.equal(ops.window_reverse_add(yw[i * nrow:(i + 1) * nrow].contiguous(), xi, ops.Grid(H, W), ws), back[i * H * W:(i + 1) * H * W])
     qkv = torch.randn(B * H * W, 3 * C).to(BF).cuda()
-    ab = ops.channel_attention(qkv, C, batch=B)
+    ab = ops.channel_attention(qkv, C, ops.Grid(H, W, B))
     for i, qi in enumerate(per(qkv, H * W)):
-        assert torch.equal(ops.channel_attention(qi, C), ab[i * H * W:(i + 1) * H * W]), f"channel attention image {i}"
+        assert torch.equal(ops.channel_attention(qi, C, ops.Grid(H, W)), ab[i * H * W:(i + 1) * H * W]), f"channel attention image {i}"
     Co = 16
     src = torch.randn(B * H * W, 4 * Co).to(BF).cuda()
-    ps = ops.pixel_shuffle2(src, H, W, Co, batch=B)
-    mp = ops.maxpool2(x, H, W, batch=B)
+    ps = ops.pixel_shuffle2(src, ops.Grid(H, W, B), Co)
+    mp = ops.maxpool2(x, ops.Grid(H, W, B))
     for i in range(B):
-        assert torch.equal(ops.pixel_shuffle2(src[i * H * W:(i + 1) * H * W].contiguous(), H, W, Co), ps[i * 4 * H * W:(i + 1) * 4 * H * W])
+        assert torch.equal(ops.pixel_shuffle2(src[i * H * W:(i + 1) * H * W].contiguous(), ops.Grid(H, W), Co), ps[i * 4 * H * W:(i + 1) * 4 * H * W])
         n2 = (H // 2) * (W // 2)
-        assert torch.equal(ops.maxpool2(x[i * H * W:(i + 1) * H * W].contiguous(), H, W), mp[i * n2:(i + 1) * n2])
+        assert torch.equal(ops.maxpool2(x[i * H * W:(i + 1) * H * W].contiguous(), ops.Grid(H, W)), mp[i * n2:(i + 1) * n2])
     img = torch.randn(B, 3, H, W).cuda()
     hb8 = ops.nchw_to_hwc8(img)
     for i in range(B):

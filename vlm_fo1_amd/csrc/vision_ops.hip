@@ -770,22 +770,37 @@ static inline int grid_for(long long total) {
     return (int)(g < 4096 ? (g > 0 ? g : 1) : 4096);
 }
 
+// Which images a spatial launch covers.  Uniform: `batch` images of H x W pixels stacked along the rows, one grid column, the kernel takes
+// (H, W, batch) and no table.  Ragged: `cols` images of their own sizes, one grid column each, the kernel takes (0, 0, 1) and the device
+// fo1_img_seg table; max_ext / total_ext = the largest image's and all images' extent in the operator's unit (pixels, window rows, tokens).
+struct ImgBatch {
+    bool ragged;
+    int H, W, batch;
+    const ImgSeg* segs;
+    int cols;
+    int max_ext;
+    long long total_ext;
+    bool some() const { return ragged ? max_ext > 0 : batch >= 1; }
+    // the grid's and the work figure's extent, given one uniform image's
+    long long largest(long long per_image) const { return ragged ? max_ext : batch * per_image; }
+    long long total(long long per_image) const { return ragged ? total_ext : batch * per_image; }
+};
+static inline ImgBatch uniform_batch(int H, int W, int batch) { return {false, H, W, batch, nullptr, 1, 0, 0}; }
+static inline ImgBatch ragged_batch(const void* segs, int n_img, int max_ext, long long total_ext) {
+    return {true, 0, 0, 1, (const ImgSeg*)segs, n_img, max_ext, total_ext};
+}
+
 }  // namespace fo1
 
-extern "C" {
-
-int fo1_dwconv3x3_bf16(const void* x, const void* weight9c, const void* bias, void* y, int H, int W, int C, int batch, void* stream) {
+// ---- one launcher per spatial operator: the checks and the launch once, for a uniform batch or a ragged one (`what` names the entry) ---
+static int check_segs(const fo1::ImgBatch& g, const char* what) {
     using namespace fo1;
-    FO1_CHECK_ARG(x && weight9c && bias && y && x != y, "dwconv: NULL operand or in-place call");
-    FO1_CHECK_ARG(H > 0 && W > 0 && C > 0 && C % 8 == 0 && batch >= 1, "dwconv: bad shape %dx%dx%d x%d", H, W, C, batch);
-    FO1_LAUNCH("dwconv3x3", (double)batch * H * W * C * 4.0, dwconv3x3_kernel, dim3(grid_for((long long)batch * H * W * (C / 8))), dim3(256), 0,
-               (hipStream_t)stream, (const uint16_t*)x, (const uint16_t*)weight9c, (const uint16_t*)bias, (uint16_t*)y, H, W, C, batch);
+    FO1_CHECK_ARG(!g.ragged || (g.segs && g.cols >= 1 && g.cols <= 65535), "%s: need a device fo1_img_seg table with 1..65535 images", what);
     return FO1_OK;
 }
 
 #ifdef FO1_ENABLE_AB
 static int g_dwln_run = 1;      // 0 = per-pixel form everywhere, 1 = product rule, 2 = the run form at every size it exists for (tests)
-int fo1_dwconv_ln_set_form(int run_form) { g_dwln_run = run_form < 0 || run_form > 2 ? 1 : run_form; return FO1_OK; }
 #else
 static constexpr int g_dwln_run = 1;
 #endif
@@ -799,25 +814,30 @@ static int dwln_form(int chunks, long long map_pixels, long long total_pixels) {
     return waves >= 4096 || g_dwln_run == 2 ? chunks : 0;
 }
 
-int fo1_dwconv3x3_ln_bf16(const void* x, const void* weight9c, const void* bias, void* y, const void* ln_weight, const void* ln_bias,
-                          float ln_eps, void* h, int H, int W, int C, int batch, void* stream) {
+static int dwconv3x3_ln(const void* x, const void* weight9c, const void* bias, void* y, const void* ln_weight, const void* ln_bias, float ln_eps, void* h,
+                        int C, const fo1::ImgBatch& g, void* stream, const char* what) {
     using namespace fo1;
-    FO1_CHECK_ARG(x && weight9c && bias && y && ln_weight && ln_bias && h && x != y && x != h && y != h,
-                  "dwconv_ln: NULL operand or aliased buffers");
-    FO1_CHECK_ARG(H > 0 && W > 0 && C > 0 && C % 8 == 0 && C <= 64 * kDwLnChunks * 8 && batch >= 1, "dwconv_ln: bad shape %dx%dx%d (C <= 2048)", H, W, C);
-    const int chunks = C / 8, npix = batch * H * W;
+    FO1_CHECK_ARG(x && weight9c && bias && y && ln_weight && ln_bias && h && x != y && x != h && y != h, "%s: NULL operand or aliased buffers", what);
+    if (int rc = check_segs(g, what)) return rc;
+    const bool c_ok = C > 0 && C % 8 == 0 && C <= 64 * kDwLnChunks * 8;
+    if (g.ragged) FO1_CHECK_ARG(g.max_ext > 0 && c_ok, "%s: bad shape (C <= 2048)", what);
+    else FO1_CHECK_ARG(g.H > 0 && g.W > 0 && c_ok && g.batch >= 1, "%s: bad shape %dx%dx%d (C <= 2048)", what, g.H, g.W, C);
+    const int chunks = C / 8;
+    // the run form's grid.  Uniform: the batch's runs.  Ragged: an image has H * ceil(W / 8) <= H * W runs, so its pixel count covers them; the
+    // workgroups past an image's last run leave at once
+    const long long runs = (long long)g.batch * g.H * cdiv(g.W, chunks == 128 ? 4 : kDwRun);
+    FO1_CHECK_ARG(runs < (1ll << 31), "%s: too many pixel runs", what);
+    const int pixels = g.ragged ? g.max_ext : g.batch * g.H * g.W, run_units = g.ragged ? g.max_ext : (int)runs;
+    const double work = (g.ragged ? (double)g.total_ext : (double)g.batch * g.H * g.W) * C * 6.0;
     const uint16_t *xp = (const uint16_t*)x, *wp = (const uint16_t*)weight9c, *bp = (const uint16_t*)bias, *lwp = (const uint16_t*)ln_weight,
                    *lbp = (const uint16_t*)ln_bias;
-    const double work = (double)batch * H * W * C * 6.0;
-    const long long runs = (long long)batch * H * cdiv(W, chunks == 128 ? 4 : kDwRun);
-    FO1_CHECK_ARG(runs < (1ll << 31), "dwconv_ln: too many pixel runs");
 #define FO1_DWLN_RUN(PPW, NCH) \
-    FO1_LAUNCH("dwconv3x3_ln", work, (dwconv3x3_ln_run_kernel<PPW, NCH, (NCH > 1 ? 4 : 8)>), dim3(cdiv((int)runs, 4 * PPW)), dim3(256), 0, (hipStream_t)stream, xp, wp, bp, \
-               (uint16_t*)y, lwp, lbp, (uint16_t*)h, H, W, C, ln_eps, batch, (const ImgSeg*)nullptr)
+    FO1_LAUNCH("dwconv3x3_ln", work, (dwconv3x3_ln_run_kernel<PPW, NCH, (NCH > 1 ? 4 : 8)>), dim3(cdiv(run_units, 4 * PPW), g.cols), dim3(256), 0, \
+               (hipStream_t)stream, xp, wp, bp, (uint16_t*)y, lwp, lbp, (uint16_t*)h, g.H, g.W, C, ln_eps, g.batch, g.segs)
 #define FO1_DWLN_PIX(PPW) \
-    FO1_LAUNCH("dwconv3x3_ln", work, dwconv3x3_ln_kernel<PPW>, dim3(cdiv(npix, 4 * PPW)), dim3(256), 0, (hipStream_t)stream, xp, wp, bp, (uint16_t*)y, \
-               lwp, lbp, (uint16_t*)h, H, W, C, ln_eps, batch, (const ImgSeg*)nullptr)
-    const int form = dwln_form(chunks, npix, npix);
+    FO1_LAUNCH("dwconv3x3_ln", work, dwconv3x3_ln_kernel<PPW>, dim3(cdiv(pixels, 4 * PPW), g.cols), dim3(256), 0, (hipStream_t)stream, xp, wp, bp, \
+               (uint16_t*)y, lwp, lbp, (uint16_t*)h, g.H, g.W, C, ln_eps, g.batch, g.segs)
+    const int form = dwln_form(chunks, pixels, g.ragged ? g.total_ext : pixels);
     if (form == 16) { FO1_DWLN_RUN(4, 1); } else if (form == 32) { FO1_DWLN_RUN(2, 1); } else if (form == 64) { FO1_DWLN_RUN(1, 1); }
     else if (form == 128) { FO1_DWLN_RUN(1, 2); }
     else if (chunks <= 16) { FO1_DWLN_PIX(4); } else if (chunks <= 32) { FO1_DWLN_PIX(2); } else { FO1_DWLN_PIX(1); }
@@ -826,93 +846,193 @@ int fo1_dwconv3x3_ln_bf16(const void* x, const void* weight9c, const void* bias,
     return FO1_OK;
 }
 
-int fo1_im2col_bf16(const void* x, void* col, int H, int W, int C, int KH, int KW, int stride, int pad, int ld_col, int batch, void* stream) {
+static int im2col(const void* x, void* col, int C, int KH, int KW, int stride, int pad, int ld_col, const fo1::ImgBatch& g, void* stream, const char* what) {
     using namespace fo1;
-    FO1_CHECK_ARG(x && col, "im2col: NULL operand");
-    FO1_CHECK_ARG(C > 0 && C % 8 == 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0, "im2col: bad parameters");
-    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    FO1_CHECK_ARG(Ho > 0 && Wo > 0 && ld_col >= KH * KW * C && ld_col % 8 == 0 && batch >= 1, "im2col: bad output shape");
-    FO1_LAUNCH("im2col", (double)batch * Ho * Wo * KH * KW * C * 4.0, im2col_kernel, dim3(grid_for((long long)batch * Ho * Wo * KH * KW * (C / 8))),
-               dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, (uint16_t*)col, H, W, C, KH, KW, stride, pad, Ho, Wo, ld_col, batch, (const ImgSeg*)nullptr);
+    FO1_CHECK_ARG(x && col, "%s: NULL operand", what);
+    if (int rc = check_segs(g, what)) return rc;
+    // a ragged call has its output sizes in the table and makes one check; a uniform call derives them and names them in a check of their own
+    const bool ld_ok = ld_col >= KH * KW * C && ld_col % 8 == 0;
+    FO1_CHECK_ARG(C > 0 && C % 8 == 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0 && (!g.ragged || (ld_ok && g.max_ext > 0)), "%s: bad parameters", what);
+    const int Ho = g.ragged ? 0 : (g.H + 2 * pad - KH) / stride + 1, Wo = g.ragged ? 0 : (g.W + 2 * pad - KW) / stride + 1;
+    FO1_CHECK_ARG(g.ragged || (Ho > 0 && Wo > 0 && ld_ok && g.batch >= 1), "%s: bad output shape", what);
+    const long long out_pixels = (long long)Ho * Wo;
+    FO1_LAUNCH("im2col", (double)g.total(out_pixels) * KH * KW * C * 4.0, im2col_kernel, dim3(grid_for(g.largest(out_pixels) * KH * KW * (C / 8)), g.cols),
+               dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, (uint16_t*)col, g.H, g.W, C, KH, KW, stride, pad, Ho, Wo, ld_col, g.batch, g.segs);
     return FO1_OK;
 }
 
-int fo1_window_partition_bf16(const void* x, void* xw, int H, int W, int C, int ws, int batch, void* stream) {
+static int window_partition(const void* x, void* xw, int C, int ws, const fo1::ImgBatch& g, void* stream, const char* what) {
     using namespace fo1;
-    FO1_CHECK_ARG(x && xw && C % 8 == 0 && ws > 0 && batch >= 1, "window_partition: bad arguments");
-    const int nWy = cdiv(H, ws), nWx = cdiv(W, ws);
-    FO1_LAUNCH("window_partition", (double)batch * nWy * nWx * ws * ws * C * 4.0, window_partition_kernel,
-               dim3(grid_for((long long)batch * nWy * nWx * ws * ws * (C / 8))), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x,
-               (uint16_t*)xw, H, W, C, ws, nWy, nWx, batch, (const ImgSeg*)nullptr);
+    FO1_CHECK_ARG(x && xw && C % 8 == 0 && ws > 0 && g.some(), "%s: bad arguments", what);
+    if (int rc = check_segs(g, what)) return rc;
+    const int nWy = cdiv(g.H, ws), nWx = cdiv(g.W, ws);         // (0 with a table: the kernel reads each image's own)
+    const long long rows = (long long)nWy * nWx * ws * ws;
+    FO1_LAUNCH("window_partition", (double)g.total(rows) * C * 4.0, window_partition_kernel, dim3(grid_for(g.largest(rows) * (C / 8)), g.cols), dim3(256), 0,
+               (hipStream_t)stream, (const uint16_t*)x, (uint16_t*)xw, g.H, g.W, C, ws, nWy, nWx, g.batch, g.segs);
     return FO1_OK;
 }
 
-int fo1_window_reverse_add_bf16(const void* yw, const void* shortcut, void* y, int H, int W, int C, int ws, int batch, void* stream) {
+static int window_reverse_add(const void* yw, const void* shortcut, void* y, int C, int ws, const fo1::ImgBatch& g, void* stream, const char* what) {
     using namespace fo1;
-    FO1_CHECK_ARG(yw && shortcut && y && C % 8 == 0 && ws > 0 && batch >= 1, "window_reverse: bad arguments");
-    FO1_LAUNCH("window_reverse_add", (double)batch * H * W * C * 6.0, window_reverse_add_kernel, dim3(grid_for((long long)batch * H * W * (C / 8))),
-               dim3(256), 0, (hipStream_t)stream, (const uint16_t*)yw, (const uint16_t*)shortcut, (uint16_t*)y, H, W, C, ws, cdiv(W, ws),
-               cdiv(H, ws) * cdiv(W, ws), batch, (const ImgSeg*)nullptr);
+    FO1_CHECK_ARG(yw && shortcut && y && C % 8 == 0 && ws > 0 && g.some(), "%s: bad arguments", what);
+    if (int rc = check_segs(g, what)) return rc;
+    const long long pixels = (long long)g.H * g.W;
+    FO1_LAUNCH("window_reverse_add", (double)g.total(pixels) * C * 6.0, window_reverse_add_kernel, dim3(grid_for(g.largest(pixels) * (C / 8)), g.cols), dim3(256), 0,
+               (hipStream_t)stream, (const uint16_t*)yw, (const uint16_t*)shortcut, (uint16_t*)y, g.H, g.W, C, ws, cdiv(g.W, ws), cdiv(g.H, ws) * cdiv(g.W, ws),
+               g.batch, g.segs);
     return FO1_OK;
 }
 
 #ifdef FO1_ENABLE_AB
 static int g_chattn_mfma = 1;
-int fo1_channel_attention_set_impl(int mfma) { g_chattn_mfma = mfma != 0; return FO1_OK; }
 #else
 static constexpr int g_chattn_mfma = 1;
 #endif
+
+// qkv rows of n images (g.H = the tokens of each, or the table's (row0, N_i)): every image's tokens form their own 32 x 32 per-group attention
+// matrices.  reference: q * N^-0.5 (modeling_davit.py:165); with a table the kernel takes each image's own N_i (scale 0)
+static int channel_attention(const void* qkv, int ld, int C, void* out, int ldo, const fo1::ImgBatch& g, void* workspace, size_t workspace_bytes, void* stream,
+                             const char* what) {
+    using namespace fo1;
+    const int N = g.ragged ? g.max_ext : g.H, n = g.ragged ? g.cols : g.batch;        // the largest image's tokens, images
+    FO1_CHECK_ARG(qkv && out && workspace, "%s: NULL operand", what);
+    if (int rc = check_segs(g, what)) return rc;
+    const bool ok = N > 0 && C > 0 && C % 32 == 0 && ld >= 3 * C && ld % 8 == 0 && ldo >= C && n >= 1;
+    if (g.ragged) FO1_CHECK_ARG(ok, "%s: bad shape", what);
+    else FO1_CHECK_ARG(ok, "%s: bad shape N=%d C=%d", what, N, C);
+    FO1_CHECK_ARG(ldo % 8 == 0 && ((uintptr_t)qkv & 15) == 0 && ((uintptr_t)out & 15) == 0, "%s: rows must be 16-byte aligned (ldo %% 8, qkv / out pointers)", what);
+    if (workspace_bytes < fo1_channel_attention_workspace_bytes(N, C, n)) return set_err(FO1_ERR_WORKSPACE, "%s: workspace too small", what);
+    const int G = C / 32, chunks = cdiv(N, kCaTok);
+    float* part = (float*)workspace;
+    float* A = part + (size_t)n * chunks * G * 1024;
+    hipStream_t st = (hipStream_t)stream;
+    const uint16_t* in = (const uint16_t*)qkv;
+    const double work = (g.ragged ? (double)g.total_ext : (double)n * N) * C * 4.0;
+    if (g_chattn_mfma) {
+        FO1_LAUNCH("chattn_gram", work, chattn_gram_mfma_kernel, dim3(chunks, cdiv(G, 4), n), dim3(256), 0, st, in, ld, g.H, C, part, g.segs);
+    } else {
+        FO1_LAUNCH("chattn_gram", work, chattn_gram_kernel, dim3(chunks, G, n), dim3(256), 0, st, in, ld, g.H, C, part, g.segs);
+    }
+    FO1_LAUNCH("chattn_softmax", (double)n * chunks * G * 4096.0, chattn_softmax_kernel, dim3(G, n), dim3(1024), 0, st, (const float*)part, chunks, G,
+               g.ragged ? 0.f : 1.0f / sqrtf((float)N), A, g.segs);
+    if (g_chattn_mfma) {
+        FO1_LAUNCH("chattn_apply", work, chattn_apply_mfma_kernel, dim3(cdiv(N, 128), cdiv(G, 4), n), dim3(256), 0, st, in, ld, g.H, C, (const float*)A,
+                   (uint16_t*)out, ldo, g.segs);
+    } else {
+        FO1_LAUNCH("chattn_apply", work, chattn_apply_kernel, dim3(min(cdiv(N, 256), 512), G, n), dim3(256), 0, st, in, ld, g.H, C, (const float*)A,
+                   (uint16_t*)out, ldo, g.segs);
+    }
+    return FO1_OK;
+}
+
+static int pixel_shuffle2(const void* src, void* dst, int Co, const fo1::ImgBatch& g, void* stream, const char* what) {
+    using namespace fo1;
+    FO1_CHECK_ARG(src && dst && Co > 0 && Co % 8 == 0 && g.some(), "%s: bad arguments", what);
+    if (int rc = check_segs(g, what)) return rc;
+    const long long pixels = (long long)g.H * g.W;
+    FO1_LAUNCH("pixel_shuffle2", (double)g.total(pixels) * 4 * Co * 4.0, pixel_shuffle2_kernel, dim3(grid_for(g.largest(pixels) * 4 * (Co / 8)), g.cols), dim3(256), 0,
+               (hipStream_t)stream, (const uint16_t*)src, (uint16_t*)dst, g.H, g.W, Co, g.batch, g.segs);
+    return FO1_OK;
+}
+
+// (the extents of a ragged call count OUTPUT pixels, four input pixels each)
+static int maxpool2(const void* x, void* y, int C, const fo1::ImgBatch& g, void* stream, const char* what) {
+    using namespace fo1;
+    FO1_CHECK_ARG(x && y && C % 8 == 0 && (g.ragged ? g.max_ext > 0 : g.H >= 2 && g.W >= 2 && g.batch >= 1), "%s: bad arguments", what);
+    if (int rc = check_segs(g, what)) return rc;
+    const double in_pixels = g.ragged ? (double)g.total_ext * 4 : (double)g.batch * g.H * g.W;
+    FO1_LAUNCH("maxpool2", in_pixels * C * 2.5, maxpool2_kernel, dim3(grid_for(g.largest((long long)(g.H / 2) * (g.W / 2)) * (C / 8)), g.cols), dim3(256), 0,
+               (hipStream_t)stream, (const uint16_t*)x, (uint16_t*)y, g.H, g.W, C, g.batch, g.segs);
+    return FO1_OK;
+}
+
+extern "C" {
+
+int fo1_dwconv3x3_bf16(const void* x, const void* weight9c, const void* bias, void* y, int H, int W, int C, int batch, void* stream) {
+    using namespace fo1;
+    FO1_CHECK_ARG(x && weight9c && bias && y && x != y, "dwconv: NULL operand or in-place call");
+    FO1_CHECK_ARG(H > 0 && W > 0 && C > 0 && C % 8 == 0 && batch >= 1, "dwconv: bad shape %dx%dx%d x%d", H, W, C, batch);
+    FO1_LAUNCH("dwconv3x3", (double)batch * H * W * C * 4.0, dwconv3x3_kernel, dim3(grid_for((long long)batch * H * W * (C / 8))), dim3(256), 0,
+               (hipStream_t)stream, (const uint16_t*)x, (const uint16_t*)weight9c, (const uint16_t*)bias, (uint16_t*)y, H, W, C, batch);
+    return FO1_OK;
+}
+
+#ifdef FO1_ENABLE_AB
+int fo1_dwconv_ln_set_form(int run_form) { g_dwln_run = run_form < 0 || run_form > 2 ? 1 : run_form; return FO1_OK; }
+int fo1_channel_attention_set_impl(int mfma) { g_chattn_mfma = mfma != 0; return FO1_OK; }
+#endif
+
+// ---- the spatial operators' entries: a uniform batch of same-size images, and (`_var`) a ragged one through a device fo1_img_seg table -------
+int fo1_dwconv3x3_ln_bf16(const void* x, const void* weight9c, const void* bias, void* y, const void* ln_weight, const void* ln_bias,
+                          float ln_eps, void* h, int H, int W, int C, int batch, void* stream) {
+    return dwconv3x3_ln(x, weight9c, bias, y, ln_weight, ln_bias, ln_eps, h, C, fo1::uniform_batch(H, W, batch), stream, "dwconv_ln");
+}
+
+int fo1_dwconv3x3_ln_var_bf16(const void* x, const void* weight9c, const void* bias, void* y, const void* ln_weight, const void* ln_bias,
+                              float ln_eps, void* h, const void* segs, int n_img, int max_pixels, long long total_pixels, int C, void* stream) {
+    return dwconv3x3_ln(x, weight9c, bias, y, ln_weight, ln_bias, ln_eps, h, C, fo1::ragged_batch(segs, n_img, max_pixels, total_pixels), stream, "dwconv_ln_var");
+}
+
+int fo1_im2col_bf16(const void* x, void* col, int H, int W, int C, int KH, int KW, int stride, int pad, int ld_col, int batch, void* stream) {
+    return im2col(x, col, C, KH, KW, stride, pad, ld_col, fo1::uniform_batch(H, W, batch), stream, "im2col");
+}
+
+int fo1_im2col_var_bf16(const void* x, void* col, const void* segs, int n_img, int max_out_pixels, long long total_out_pixels, int C, int KH, int KW,
+                        int stride, int pad, int ld_col, void* stream) {
+    return im2col(x, col, C, KH, KW, stride, pad, ld_col, fo1::ragged_batch(segs, n_img, max_out_pixels, total_out_pixels), stream, "im2col_var");
+}
+
+int fo1_window_partition_bf16(const void* x, void* xw, int H, int W, int C, int ws, int batch, void* stream) {
+    return window_partition(x, xw, C, ws, fo1::uniform_batch(H, W, batch), stream, "window_partition");
+}
+
+int fo1_window_partition_var_bf16(const void* x, void* xw, const void* segs, int n_img, int max_window_rows, long long total_window_rows, int C, int ws,
+                                  void* stream) {
+    return window_partition(x, xw, C, ws, fo1::ragged_batch(segs, n_img, max_window_rows, total_window_rows), stream, "window_partition_var");
+}
+
+int fo1_window_reverse_add_bf16(const void* yw, const void* shortcut, void* y, int H, int W, int C, int ws, int batch, void* stream) {
+    return window_reverse_add(yw, shortcut, y, C, ws, fo1::uniform_batch(H, W, batch), stream, "window_reverse");
+}
+
+int fo1_window_reverse_add_var_bf16(const void* yw, const void* shortcut, void* y, const void* segs, int n_img, int max_pixels, long long total_pixels,
+                                    int C, int ws, void* stream) {
+    return window_reverse_add(yw, shortcut, y, C, ws, fo1::ragged_batch(segs, n_img, max_pixels, total_pixels), stream, "window_reverse_var");
+}
 
 size_t fo1_channel_attention_workspace_bytes(int N, int C, int batch) {
     const int G = C / 32, chunks = fo1::cdiv(N, fo1::kCaTok);
     return (size_t)batch * ((size_t)chunks * G * 1024 + (size_t)G * 1024) * sizeof(float);
 }
 
-// qkv rows [batch * N, 3C]: every image's N tokens form their own 32 x 32 per-group attention matrices
+size_t fo1_channel_attention_var_workspace_bytes(int max_tokens, int C, int n_img) { return fo1_channel_attention_workspace_bytes(max_tokens, C, n_img); }
+
+// qkv rows [batch * N, 3C]; the ragged entry's table rows are (segs[i].in_row0, segs[i].H = N_i tokens)
 int fo1_channel_attention_bf16(const void* qkv, int ld, int N, int C, void* out, int ldo, int batch, void* workspace, size_t workspace_bytes,
                                void* stream) {
-    using namespace fo1;
-    FO1_CHECK_ARG(qkv && out && workspace, "channel_attention: NULL operand");
-    FO1_CHECK_ARG(N > 0 && C > 0 && C % 32 == 0 && ld >= 3 * C && ld % 8 == 0 && ldo >= C && batch >= 1, "channel_attention: bad shape N=%d C=%d", N, C);
-    FO1_CHECK_ARG(ldo % 8 == 0 && ((uintptr_t)qkv & 15) == 0 && ((uintptr_t)out & 15) == 0, "channel_attention: rows must be 16-byte aligned (ldo %% 8, qkv / out pointers)");
-    if (workspace_bytes < fo1_channel_attention_workspace_bytes(N, C, batch))
-        return set_err(FO1_ERR_WORKSPACE, "channel_attention: workspace too small");
-    const int G = C / 32, chunks = cdiv(N, kCaTok);
-    float* part = (float*)workspace;
-    float* A = part + (size_t)batch * chunks * G * 1024;
-    hipStream_t st = (hipStream_t)stream;
-    if (g_chattn_mfma) {
-        FO1_LAUNCH("chattn_gram", (double)batch * N * C * 4.0, chattn_gram_mfma_kernel, dim3(chunks, cdiv(G, 4), batch), dim3(256), 0, st, (const uint16_t*)qkv, ld, N, C, part, (const ImgSeg*)nullptr);
-    } else {
-        FO1_LAUNCH("chattn_gram", (double)batch * N * C * 4.0, chattn_gram_kernel, dim3(chunks, G, batch), dim3(256), 0, st, (const uint16_t*)qkv, ld, N, C, part, (const ImgSeg*)nullptr);
-    }
-    // reference: q * N^-0.5 (modeling_davit.py:165)
-    FO1_LAUNCH("chattn_softmax", (double)batch * chunks * G * 4096.0, chattn_softmax_kernel, dim3(G, batch), dim3(1024), 0, st, (const float*)part, chunks, G,
-               1.0f / sqrtf((float)N), A, (const ImgSeg*)nullptr);
-    if (g_chattn_mfma) {
-        FO1_LAUNCH("chattn_apply", (double)batch * N * C * 4.0, chattn_apply_mfma_kernel, dim3(cdiv(N, 128), cdiv(G, 4), batch), dim3(256), 0, st, (const uint16_t*)qkv,
-                   ld, N, C, (const float*)A, (uint16_t*)out, ldo, (const ImgSeg*)nullptr);
-    } else {
-        FO1_LAUNCH("chattn_apply", (double)batch * N * C * 4.0, chattn_apply_kernel, dim3(min(cdiv(N, 256), 512), G, batch), dim3(256), 0, st, (const uint16_t*)qkv, ld,
-                   N, C, (const float*)A, (uint16_t*)out, ldo, (const ImgSeg*)nullptr);
-    }
-    return FO1_OK;
+    return channel_attention(qkv, ld, C, out, ldo, fo1::uniform_batch(N, 1, batch), workspace, workspace_bytes, stream, "channel_attention");
+}
+
+int fo1_channel_attention_var_bf16(const void* qkv, int ld, const void* segs, int n_img, int max_tokens, long long total_tokens, int C, void* out, int ldo,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    return channel_attention(qkv, ld, C, out, ldo, fo1::ragged_batch(segs, n_img, max_tokens, total_tokens), workspace, workspace_bytes, stream,
+                             "channel_attention_var");
 }
 
 int fo1_pixel_shuffle2_bf16(const void* src, void* dst, int H, int W, int Co, int batch, void* stream) {
-    using namespace fo1;
-    FO1_CHECK_ARG(src && dst && Co > 0 && Co % 8 == 0 && batch >= 1, "pixel_shuffle: bad arguments");
-    FO1_LAUNCH("pixel_shuffle2", (double)batch * H * W * 4 * Co * 4.0, pixel_shuffle2_kernel, dim3(grid_for((long long)batch * H * W * 4 * (Co / 8))),
-               dim3(256), 0, (hipStream_t)stream, (const uint16_t*)src, (uint16_t*)dst, H, W, Co, batch, (const ImgSeg*)nullptr);
-    return FO1_OK;
+    return pixel_shuffle2(src, dst, Co, fo1::uniform_batch(H, W, batch), stream, "pixel_shuffle");
+}
+
+int fo1_pixel_shuffle2_var_bf16(const void* src, void* dst, const void* segs, int n_img, int max_pixels, long long total_pixels, int Co, void* stream) {
+    return pixel_shuffle2(src, dst, Co, fo1::ragged_batch(segs, n_img, max_pixels, total_pixels), stream, "pixel_shuffle_var");
 }
 
 int fo1_maxpool2_bf16(const void* x, void* y, int H, int W, int C, int batch, void* stream) {
-    using namespace fo1;
-    FO1_CHECK_ARG(x && y && C % 8 == 0 && H >= 2 && W >= 2 && batch >= 1, "maxpool: bad arguments");
-    FO1_LAUNCH("maxpool2", (double)batch * H * W * C * 2.5, maxpool2_kernel, dim3(grid_for((long long)batch * (H / 2) * (W / 2) * (C / 8))), dim3(256), 0,
-               (hipStream_t)stream, (const uint16_t*)x, (uint16_t*)y, H, W, C, batch, (const ImgSeg*)nullptr);
-    return FO1_OK;
+    return maxpool2(x, y, C, fo1::uniform_batch(H, W, batch), stream, "maxpool");
+}
+
+int fo1_maxpool2_var_bf16(const void* x, void* y, const void* segs, int n_img, int max_out_pixels, long long total_out_pixels, int C, void* stream) {
+    return maxpool2(x, y, C, fo1::ragged_batch(segs, n_img, max_out_pixels, total_out_pixels), stream, "maxpool_var");
 }
 
 int fo1_nchw_to_hwc8_bf16(const void* img, int is_f32, void* out, int H, int W, int batch, void* stream) {
@@ -935,125 +1055,6 @@ int fo1_gather_rows_bf16(const void* table0, int ld0, const void* table1, int ld
     FO1_LAUNCH("gather_rows", (double)R * D * 4.0, gather_rows_kernel, dim3(grid_for((long long)R * (D / 8))), dim3(256), 0,
                (hipStream_t)stream, (const uint16_t*)table0, (const uint16_t*)table1, (const uint16_t*)table2, ld0, ld1, ld2, plan,
                (uint16_t*)out, ldo, R, D);
-    return FO1_OK;
-}
-
-// ---- ragged image batches: the same kernels, one workgroup column per image (fo1_img_seg table in device memory) ----------------
-static int check_segs(const void* segs, int n_img, const char* what) {
-    using namespace fo1;
-    FO1_CHECK_ARG(segs && n_img >= 1 && n_img <= 65535, "%s: need a device fo1_img_seg table with 1..65535 images", what);
-    return FO1_OK;
-}
-
-int fo1_dwconv3x3_ln_var_bf16(const void* x, const void* weight9c, const void* bias, void* y, const void* ln_weight, const void* ln_bias,
-                              float ln_eps, void* h, const void* segs, int n_img, int max_pixels, long long total_pixels, int C, void* stream) {
-    using namespace fo1;
-    FO1_CHECK_ARG(x && weight9c && bias && y && ln_weight && ln_bias && h && x != y && x != h && y != h, "dwconv_ln_var: NULL operand or aliased buffers");
-    if (int rc = check_segs(segs, n_img, "dwconv_ln_var")) return rc;
-    FO1_CHECK_ARG(max_pixels > 0 && C > 0 && C % 8 == 0 && C <= 64 * kDwLnChunks * 8, "dwconv_ln_var: bad shape (C <= 2048)");
-    const int chunks = C / 8;
-    const ImgSeg* sg = (const ImgSeg*)segs;
-    const double work = (double)total_pixels * C * 6.0;
-#define FO1_DWLN_VAR(PPW, PIXPB) \
-    FO1_LAUNCH("dwconv3x3_ln", work, dwconv3x3_ln_kernel<PPW>, dim3(cdiv(max_pixels, PIXPB), n_img), dim3(256), 0, (hipStream_t)stream, \
-               (const uint16_t*)x, (const uint16_t*)weight9c, (const uint16_t*)bias, (uint16_t*)y, (const uint16_t*)ln_weight, \
-               (const uint16_t*)ln_bias, (uint16_t*)h, 0, 0, C, ln_eps, 1, sg)
-    // the run form's grid: an image has H * ceil(W / 8) <= H * W runs; the workgroups past an image's last run leave at once
-#define FO1_DWLN_VAR_RUN(PPW, NCH) \
-    FO1_LAUNCH("dwconv3x3_ln", work, (dwconv3x3_ln_run_kernel<PPW, NCH, (NCH > 1 ? 4 : 8)>), dim3(cdiv(max_pixels, 4 * PPW), n_img), dim3(256), 0, (hipStream_t)stream, \
-               (const uint16_t*)x, (const uint16_t*)weight9c, (const uint16_t*)bias, (uint16_t*)y, (const uint16_t*)ln_weight, \
-               (const uint16_t*)ln_bias, (uint16_t*)h, 0, 0, C, ln_eps, 1, sg)
-    const int form = dwln_form(chunks, max_pixels, total_pixels);
-    if (form == 16) { FO1_DWLN_VAR_RUN(4, 1); } else if (form == 32) { FO1_DWLN_VAR_RUN(2, 1); } else if (form == 64) { FO1_DWLN_VAR_RUN(1, 1); }
-    else if (form == 128) { FO1_DWLN_VAR_RUN(1, 2); }
-    else if (chunks <= 16) { FO1_DWLN_VAR(4, 16); } else if (chunks <= 32) { FO1_DWLN_VAR(2, 8); } else { FO1_DWLN_VAR(1, 4); }
-#undef FO1_DWLN_VAR_RUN
-#undef FO1_DWLN_VAR
-    return FO1_OK;
-}
-
-int fo1_im2col_var_bf16(const void* x, void* col, const void* segs, int n_img, int max_out_pixels, long long total_out_pixels, int C, int KH, int KW,
-                        int stride, int pad, int ld_col, void* stream) {
-    using namespace fo1;
-    FO1_CHECK_ARG(x && col, "im2col_var: NULL operand");
-    if (int rc = check_segs(segs, n_img, "im2col_var")) return rc;
-    FO1_CHECK_ARG(C > 0 && C % 8 == 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0 && ld_col >= KH * KW * C && ld_col % 8 == 0 && max_out_pixels > 0,
-                  "im2col_var: bad parameters");
-    FO1_LAUNCH("im2col", (double)total_out_pixels * KH * KW * C * 4.0, im2col_kernel, dim3(grid_for((long long)max_out_pixels * KH * KW * (C / 8)), n_img),
-               dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, (uint16_t*)col, 0, 0, C, KH, KW, stride, pad, 0, 0, ld_col, 1, (const ImgSeg*)segs);
-    return FO1_OK;
-}
-
-int fo1_window_partition_var_bf16(const void* x, void* xw, const void* segs, int n_img, int max_window_rows, long long total_window_rows, int C, int ws,
-                                  void* stream) {
-    using namespace fo1;
-    FO1_CHECK_ARG(x && xw && C % 8 == 0 && ws > 0 && max_window_rows > 0, "window_partition_var: bad arguments");
-    if (int rc = check_segs(segs, n_img, "window_partition_var")) return rc;
-    FO1_LAUNCH("window_partition", (double)total_window_rows * C * 4.0, window_partition_kernel, dim3(grid_for((long long)max_window_rows * (C / 8)), n_img),
-               dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, (uint16_t*)xw, 0, 0, C, ws, 0, 0, 1, (const ImgSeg*)segs);
-    return FO1_OK;
-}
-
-int fo1_window_reverse_add_var_bf16(const void* yw, const void* shortcut, void* y, const void* segs, int n_img, int max_pixels, long long total_pixels,
-                                    int C, int ws, void* stream) {
-    using namespace fo1;
-    FO1_CHECK_ARG(yw && shortcut && y && C % 8 == 0 && ws > 0 && max_pixels > 0, "window_reverse_var: bad arguments");
-    if (int rc = check_segs(segs, n_img, "window_reverse_var")) return rc;
-    FO1_LAUNCH("window_reverse_add", (double)total_pixels * C * 6.0, window_reverse_add_kernel, dim3(grid_for((long long)max_pixels * (C / 8)), n_img),
-               dim3(256), 0, (hipStream_t)stream, (const uint16_t*)yw, (const uint16_t*)shortcut, (uint16_t*)y, 0, 0, C, ws, 0, 0, 1, (const ImgSeg*)segs);
-    return FO1_OK;
-}
-
-size_t fo1_channel_attention_var_workspace_bytes(int max_tokens, int C, int n_img) { return fo1_channel_attention_workspace_bytes(max_tokens, C, n_img); }
-
-// qkv rows of n_img images of different token counts (segs[i].H = N_i tokens from row segs[i].in_row0): every image its own 32 x 32
-// per-group attention matrices and its own q * N_i^-0.5
-int fo1_channel_attention_var_bf16(const void* qkv, int ld, const void* segs, int n_img, int max_tokens, long long total_tokens, int C, void* out, int ldo,
-                                   void* workspace, size_t workspace_bytes, void* stream) {
-    using namespace fo1;
-    FO1_CHECK_ARG(qkv && out && workspace, "channel_attention_var: NULL operand");
-    if (int rc = check_segs(segs, n_img, "channel_attention_var")) return rc;
-    FO1_CHECK_ARG(max_tokens > 0 && C > 0 && C % 32 == 0 && ld >= 3 * C && ld % 8 == 0 && ldo >= C, "channel_attention_var: bad shape");
-    FO1_CHECK_ARG(ldo % 8 == 0 && ((uintptr_t)qkv & 15) == 0 && ((uintptr_t)out & 15) == 0, "channel_attention_var: rows must be 16-byte aligned (ldo %% 8, qkv / out pointers)");
-    if (workspace_bytes < fo1_channel_attention_workspace_bytes(max_tokens, C, n_img))
-        return set_err(FO1_ERR_WORKSPACE, "channel_attention_var: workspace too small");
-    const int G = C / 32, chunks = cdiv(max_tokens, kCaTok);
-    float* part = (float*)workspace;
-    float* A = part + (size_t)n_img * chunks * G * 1024;
-    hipStream_t st = (hipStream_t)stream;
-    const ImgSeg* sg = (const ImgSeg*)segs;
-    if (g_chattn_mfma) {
-        FO1_LAUNCH("chattn_gram", (double)total_tokens * C * 4.0, chattn_gram_mfma_kernel, dim3(chunks, cdiv(G, 4), n_img), dim3(256), 0, st, (const uint16_t*)qkv, ld, 0, C, part, sg);
-    } else {
-        FO1_LAUNCH("chattn_gram", (double)total_tokens * C * 4.0, chattn_gram_kernel, dim3(chunks, G, n_img), dim3(256), 0, st, (const uint16_t*)qkv, ld, 0, C, part, sg);
-    }
-    FO1_LAUNCH("chattn_softmax", (double)n_img * chunks * G * 4096.0, chattn_softmax_kernel, dim3(G, n_img), dim3(1024), 0, st, (const float*)part, chunks, G,
-               0.f, A, sg);
-    if (g_chattn_mfma) {
-        FO1_LAUNCH("chattn_apply", (double)total_tokens * C * 4.0, chattn_apply_mfma_kernel, dim3(cdiv(max_tokens, 128), cdiv(G, 4), n_img), dim3(256), 0, st,
-                   (const uint16_t*)qkv, ld, 0, C, (const float*)A, (uint16_t*)out, ldo, sg);
-    } else {
-        FO1_LAUNCH("chattn_apply", (double)total_tokens * C * 4.0, chattn_apply_kernel, dim3(min(cdiv(max_tokens, 256), 512), G, n_img), dim3(256), 0, st,
-                   (const uint16_t*)qkv, ld, 0, C, (const float*)A, (uint16_t*)out, ldo, sg);
-    }
-    return FO1_OK;
-}
-
-int fo1_pixel_shuffle2_var_bf16(const void* src, void* dst, const void* segs, int n_img, int max_pixels, long long total_pixels, int Co, void* stream) {
-    using namespace fo1;
-    FO1_CHECK_ARG(src && dst && Co > 0 && Co % 8 == 0 && max_pixels > 0, "pixel_shuffle_var: bad arguments");
-    if (int rc = check_segs(segs, n_img, "pixel_shuffle_var")) return rc;
-    FO1_LAUNCH("pixel_shuffle2", (double)total_pixels * 4 * Co * 4.0, pixel_shuffle2_kernel, dim3(grid_for((long long)max_pixels * 4 * (Co / 8)), n_img),
-               dim3(256), 0, (hipStream_t)stream, (const uint16_t*)src, (uint16_t*)dst, 0, 0, Co, 1, (const ImgSeg*)segs);
-    return FO1_OK;
-}
-
-int fo1_maxpool2_var_bf16(const void* x, void* y, const void* segs, int n_img, int max_out_pixels, long long total_out_pixels, int C, void* stream) {
-    using namespace fo1;
-    FO1_CHECK_ARG(x && y && C % 8 == 0 && max_out_pixels > 0, "maxpool_var: bad arguments");
-    if (int rc = check_segs(segs, n_img, "maxpool_var")) return rc;
-    FO1_LAUNCH("maxpool2", (double)total_out_pixels * 4 * C * 2.5, maxpool2_kernel, dim3(grid_for((long long)max_out_pixels * (C / 8)), n_img), dim3(256), 0,
-               (hipStream_t)stream, (const uint16_t*)x, (uint16_t*)y, 0, 0, C, 1, (const ImgSeg*)segs);
     return FO1_OK;
 }
 

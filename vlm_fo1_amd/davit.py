@@ -103,35 +103,68 @@ class DaViT:
         items = self._window_items(n // (ws * ws), ws * ws, heads)
         return ops.attention(qkv[:, :C], qkv[:, C:2 * C], vt, items, heads, heads, hd, float(hd) ** -0.5, False, flops=4.0 * C * n * ws * ws)
 
-    def _conv_ffn(self, x, H, W, d, B=1):
+    # Every block takes the geometry of its level, `lv`: the roles `pix` (pixel rows), `win` (12 x 12 windows), `tok` (channel-attention tokens)
+    # and `conv` (previous level -> this level).  A uniform pass has one ops.Grid in the first three and the previous level's Grid in `conv`;
+    # a ragged pass has the level's ops.ImgSegs tables (RaggedAuxPlan.levels[i]).
+    def _conv_ffn(self, x, pix, d):
         """conv2 (depthwise 3x3 + residual) -> LayerNorm -> MLP(+residual); the conv and the norm are one launch."""
-        x, h = ops.dwconv3x3_res_ln(x, d["conv2_w"], d["conv2_b"], H, W, d["fn_w"], d["fn_b"], 1e-5, batch=B)
+        x, h = ops.dwconv3x3_res_ln(x, d["conv2_w"], d["conv2_b"], pix, d["fn_w"], d["fn_b"], 1e-5)
         h = ops.gemm(h, d["fc1_w"], d["fc1_b"], act=ops.ACT_GELU)
         return ops.gemm(h, d["fc2_w"], d["fc2_b"], residual=x)
 
-    def _spatial(self, x, H, W, C, heads, d, B=1):
+    def _spatial(self, x, lv, C, heads, d):
         ws = self.cfg["window"]
-        x, h = ops.dwconv3x3_res_ln(x, d["conv1_w"], d["conv1_b"], H, W, d["an_w"], d["an_b"], 1e-5, batch=B)
+        x, h = ops.dwconv3x3_res_ln(x, d["conv1_w"], d["conv1_b"], lv["pix"], d["an_w"], d["an_b"], 1e-5)
         if self._window_map(C, heads, ws, d):
             # no partition, no padded rows in the GEMMs, no reverse: the attention finds a window's tokens among the pixel rows by arithmetic, the
             # tokens of the reference's zero padding (:248-251) are the q/k/v bias row, and the residual rides in the proj GEMM's epilogue
             qkv = ops.gemm(h, d["qkv_w"], d["qkv_b"])
-            att = ops.window_attention_map(qkv, C, heads, ws, H, W, B, d["qkv_b"], float(C // heads) ** -0.5)
+            att = ops.window_attention_map(qkv, C, heads, ws, lv["win"], d["qkv_b"], float(C // heads) ** -0.5)
             x = ops.gemm(att, d["proj_w"], d["proj_b"], residual=x)
-            return self._conv_ffn(x, H, W, d, B)
-        hw = ops.window_partition(h, H, W, ws, batch=B)   # zero-padded AFTER the norm, like the reference (:248-251)
+            return self._conv_ffn(x, lv["pix"], d)
+        hw = ops.window_partition(h, lv["win"], ws)   # per image zero-padded AFTER the norm, like the reference (:248-251)
         qkv = ops.gemm(hw, d["qkv_w"], d["qkv_b"])
         att = self._window_attention(qkv, C, heads, ws, x.device)
         y = ops.gemm(att, d["proj_w"], d["proj_b"])
-        x = ops.window_reverse_add(y, x, H, W, ws, batch=B)
-        return self._conv_ffn(x, H, W, d, B)
+        x = ops.window_reverse_add(y, x, lv["win"], ws)
+        return self._conv_ffn(x, lv["pix"], d)
 
-    def _channel(self, x, H, W, C, d, B=1):
-        x, h = ops.dwconv3x3_res_ln(x, d["conv1_w"], d["conv1_b"], H, W, d["an_w"], d["an_b"], 1e-5, batch=B)
+    def _channel(self, x, lv, C, d):
+        x, h = ops.dwconv3x3_res_ln(x, d["conv1_w"], d["conv1_b"], lv["pix"], d["an_w"], d["an_b"], 1e-5)
         qkv = ops.gemm(h, d["qkv_w"], d["qkv_b"])
-        a = ops.channel_attention(qkv, C, batch=B)
+        a = ops.channel_attention(qkv, C, lv["tok"])
         x = ops.gemm(a, d["proj_w"], d["proj_b"], residual=x)
-        return self._conv_ffn(x, H, W, d, B)
+        return self._conv_ffn(x, lv["pix"], d)
+
+    def _stages(self, x, in_sizes, levels, padded):
+        """The four stages over the rows `x` of images of `in_sizes`: levels[i] = stage i's geometry (an iterator: a uniform pass derives a
+        level from the one before), padded(plan) = the zero-framed buffer of an implicit convolution.  -> the stage outputs."""
+        cfg = self.cfg
+        outs, prev_sizes = [], in_sizes
+        for i, (C, lv) in enumerate(zip(cfg["dims"], levels)):
+            cv = self.convs[i]
+            k, s, p = cfg["patch_size"][i], cfg["patch_stride"][i], cfg["patch_padding"][i]
+            prenorm = i > 0 and cfg["patch_prenorm"][i]
+            if prenorm and cv["Kp"] == k * k * x.shape[1] and ops.conv3x3_implicit_for(prev_sizes, s, C, x.shape[1], k, p):
+                # pre-norm ConvEmbed (modeling_davit.py:102-148) as an implicit GEMM: the LayerNorm writes the zero-framed map (one buffer with a
+                # common row pitch for a ragged pack), the 256 x 256 GEMM gathers its 9 taps from it — no [M, 9 Cin] column matrix (same bits as
+                # layernorm + im2col + gemm)
+                cp = ops.conv3x3_plan(prev_sizes, s, x.shape[1], self.dev)
+                assert cp.out_hw == [tuple(t) for t in lv["sizes"]] and cp.M_in == x.shape[0]
+                xp = ops.layernorm_rows(x, cv["nw"], cv["nb"], 1e-5, padded(cp), cp.rowmap)
+                x = ops.conv3x3_gemm(xp, cp, cv["w"], cv["b"])
+            else:
+                if prenorm:
+                    x = ops.layernorm(x, cv["nw"], cv["nb"], 1e-5)
+                x = ops.gemm(ops.im2col(x, lv["conv"], k, k, s, p, ld=cv["Kp"]), cv["w"], cv["b"])
+                if not prenorm:
+                    x = ops.layernorm(x, cv["nw"], cv["nb"], 1e-5)
+            for blk in self.blocks[i]:
+                x = self._spatial(x, lv, C, cfg["heads"][i], blk["spatial_block"])
+                x = self._channel(x, lv, C, blk["channel_block"])
+            outs.append(x)
+            prev_sizes = lv["sizes"]
+        return outs
 
     # ---- ragged batches: images of different sizes in ONE pass (row-wise packing, per-image geometry tables) ------------------------
     def ragged_plan(self, sizes: Sequence[Tuple[int, int]]) -> "RaggedAuxPlan":
@@ -144,106 +177,39 @@ class DaViT:
             pl = plans[key] = RaggedAuxPlan(key, self.cfg, self.dev)
         return pl
 
-    def _conv_ffn_var(self, x, pix, d):
-        x, h = ops.dwconv3x3_res_ln_var(x, d["conv2_w"], d["conv2_b"], pix, d["fn_w"], d["fn_b"], 1e-5)
-        h = ops.gemm(h, d["fc1_w"], d["fc1_b"], act=ops.ACT_GELU)
-        return ops.gemm(h, d["fc2_w"], d["fc2_b"], residual=x)
-
-    def _spatial_var(self, x, lv, C, heads, d):
-        ws = self.cfg["window"]
-        x, h = ops.dwconv3x3_res_ln_var(x, d["conv1_w"], d["conv1_b"], lv["pix"], d["an_w"], d["an_b"], 1e-5)
-        if self._window_map(C, heads, ws, d):
-            qkv = ops.gemm(h, d["qkv_w"], d["qkv_b"])
-            att = ops.window_attention_map_var(qkv, C, heads, ws, lv["win"], d["qkv_b"], float(C // heads) ** -0.5)
-            x = ops.gemm(att, d["proj_w"], d["proj_b"], residual=x)
-            return self._conv_ffn_var(x, lv["pix"], d)
-        hw = ops.window_partition_var(h, lv["win"], ws)         # per image zero-padded AFTER the norm, like the reference (:248-251)
-        qkv = ops.gemm(hw, d["qkv_w"], d["qkv_b"])
-        att = self._window_attention(qkv, C, heads, ws, x.device)
-        y = ops.gemm(att, d["proj_w"], d["proj_b"])
-        x = ops.window_reverse_add_var(y, x, lv["win"], ws)
-        return self._conv_ffn_var(x, lv["pix"], d)
-
-    def _channel_var(self, x, lv, C, d):
-        x, h = ops.dwconv3x3_res_ln_var(x, d["conv1_w"], d["conv1_b"], lv["pix"], d["an_w"], d["an_b"], 1e-5)
-        qkv = ops.gemm(h, d["qkv_w"], d["qkv_b"])
-        a = ops.channel_attention_var(qkv, C, lv["tok"])
-        x = ops.gemm(a, d["proj_w"], d["proj_b"], residual=x)
-        return self._conv_ffn_var(x, lv["pix"], d)
-
     def forward_ragged(self, imgs: Sequence[torch.Tensor]):
         """imgs: [3,H_b,W_b] device tensors of DIFFERENT sizes -> ([4 token-major maps [sum_b H_ib*W_ib, C_i] bf16, image b at rows
         plan.row0[i][b] ...], plan (RaggedAuxPlan: per level sizes[i][b], row0[i][b])).  Same launches as forward(), every GEMM /
         LayerNorm over the rows of ALL images, the spatial kernels per image through the geometry tables: each image's maps are
         bit-identical to its one-image pass when the GEMM tile is pinned (tests/test_ragged_towers_gpu.py).  The reference runs the
         tower image by image (davit_aux_encoder.py:54-69)."""
-        cfg = self.cfg
         plan = self.ragged_plan([tuple(im.shape[-2:]) for im in imgs])
         x = torch.empty(plan.total_in, 8, dtype=torch.bfloat16, device=self.dev)
         for im, r0, (H, W) in zip(imgs, plan.in_row0, plan.in_sizes):
             ops.nchw_to_hwc8(im.contiguous(), out=x[r0:r0 + H * W])
-        outs = []
-        for i, C in enumerate(cfg["dims"]):
-            cv, lv = self.convs[i], plan.levels[i]
-            k, s, p = cfg["patch_size"][i], cfg["patch_stride"][i], cfg["patch_padding"][i]
-            prev_sizes = plan.in_sizes if i == 0 else plan.sizes[i - 1]
-            if i > 0 and cfg["patch_prenorm"][i] and cv["Kp"] == k * k * x.shape[1] and ops.conv3x3_implicit_for(prev_sizes, s, C, x.shape[1], k, p):
-                # pre-norm ConvEmbed as an implicit GEMM over the ragged pack (as forward() does for uniform batches): one zero-framed buffer with a
-                # common row pitch, the same bits as layernorm + im2col_var + gemm without the [M, 9 Cin] column matrix
-                cp = ops.conv3x3_plan(prev_sizes, s, x.shape[1], self.dev)
-                assert cp.out_hw == [tuple(t) for t in plan.sizes[i]] and cp.M_in == x.shape[0]
-                xp = ops.layernorm_rows(x, cv["nw"], cv["nb"], 1e-5, torch.zeros(cp.pad_rows, x.shape[1], dtype=torch.bfloat16, device=self.dev), cp.rowmap)
-                x = ops.conv3x3_gemm(xp, cp, cv["w"], cv["b"])
-            else:
-                if i > 0 and cfg["patch_prenorm"][i]:
-                    x = ops.layernorm(x, cv["nw"], cv["nb"], 1e-5)
-                col = ops.im2col_var(x, lv["conv"], k, k, s, p, ld=cv["Kp"])
-                x = ops.gemm(col, cv["w"], cv["b"])
-                if i == 0 or not cfg["patch_prenorm"][i]:
-                    x = ops.layernorm(x, cv["nw"], cv["nb"], 1e-5)
-            for blk in self.blocks[i]:
-                x = self._spatial_var(x, lv, C, cfg["heads"][i], blk["spatial_block"])
-                x = self._channel_var(x, lv, C, blk["channel_block"])
-            outs.append(x)
+        # (a ragged pack's zero-framed buffer is allocated and filled per call: commit 687aec2)
+        outs = self._stages(x, plan.in_sizes, plan.levels,
+                            lambda cp: torch.zeros(cp.pad_rows, cp.cin, dtype=torch.bfloat16, device=self.dev))
         return outs, plan
+
+    def _uniform_levels(self, g: "ops.Grid"):
+        cfg = self.cfg
+        for i in range(len(cfg["dims"])):
+            prev, g = g, g.conv_out(cfg["patch_size"][i], cfg["patch_size"][i], cfg["patch_stride"][i], cfg["patch_padding"][i])
+            yield dict(conv=prev, pix=g, win=g, tok=g, sizes=g.sizes)
 
     def forward(self, img: torch.Tensor):
         """img [3,H,W] or [B,3,H,W] (device, bf16/fp32, CLIP-normalised; B same-size images in one pass).  Returns
         ([4 token-major maps [B*H_i*W_i, C_i] bf16 — image b at rows [b*H_i*W_i, (b+1)*H_i*W_i)], [(H_i, W_i)])."""
-        cfg = self.cfg
         from . import stage_abi
         if stage_abi.enabled():      # the same launches, sequenced by fo1_davit_forward (csrc/stages.hip)
             return stage_abi.davit_stage(self).forward(img)
         if img.dim() == 3:
             img = img.unsqueeze(0)
-        B = img.shape[0]
-        H, W = img.shape[2:]
-        x = ops.nchw_to_hwc8(img.contiguous())
-        outs, sizes = [], []
-        for i, C in enumerate(cfg["dims"]):
-            cv = self.convs[i]
-            k, s, p = cfg["patch_size"][i], cfg["patch_stride"][i], cfg["patch_padding"][i]
-            Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
-            if i > 0 and cfg["patch_prenorm"][i] and cv["Kp"] == k * k * x.shape[1] and ops.conv3x3_implicit_for(((H, W),) * B, s, C, x.shape[1], k, p):
-                # pre-norm ConvEmbed (modeling_davit.py:102-148) as an implicit GEMM: the LayerNorm writes the zero-padded map, the 256 x 256 GEMM
-                # gathers its 9 taps from it — no [M, 9 Cin] column matrix (same bits as layernorm + im2col + gemm)
-                pl = ops.conv3x3_plan(((H, W),) * B, s, x.shape[1], self.dev)
-                xp = ops.layernorm_rows(x, cv["nw"], cv["nb"], 1e-5, ops.conv3x3_padded(pl, self.dev), pl.rowmap)
-                x = ops.conv3x3_gemm(xp, pl, cv["w"], cv["b"])
-                H, W = Ho, Wo
-            else:
-                if i > 0 and cfg["patch_prenorm"][i]:
-                    x = ops.layernorm(x, cv["nw"], cv["nb"], 1e-5)
-                col, H, W = ops.im2col(x, H, W, k, k, s, p, ld=cv["Kp"], batch=B)
-                x = ops.gemm(col, cv["w"], cv["b"])
-            if i == 0 or not cfg["patch_prenorm"][i]:
-                x = ops.layernorm(x, cv["nw"], cv["nb"], 1e-5)
-            for blk in self.blocks[i]:
-                x = self._spatial(x, H, W, C, cfg["heads"][i], blk["spatial_block"], B)
-                x = self._channel(x, H, W, C, blk["channel_block"], B)
-            outs.append(x)
-            sizes.append((H, W))
-        return outs, sizes
+        g = ops.Grid(img.shape[2], img.shape[3], img.shape[0])
+        levels = list(self._uniform_levels(g))
+        outs = self._stages(ops.nchw_to_hwc8(img.contiguous()), g.sizes, levels, lambda cp: ops.conv3x3_padded(cp, self.dev))
+        return outs, [(lv["pix"].H, lv["pix"].W) for lv in levels]
 
 
 class RaggedAuxPlan:
@@ -281,7 +247,7 @@ class RaggedAuxPlan:
             win = ops.ImgSegs([(r, h, w, wr, a, b) for r, (h, w), wr, (a, b) in zip(r0, cur, wr0, nwin)], device, max(npx), sum(npx),
                               max(a * b * ws * ws for a, b in nwin), woff)
             tok = ops.ImgSegs([(r, n) for r, n in zip(r0, npx)], device, max(npx), sum(npx), max(npx), sum(npx))
-            self.levels.append(dict(conv=conv, pix=pix, win=win, tok=tok))
+            self.levels.append(dict(conv=conv, pix=pix, win=win, tok=tok, sizes=cur))
             self.sizes.append(cur)
             self.row0.append(r0)
             prev_sizes, prev_row0 = cur, r0

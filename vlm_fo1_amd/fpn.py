@@ -45,24 +45,38 @@ class SimpleFPN:
                 w1=conv1(s[f"{name}.{a}weight"]), n1=(dv(s[f"{name}.{a}norm.weight"]), dv(s[f"{name}.{a}norm.bias"])),
                 w3=conv3(s[f"{name}.{b}weight"]), n3=(dv(s[f"{name}.{b}norm.weight"]), dv(s[f"{name}.{b}norm.bias"]))))
 
-    def _up(self, x, H, W, t, B=1):
+    # The geometry of a pass, `pl`: up_1a / up_1b (grid -> 2x -> 4x), pool (grid -> 1/2), conv[l] and sizes[l] of the four output levels.  A
+    # ragged pass has a RaggedFpnPlan of ops.ImgSegs tables, a uniform pass the ops.Grid of each (_uniform_plan).
+    def _up(self, x, geom, t):
         w, b, cout = t
-        return ops.pixel_shuffle2(ops.gemm(x, w, b), H, W, cout, batch=B), 2 * H, 2 * W
+        return ops.pixel_shuffle2(ops.gemm(x, w, b), geom, cout)
 
-    def _head(self, x, H, W, h, B=1):
+    def _head(self, x, geom, sizes, h, padded):
         y = ops.gemm(x, h["w1"])
         C = y.shape[1]
-        if ops.conv3x3_implicit_for(((H, W),) * B, 1, h["w3"].shape[0], C, 3, 1):
-            # the 3x3 output convolution (simple_fpn.py:141-176) as an implicit GEMM: the channel LayerNorm writes the zero-padded map, the GEMM
-            # gathers its taps from it (no im2col matrix: 2.2 GB per launch at the finest level); same bits as layernorm + im2col + gemm
-            pl = ops.conv3x3_plan(((H, W),) * B, 1, C, y.device)
-            yp = ops.layernorm_rows(y, h["n1"][0], h["n1"][1], 1e-6, ops.conv3x3_padded(pl, y.device), pl.rowmap)
-            y = ops.conv3x3_gemm(yp, pl, h["w3"])
+        if ops.conv3x3_implicit_for(sizes, 1, h["w3"].shape[0], C, 3, 1):
+            # the 3x3 output convolution (simple_fpn.py:141-176) as an implicit GEMM: the channel LayerNorm writes the zero-framed map (a ragged
+            # pack's levels are packed back to back, image by image: RaggedFpnPlan), the GEMM gathers its taps from it (no im2col matrix: 2.2 GB
+            # per launch at the finest level); same bits as layernorm + im2col + gemm
+            cp = ops.conv3x3_plan(sizes, 1, C, y.device)
+            assert cp.M_in == y.shape[0]
+            yp = ops.layernorm_rows(y, h["n1"][0], h["n1"][1], 1e-6, padded(cp), cp.rowmap)
+            y = ops.conv3x3_gemm(yp, cp, h["w3"])
         else:
             y = ops.layernorm(y, h["n1"][0], h["n1"][1], 1e-6)
-            col, _, _ = ops.im2col(y, H, W, 3, 3, 1, 1, batch=B)
-            y = ops.gemm(col, h["w3"])
+            y = ops.gemm(ops.im2col(y, geom, 3, 3, 1, 1), h["w3"])
         return ops.layernorm(y, h["n3"][0], h["n3"][1], 1e-6)
+
+    def _levels(self, x, pl, padded):
+        """The four output maps of the rows `x`; padded(plan) = the zero-framed buffer of an implicit convolution."""
+        y = self._up(x, pl.up_1a, self.t1a)
+        y = ops.layernorm(y, self.t1_ln[0], self.t1_ln[1], 1e-6)
+        y = ops.bias_act(y, None, 1)
+
+        def head(l, y):
+            return self._head(y, pl.conv[l], pl.sizes[l], self.heads[l], padded)
+
+        return [head(0, self._up(y, pl.up_1b, self.t1b)), head(1, self._up(x, pl.up_1a, self.t2)), head(2, x), head(3, ops.maxpool2(x, pl.pool))]
 
     # ---- ragged batches: maps of different grids packed row-wise ----------------------------------------------------------------
     def ragged_plan(self, grids, row0) -> "RaggedFpnPlan":
@@ -75,62 +89,27 @@ class SimpleFPN:
             pl = plans[key] = RaggedFpnPlan(key[0], key[1], self.dev)
         return pl
 
-    def _head_var(self, x, sg, h, sizes):
-        y = ops.gemm(x, h["w1"])
-        C = y.shape[1]
-        if ops.conv3x3_implicit_for(sizes, 1, h["w3"].shape[0], C, 3, 1):
-            # the 3x3 output convolution as an implicit GEMM over the ragged pack (levels are packed back to back, image by image: RaggedFpnPlan)
-            cp = ops.conv3x3_plan(sizes, 1, C, y.device)
-            assert cp.M_in == y.shape[0]
-            yp = ops.layernorm_rows(y, h["n1"][0], h["n1"][1], 1e-6, torch.zeros(cp.pad_rows, C, dtype=torch.bfloat16, device=y.device), cp.rowmap)
-            y = ops.conv3x3_gemm(yp, cp, h["w3"])
-        else:
-            y = ops.layernorm(y, h["n1"][0], h["n1"][1], 1e-6)
-            col = ops.im2col_var(y, sg, 3, 3, 1, 1)
-            y = ops.gemm(col, h["w3"])
-        return ops.layernorm(y, h["n3"][0], h["n3"][1], 1e-6)
-
     def forward_ragged(self, x: torch.Tensor, grids, row0):
         """x [sum gh_b*gw_b, 1280] token-major raster maps of images with DIFFERENT grids (image b at rows row0[b]...) -> (4 maps
         [sum .., 512], plan with sizes[l][b] / row0[l][b]).  Same launches as forward(); every image bit-identical to its own pass."""
         pl = self.ragged_plan(grids, row0)
+        # (a ragged pack's zero-framed buffer is allocated and filled per call: commit 687aec2)
+        return self._levels(x, pl, lambda cp: torch.zeros(cp.pad_rows, cp.cin, dtype=torch.bfloat16, device=x.device)), pl
 
-        def up(y, sg, t):
-            w, b, cout = t
-            return ops.pixel_shuffle2_var(ops.gemm(y, w, b), sg, cout)
-
-        outs = []
-        y = up(x, pl.up_1a, self.t1a)
-        y = ops.layernorm(y, self.t1_ln[0], self.t1_ln[1], 1e-6)
-        y = ops.bias_act(y, None, 1)
-        y = up(y, pl.up_1b, self.t1b)
-        outs.append(self._head_var(y, pl.conv[0], self.heads[0], pl.sizes[0]))
-        y = up(x, pl.up_1a, self.t2)
-        outs.append(self._head_var(y, pl.conv[1], self.heads[1], pl.sizes[1]))
-        outs.append(self._head_var(x, pl.conv[2], self.heads[2], pl.sizes[2]))
-        y = ops.maxpool2_var(x, pl.pool)
-        outs.append(self._head_var(y, pl.conv[3], self.heads[3], pl.sizes[3]))
-        return outs, pl
+    @staticmethod
+    def _uniform_plan(g: "ops.Grid"):
+        from types import SimpleNamespace
+        conv = [g.scaled(4), g.scaled(2), g, g.scaled(1, 2)]
+        return SimpleNamespace(up_1a=g, up_1b=g.scaled(2), pool=g, conv=conv, sizes=[c.sizes for c in conv])
 
     def forward(self, x: torch.Tensor, H: int, W: int, batch: int = 1) -> Tuple[List[torch.Tensor], List[Tuple[int, int]]]:
         """x [batch*H*W, 1280] token-major bf16 (same-size maps stacked) -> 4 token-major maps [batch*.., 512] at (4H,4W),
         (2H,2W), (H,W), (H/2,W/2); image b owns rows [b*h*w, (b+1)*h*w) of every level."""
-        B = batch
         from . import stage_abi
         if stage_abi.enabled():      # the same launches, sequenced by fo1_simplefpn_forward (csrc/stages.hip)
-            return stage_abi.fpn_stage(self).forward(x, H, W, B)
-        outs, sizes = [], []
-        y, h1, w1 = self._up(x, H, W, self.t1a, B)
-        y = ops.layernorm(y, self.t1_ln[0], self.t1_ln[1], 1e-6)
-        y = ops.bias_act(y, None, 1)
-        y, h1, w1 = self._up(y, h1, w1, self.t1b, B)
-        outs.append(self._head(y, h1, w1, self.heads[0], B)); sizes.append((h1, w1))
-        y, h2, w2 = self._up(x, H, W, self.t2, B)
-        outs.append(self._head(y, h2, w2, self.heads[1], B)); sizes.append((h2, w2))
-        outs.append(self._head(x, H, W, self.heads[2], B)); sizes.append((H, W))
-        y = ops.maxpool2(x, H, W, batch=B)
-        outs.append(self._head(y, H // 2, W // 2, self.heads[3], B)); sizes.append((H // 2, W // 2))
-        return outs, sizes
+            return stage_abi.fpn_stage(self).forward(x, H, W, batch)
+        pl = self._uniform_plan(ops.Grid(H, W, batch))
+        return self._levels(x, pl, lambda cp: ops.conv3x3_padded(cp, x.device)), [(c.H, c.W) for c in pl.conv]
 
 
 class RaggedFpnPlan:

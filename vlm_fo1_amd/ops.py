@@ -1087,7 +1087,79 @@ def attention_windows(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, items:
 
 
 # ---- DaViT / SimpleFPN / splice helpers -----------------------------------------------------
-# Every spatial op takes `batch`: that many same-size images stacked along the row dimension ([batch*H*W, C]).
+# Every spatial op takes the geometry of its batch: a Grid (same-size images stacked along the rows, the `_bf16` entry) or an ImgSegs
+# (images of different sizes packed row-wise, the `_var_bf16` entry reading a device table).  Both answer what a front end needs.
+class Grid:
+    """`batch` images of H x W pixels (or tokens) stacked along the row dimension ([batch*H*W, C]).  Host arithmetic only."""
+    ragged = False
+
+    def __init__(self, H: int, W: int, batch: int = 1):
+        self.H, self.W, self.batch = int(H), int(W), int(batch)
+        self.n, self.max_in, self.total_in = self.batch, self.H * self.W, self.batch * self.H * self.W
+
+    @property
+    def sizes(self):
+        return ((self.H, self.W),) * self.batch
+
+    def conv_out(self, KH: int, KW: int, stride: int, pad: int) -> "Grid":
+        return Grid((self.H + 2 * pad - KH) // stride + 1, (self.W + 2 * pad - KW) // stride + 1, self.batch)
+
+    def scaled(self, num: int, den: int = 1) -> "Grid":
+        """The grid of a 2x transposed convolution (2) or of a 2 x 2 max-pool (1, 2)."""
+        return Grid(self.H * num // den, self.W * num // den, self.batch)
+
+    def windows(self, ws: int) -> "Grid":
+        """Padded to whole ws x ws windows."""
+        return Grid(-(-self.H // ws) * ws, -(-self.W // ws) * ws, self.batch)
+
+    def rows_out(self, out_grid) -> int:
+        return out_grid(self).total_in
+
+    def args(self, side: str, *mid):
+        """The geometry arguments of a uniform entry, around the operator's own `mid`."""
+        return (self.H, self.W, *mid, self.batch)
+
+
+class ImgSegs:
+    """Per-operator geometry table of a ragged batch: host rows [(in_row0, H, W, out_row0, Ho, Wo)] -> device int32 [n, 8] + the sizes
+    the launch needs (largest image, totals).  Built once per batch signature (the tower plans cache them).  include/fo1.h fo1_img_seg."""
+    ragged = True
+
+    def __init__(self, rows, device, max_in: int, total_in: int, max_out: int, total_out: int):
+        t = torch.zeros(len(rows), 8, dtype=torch.int32)
+        for i, r in enumerate(rows):
+            t[i, :len(r)] = torch.tensor(r, dtype=torch.int32)
+        self.dev = t.to(device)
+        self.n = len(rows)
+        self.max_in, self.total_in, self.max_out, self.total_out = int(max_in), int(total_in), int(max_out), int(total_out)
+
+    @property
+    def ptr(self):
+        return self.dev.data_ptr()
+
+    def rows_out(self, out_grid) -> int:
+        return self.total_out
+
+    def args(self, side: str, *mid):
+        """The geometry arguments of a ragged entry; `side` says whether it sizes its grid by the input or the output extents."""
+        return (self.ptr, self.n, getattr(self, "max_" + side), getattr(self, "total_" + side), *mid)
+
+
+def _packed(t: torch.Tensor, name: str, rows: int) -> None:
+    _chk(t, name)
+    assert t.is_contiguous() and t.shape[0] == rows, f"{name}: need {rows} contiguous rows, got shape {tuple(t.shape)} strides {t.stride()}"
+
+
+def _new_rows(rows: int, cols: int, device, zero: bool = False) -> torch.Tensor:
+    return (torch.zeros if zero else torch.empty)(rows, cols, dtype=torch.bfloat16, device=device)
+
+
+def _spatial(entry: str, geom, head, geo_args, tail=()) -> None:
+    """Launch the uniform (`<entry>_bf16`) or the ragged (`<entry>_var_bf16`) form of a spatial operator."""
+    name = entry + ("_var_bf16" if geom.ragged else "_bf16")
+    _L.check(getattr(_L.load(), name)(*head, *geo_args, *tail, _stream()), name)
+
+
 def dwconv3x3_res(x: torch.Tensor, w9c: torch.Tensor, bias: torch.Tensor, H: int, W: int, batch: int = 1) -> torch.Tensor:
     """x [batch*H*W, C] token-major -> x + dwconv3x3(x) (+bias); w9c is the [9, C] tap-major weight."""
     _chk(x, "x"); _chk(w9c, "w9c"); _chk(bias, "bias")
@@ -1098,48 +1170,39 @@ def dwconv3x3_res(x: torch.Tensor, w9c: torch.Tensor, bias: torch.Tensor, H: int
     return y
 
 
-def dwconv3x3_res_ln(x: torch.Tensor, w9c: torch.Tensor, bias: torch.Tensor, H: int, W: int, ln_w: torch.Tensor, ln_b: torch.Tensor,
-                     eps: float, batch: int = 1):
-    """-> (y = x + dwconv3x3(x) + bias, LayerNorm(y)) in one launch (fo1_dwconv3x3_ln_bf16), bit-identical to
+def dwconv3x3_res_ln(x: torch.Tensor, w9c: torch.Tensor, bias: torch.Tensor, geom, ln_w: torch.Tensor, ln_b: torch.Tensor, eps: float):
+    """-> (y = x + dwconv3x3(x) + bias, LayerNorm(y)) in one launch (fo1_dwconv3x3_ln[_var]_bf16), bit-identical to
     dwconv3x3_res followed by layernorm."""
-    _chk(x, "x"); _chk(w9c, "w9c"); _chk(bias, "bias"); _chk(ln_w, "ln_w"); _chk(ln_b, "ln_b")
-    assert x.is_contiguous() and x.shape[0] == batch * H * W and w9c.shape == (9, x.shape[1]) and w9c.is_contiguous()
+    _packed(x, "x", geom.total_in); _chk(w9c, "w9c"); _chk(bias, "bias"); _chk(ln_w, "ln_w"); _chk(ln_b, "ln_b")
+    assert w9c.shape == (9, x.shape[1]) and w9c.is_contiguous()
     y, h = torch.empty_like(x), torch.empty_like(x)
-    _L.check(_L.load().fo1_dwconv3x3_ln_bf16(x.data_ptr(), w9c.data_ptr(), bias.data_ptr(), y.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(),
-                                             float(eps), h.data_ptr(), H, W, x.shape[1], batch, _stream()), "fo1_dwconv3x3_ln_bf16")
+    _spatial("fo1_dwconv3x3_ln", geom, (x.data_ptr(), w9c.data_ptr(), bias.data_ptr(), y.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), float(eps),
+                                        h.data_ptr()), geom.args("in", x.shape[1]))
     return y, h
 
 
-def im2col(x: torch.Tensor, H: int, W: int, KH: int, KW: int, stride: int, pad: int, ld: Optional[int] = None, batch: int = 1):
-    """x [batch*H*W, C] -> (col [batch*Ho*Wo, ld>=KH*KW*C] (pad columns zero), Ho, Wo)."""
-    _chk(x, "x")
-    assert x.is_contiguous() and x.shape[0] == batch * H * W
+def im2col(x: torch.Tensor, geom, KH: int, KW: int, stride: int, pad: int, ld: Optional[int] = None) -> torch.Tensor:
+    """x [rows of geom, C] -> col [output pixels, ld>=KH*KW*C] (pad columns zero); a Grid's output grid is geom.conv_out(KH, KW, stride, pad)."""
+    _packed(x, "x", geom.total_in)
     C = x.shape[1]
-    Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
     K = KH * KW * C
     ld = ld or K
-    col = torch.zeros(batch * Ho * Wo, ld, dtype=torch.bfloat16, device=x.device) if ld != K else \
-        torch.empty(batch * Ho * Wo, ld, dtype=torch.bfloat16, device=x.device)
-    _L.check(_L.load().fo1_im2col_bf16(x.data_ptr(), col.data_ptr(), H, W, C, KH, KW, stride, pad, ld, batch, _stream()), "fo1_im2col_bf16")
-    return col, Ho, Wo
+    col = _new_rows(geom.rows_out(lambda g: g.conv_out(KH, KW, stride, pad)), ld, x.device, zero=ld != K)
+    _spatial("fo1_im2col", geom, (x.data_ptr(), col.data_ptr()), geom.args("out", C, KH, KW, stride, pad, ld))
+    return col
 
 
-def window_partition(x: torch.Tensor, H: int, W: int, ws: int, batch: int = 1) -> torch.Tensor:
-    _chk(x, "x")
-    assert x.is_contiguous() and x.shape[0] == batch * H * W
-    nW = ((H + ws - 1) // ws) * ((W + ws - 1) // ws)
-    xw = torch.empty(batch * nW * ws * ws, x.shape[1], dtype=torch.bfloat16, device=x.device)
-    _L.check(_L.load().fo1_window_partition_bf16(x.data_ptr(), xw.data_ptr(), H, W, x.shape[1], ws, batch, _stream()),
-             "fo1_window_partition_bf16")
+def window_partition(x: torch.Tensor, geom, ws: int) -> torch.Tensor:
+    _packed(x, "x", geom.total_in)
+    xw = _new_rows(geom.rows_out(lambda g: g.windows(ws)), x.shape[1], x.device)
+    _spatial("fo1_window_partition", geom, (x.data_ptr(), xw.data_ptr()), geom.args("out", x.shape[1], ws))
     return xw
 
 
-def window_reverse_add(yw: torch.Tensor, shortcut: torch.Tensor, H: int, W: int, ws: int, batch: int = 1) -> torch.Tensor:
-    _chk(yw, "yw"); _chk(shortcut, "shortcut")
-    assert yw.is_contiguous() and shortcut.is_contiguous() and shortcut.shape[0] == batch * H * W
+def window_reverse_add(yw: torch.Tensor, shortcut: torch.Tensor, geom, ws: int) -> torch.Tensor:
+    _packed(yw, "yw", geom.rows_out(lambda g: g.windows(ws))); _packed(shortcut, "shortcut", geom.total_in)
     y = torch.empty_like(shortcut)
-    _L.check(_L.load().fo1_window_reverse_add_bf16(yw.data_ptr(), shortcut.data_ptr(), y.data_ptr(), H, W, shortcut.shape[1], ws, batch,
-                                                   _stream()), "fo1_window_reverse_add_bf16")
+    _spatial("fo1_window_reverse_add", geom, (yw.data_ptr(), shortcut.data_ptr(), y.data_ptr()), geom.args("in", shortcut.shape[1], ws))
     return y
 
 
@@ -1161,149 +1224,47 @@ def window_attention(qkv: torch.Tensor, C: int, n_heads: int, window_tokens: int
 WINDOW_ATTENTION_MAP_WINDOW = 12       # fo1_window_attention_map_bf16: the window side its token -> pixel arithmetic is built for
 
 
-def window_attention_map(qkv: torch.Tensor, C: int, n_heads: int, window: int, H: int, W: int, batch: int, pad_row: torch.Tensor, scale: float,
+def window_attention_map(qkv: torch.Tensor, C: int, n_heads: int, window: int, geom, pad_row: torch.Tensor, scale: float,
                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Window attention on UN-partitioned rows: qkv [batch * H * W, 3C] = the q/k/v projection of the images' pixels in raster order; the windows'
+    """Window attention on UN-partitioned rows: qkv [rows of geom, 3C] = the q/k/v projection of the images' pixels in raster order; the windows'
     tokens are found by arithmetic, tokens outside the image read `pad_row` (the layer's bf16 q/k/v bias = the projection of the reference's zero
-    padding, modeling_davit.py:248-251).  -> [batch * H * W, C] in pixel order (fo1_window_attention_map_bf16)."""
+    padding, modeling_davit.py:248-251).  -> [rows, C] in pixel order (fo1_window_attention_map[_var]_bf16; a ragged geom is the
+    window-partition table: pixels row0, H, W, -, windows down / across)."""
     _chk(qkv, "qkv"); _chk(pad_row, "pad_row")
     p, ld, n, _ = _rows(qkv, "qkv")
-    assert C == n_heads * 32 and n == batch * H * W and window == WINDOW_ATTENTION_MAP_WINDOW and pad_row.numel() == 3 * C and pad_row.is_contiguous()
+    assert C == n_heads * 32 and n == geom.total_in and window == WINDOW_ATTENTION_MAP_WINDOW and pad_row.numel() == 3 * C and pad_row.is_contiguous()
     out = _out_rows(out, n, C, qkv.device)
-    _L.check(_L.load().fo1_window_attention_map_bf16(p, ld, C, n_heads, window, H, W, batch, pad_row.data_ptr(), out.data_ptr(), out.stride(0), float(scale), _stream()),
-             "fo1_window_attention_map_bf16")
+    geo = (geom.ptr, geom.n, geom.max_out // (window * window), geom.total_in) if geom.ragged else geom.args("in")
+    _spatial("fo1_window_attention_map", geom, (p, ld, C, n_heads, window), geo, (pad_row.data_ptr(), out.data_ptr(), out.stride(0), float(scale)))
     return out
 
 
-def window_attention_map_var(qkv: torch.Tensor, C: int, n_heads: int, window: int, sg: "ImgSegs", pad_row: torch.Tensor, scale: float,
-                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """window_attention_map for images of different sizes (sg = the window-partition geometry table: pixels row0, H, W, -, windows down / across)."""
-    _chk(qkv, "qkv"); _chk(pad_row, "pad_row")
-    p, ld, n, _ = _rows(qkv, "qkv")
-    assert C == n_heads * 32 and n == sg.total_in and window == WINDOW_ATTENTION_MAP_WINDOW and pad_row.numel() == 3 * C and pad_row.is_contiguous()
-    out = _out_rows(out, n, C, qkv.device)
-    _L.check(_L.load().fo1_window_attention_map_var_bf16(p, ld, C, n_heads, window, sg.ptr, sg.n, sg.max_out // (window * window), sg.total_in,
-                                                         pad_row.data_ptr(), out.data_ptr(), out.stride(0), float(scale), _stream()), "fo1_window_attention_map_var_bf16")
-    return out
-
-
-def channel_attention(qkv: torch.Tensor, C: int, batch: int = 1) -> torch.Tensor:
-    """qkv [batch*N, 3C]: per image, per 32-channel group attention over the image's own N tokens."""
+def channel_attention(qkv: torch.Tensor, C: int, geom) -> torch.Tensor:
+    """qkv [rows of geom, 3C]: per image, per 32-channel group attention over the image's own tokens (a Grid's H * W; a ragged geom's rows
+    are (row0, N_i))."""
     _chk(qkv, "qkv")
     p, ld, NB, _ = _rows(qkv, "qkv")
-    assert NB % batch == 0 and (batch == 1 or qkv.is_contiguous() or qkv.stride(0) == ld)
-    N = NB // batch
-    need = _L.load().fo1_channel_attention_workspace_bytes(N, C, batch)
+    assert NB == geom.total_in
+    need = _L.load().fo1_channel_attention_workspace_bytes(geom.max_in, C, geom.n)
     ws = _workspace("channel_attention", qkv.device, need)
-    out = torch.empty(NB, C, dtype=torch.bfloat16, device=qkv.device)
-    _L.check(_L.load().fo1_channel_attention_bf16(p, ld, N, C, out.data_ptr(), C, batch, ws.data_ptr(), ws.numel(), _stream()),
-             "fo1_channel_attention_bf16")
+    out = _new_rows(NB, C, qkv.device)
+    geo = (geom.ptr, geom.n, geom.max_in, geom.total_in, C, out.data_ptr(), C) if geom.ragged else (geom.max_in, C, out.data_ptr(), C, geom.n)
+    _spatial("fo1_channel_attention", geom, (p, ld), geo, (ws.data_ptr(), ws.numel()))
     return out
 
 
-def pixel_shuffle2(src: torch.Tensor, H: int, W: int, Co: int, batch: int = 1) -> torch.Tensor:
-    _chk(src, "src")
-    assert src.is_contiguous() and src.shape == (batch * H * W, 4 * Co)
-    dst = torch.empty(batch * 4 * H * W, Co, dtype=torch.bfloat16, device=src.device)
-    _L.check(_L.load().fo1_pixel_shuffle2_bf16(src.data_ptr(), dst.data_ptr(), H, W, Co, batch, _stream()), "fo1_pixel_shuffle2_bf16")
+def pixel_shuffle2(src: torch.Tensor, geom, Co: int) -> torch.Tensor:
+    _packed(src, "src", geom.total_in)
+    assert src.shape[1] == 4 * Co
+    dst = _new_rows(geom.rows_out(lambda g: g.scaled(2)), Co, src.device)
+    _spatial("fo1_pixel_shuffle2", geom, (src.data_ptr(), dst.data_ptr()), geom.args("in", Co))
     return dst
 
 
-def maxpool2(x: torch.Tensor, H: int, W: int, batch: int = 1) -> torch.Tensor:
-    _chk(x, "x")
-    assert x.is_contiguous() and x.shape[0] == batch * H * W
-    y = torch.empty(batch * (H // 2) * (W // 2), x.shape[1], dtype=torch.bfloat16, device=x.device)
-    _L.check(_L.load().fo1_maxpool2_bf16(x.data_ptr(), y.data_ptr(), H, W, x.shape[1], batch, _stream()), "fo1_maxpool2_bf16")
-    return y
-
-
-# ---- ragged image batches: images of different sizes packed row-wise (include/fo1.h fo1_img_seg) ---------------------------------
-class ImgSegs:
-    """Per-operator geometry table of a ragged batch: host rows [(in_row0, H, W, out_row0, Ho, Wo)] -> device int32 [n, 8] + the sizes
-    the launch needs (largest image, totals).  Built once per batch signature (the tower plans cache them)."""
-
-    def __init__(self, rows, device, max_in: int, total_in: int, max_out: int, total_out: int):
-        t = torch.zeros(len(rows), 8, dtype=torch.int32)
-        for i, r in enumerate(rows):
-            t[i, :len(r)] = torch.tensor(r, dtype=torch.int32)
-        self.dev = t.to(device)
-        self.n = len(rows)
-        self.max_in, self.total_in, self.max_out, self.total_out = int(max_in), int(total_in), int(max_out), int(total_out)
-
-    @property
-    def ptr(self):
-        return self.dev.data_ptr()
-
-
-def dwconv3x3_res_ln_var(x: torch.Tensor, w9c: torch.Tensor, bias: torch.Tensor, sg: ImgSegs, ln_w: torch.Tensor, ln_b: torch.Tensor, eps: float):
-    _chk(x, "x"); _chk(w9c, "w9c"); _chk(bias, "bias"); _chk(ln_w, "ln_w"); _chk(ln_b, "ln_b")
-    assert x.is_contiguous() and x.shape[0] == sg.total_in and w9c.shape == (9, x.shape[1]) and w9c.is_contiguous()
-    y, h = torch.empty_like(x), torch.empty_like(x)
-    _L.check(_L.load().fo1_dwconv3x3_ln_var_bf16(x.data_ptr(), w9c.data_ptr(), bias.data_ptr(), y.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(),
-                                                 float(eps), h.data_ptr(), sg.ptr, sg.n, sg.max_in, sg.total_in, x.shape[1], _stream()),
-             "fo1_dwconv3x3_ln_var_bf16")
-    return y, h
-
-
-def im2col_var(x: torch.Tensor, sg: ImgSegs, KH: int, KW: int, stride: int, pad: int, ld: Optional[int] = None) -> torch.Tensor:
-    _chk(x, "x")
-    assert x.is_contiguous() and x.shape[0] == sg.total_in
-    C = x.shape[1]
-    K = KH * KW * C
-    ld = ld or K
-    col = torch.zeros(sg.total_out, ld, dtype=torch.bfloat16, device=x.device) if ld != K else \
-        torch.empty(sg.total_out, ld, dtype=torch.bfloat16, device=x.device)
-    _L.check(_L.load().fo1_im2col_var_bf16(x.data_ptr(), col.data_ptr(), sg.ptr, sg.n, sg.max_out, sg.total_out, C, KH, KW, stride, pad, ld, _stream()),
-             "fo1_im2col_var_bf16")
-    return col
-
-
-def window_partition_var(x: torch.Tensor, sg: ImgSegs, ws: int) -> torch.Tensor:
-    _chk(x, "x")
-    assert x.is_contiguous() and x.shape[0] == sg.total_in
-    xw = torch.empty(sg.total_out, x.shape[1], dtype=torch.bfloat16, device=x.device)
-    _L.check(_L.load().fo1_window_partition_var_bf16(x.data_ptr(), xw.data_ptr(), sg.ptr, sg.n, sg.max_out, sg.total_out, x.shape[1], ws, _stream()),
-             "fo1_window_partition_var_bf16")
-    return xw
-
-
-def window_reverse_add_var(yw: torch.Tensor, shortcut: torch.Tensor, sg: ImgSegs, ws: int) -> torch.Tensor:
-    _chk(yw, "yw"); _chk(shortcut, "shortcut")
-    assert yw.is_contiguous() and shortcut.is_contiguous() and shortcut.shape[0] == sg.total_in and yw.shape[0] == sg.total_out
-    y = torch.empty_like(shortcut)
-    _L.check(_L.load().fo1_window_reverse_add_var_bf16(yw.data_ptr(), shortcut.data_ptr(), y.data_ptr(), sg.ptr, sg.n, sg.max_in, sg.total_in,
-                                                       shortcut.shape[1], ws, _stream()), "fo1_window_reverse_add_var_bf16")
-    return y
-
-
-def channel_attention_var(qkv: torch.Tensor, C: int, sg: ImgSegs) -> torch.Tensor:
-    """qkv [sum N_i, 3C]: per image, per 32-channel group attention over the image's own N_i tokens (sg rows: (row0, N_i))."""
-    _chk(qkv, "qkv")
-    p, ld, NB, _ = _rows(qkv, "qkv")
-    assert NB == sg.total_in
-    need = _L.load().fo1_channel_attention_var_workspace_bytes(sg.max_in, C, sg.n)
-    ws = _workspace("channel_attention", qkv.device, need)
-    out = torch.empty(NB, C, dtype=torch.bfloat16, device=qkv.device)
-    _L.check(_L.load().fo1_channel_attention_var_bf16(p, ld, sg.ptr, sg.n, sg.max_in, sg.total_in, C, out.data_ptr(), C, ws.data_ptr(), ws.numel(),
-                                                      _stream()), "fo1_channel_attention_var_bf16")
-    return out
-
-
-def pixel_shuffle2_var(src: torch.Tensor, sg: ImgSegs, Co: int) -> torch.Tensor:
-    _chk(src, "src")
-    assert src.is_contiguous() and src.shape == (sg.total_in, 4 * Co)
-    dst = torch.empty(sg.total_out, Co, dtype=torch.bfloat16, device=src.device)
-    _L.check(_L.load().fo1_pixel_shuffle2_var_bf16(src.data_ptr(), dst.data_ptr(), sg.ptr, sg.n, sg.max_in, sg.total_in, Co, _stream()),
-             "fo1_pixel_shuffle2_var_bf16")
-    return dst
-
-
-def maxpool2_var(x: torch.Tensor, sg: ImgSegs) -> torch.Tensor:
-    _chk(x, "x")
-    assert x.is_contiguous() and x.shape[0] == sg.total_in
-    y = torch.empty(sg.total_out, x.shape[1], dtype=torch.bfloat16, device=x.device)
-    _L.check(_L.load().fo1_maxpool2_var_bf16(x.data_ptr(), y.data_ptr(), sg.ptr, sg.n, sg.max_out, sg.total_out, x.shape[1], _stream()),
-             "fo1_maxpool2_var_bf16")
+def maxpool2(x: torch.Tensor, geom) -> torch.Tensor:
+    _packed(x, "x", geom.total_in)
+    y = _new_rows(geom.rows_out(lambda g: g.scaled(1, 2)), x.shape[1], x.device)
+    _spatial("fo1_maxpool2", geom, (x.data_ptr(), y.data_ptr()), geom.args("out", x.shape[1]))
     return y
 
 

@@ -360,7 +360,8 @@ class SwinBackbone:
             pad[:, :H, :W].copy_(img)
             img = pad
         x = ops.nchw_to_hwc8(img.contiguous())
-        col, H, W = ops.im2col(x, Hp, Wp, 4, 4, 4, 0)
+        H, W = Hp // 4, Wp // 4
+        col = ops.im2col(x, ops.Grid(Hp, Wp), 4, 4, 4, 0)
         x = ops.layernorm(ops.gemm(col, self.pe_w, self.pe_b), self.pe_n[0], self.pe_n[1], 1e-5)
         feats, sizes = [], []
         C = self.C0
@@ -422,7 +423,8 @@ class InputProjection:
         for l in range(len(feats), self.n_levels):
             pr = self.proj[l]
             inp, (H, W) = (feats[-1], sizes[-1]) if l == len(feats) else (srcs[-1], shapes[-1])
-            col, Ho, Wo = ops.im2col(inp, H, W, 3, 3, 2, 1)
+            g = ops.Grid(H, W)
+            col, (Ho, Wo) = ops.im2col(inp, g, 3, 3, 2, 1), g.conv_out(3, 3, 2, 1).sizes[0]
             srcs.append(ops.groupnorm_tokens(ops.gemm(col, pr["w"], pr["b"]), self.groups, pr["gw"], pr["gb"], 1e-5))
             shapes.append((Ho, Wo))
         key = tuple(shapes)
