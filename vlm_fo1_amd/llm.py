@@ -178,7 +178,7 @@ class QwenLLM:
         self.rope_cos, self.rope_sin = cos_t.to(self.dev), sin_t.to(self.dev)
         self.dstate = torch.zeros(8, dtype=torch.int32, device=self.dev)       # [pos, rope_row, -, -, item(4)]
         self.dplan = torch.zeros(1, 2, dtype=torch.int32, device=self.dev)     # gather plan of the one new token: (0, token id)
-        self._dgraph = None
+        self._dgraph = {}           # head (sampled?) -> (hipGraph, logits); emptied whenever the caches or the rope tables move
         self._dstate_keep = None
         self._sampled = False       # sampled head of the single-sequence step (set_sampling)
         self._sbuf = None
@@ -206,7 +206,7 @@ class QwenLLM:
         # (the text-position rope table is NOT grown here: the prefill does not read it — packed passes bring their own tables — and a
         # worker thread's reserve() must not re-allocate a table that the decode pool's graphs, replaying on another stream, still read
         # (ADVICE r4).  The decode paths grow it when THEY need the rows: _check_room, BatchDecoder._ensure, DecodePool.)
-        self._dgraph = None
+        self._dgraph = {}
         self._item_cache = {}
         self.cache_epoch += 1
         torch.cuda.current_stream().synchronize()
@@ -225,7 +225,7 @@ class QwenLLM:
         # stream, and nothing here can wait for it (the epoch / data_ptr graph keys only protect the NEXT capture)
         self._rope_retired.append((self.rope_cos, self.rope_sin))
         self.rope_cos, self.rope_sin = cos_t.to(self.dev), sin_t.to(self.dev)
-        self._dgraph = None
+        self._dgraph = {}
         self.rope_epoch += 1
 
     def replica(self) -> "QwenLLM":
@@ -240,7 +240,7 @@ class QwenLLM:
         r.rope_delta = 0
         r.dstate = torch.zeros_like(self.dstate)
         r.dplan = torch.zeros_like(self.dplan)
-        r._dgraph = None
+        r._dgraph = {}
         r._dstate_keep = None
         r._sampled, r._sbuf = False, None
         r._item_cache = {}
@@ -624,32 +624,11 @@ class QwenLLM:
         self._sample_room()
         if token_id is not None:
             self.dplan.view(-1)[1:2].copy_(token_id.to(torch.int32).view(1), non_blocking=True)
-        if self._dgraph is None or self._sampled not in self._dgraph:      # one graph per head (greedy / sampled); the sampling values are data
-            with ops.graph_lock.capture(), torch.inference_mode(False):   # exclusive (see ops._CaptureLock); mode: see FO1Engine._capture
-                snap = self.dstate.clone()
-                plan = self.dplan.clone()
-                sb = [self._sbuf[k] for k in ("state", "ids", "done")] if self._sampled else []
-                sb_snap = [t.clone() for t in sb]
-                s = torch.cuda.Stream()
-                s.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(s):
-                    self._decode_device()          # warm-up: allocates scratch (the step it computes is re-done below)
-                torch.cuda.current_stream().wait_stream(s)
-                torch.cuda.synchronize()
-                self.dstate.copy_(snap)
-                self.dplan.copy_(plan)
-                for t, t0 in zip(sb, sb_snap):
-                    t.copy_(t0)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):   # RCCL watchdog threads may touch the runtime meanwhile
-                    logits = self._decode_device()
-                self.dstate.copy_(snap)            # the capture itself does not execute, but keep the state exact
-                self.dplan.copy_(plan)
-                self._dgraph = dict(self._dgraph or {})
-                self._dgraph[self._sampled] = (g, logits)
+        if self._sampled not in self._dgraph:      # one graph per head (greedy / sampled); the sampling values are data
+            sb = [self._sbuf[k] for k in ("state", "ids", "done")] if self._sampled else []
+            self._dgraph[self._sampled] = ops.capture_graph(self._decode_device, rollback=(self.dstate, self.dplan, *sb))
         g, logits = self._dgraph[self._sampled]
-        with ops.graph_lock.replay():
-            g.replay()
+        ops.replay_graph(g)
         self.kv_len += 1
         return logits, self.dplan.view(-1)[1:2]
 
@@ -678,6 +657,36 @@ def reloc_rows(seqs, dst0s):
         else:
             rows.append([o, d, L, 0])
     return rows
+
+
+# ---- host bookkeeping of the decode classes (BatchDecoder, DecodePool).  No silent truncation: the HF-like contract is
+# "exactly these stop ids, exactly this budget" ----
+def stop_id_list(stop_ids, max_stop: int, who: str, hint: str = "") -> List[int]:
+    """The sorted distinct stop ids; more than the device-side rule compares against is an error."""
+    ids = sorted(set(int(t) for t in stop_ids))
+    if len(ids) > max_stop:
+        raise ValueError(f"{who} evaluates at most {max_stop} stop ids on the device (got {len(ids)}){hint}")
+    return ids
+
+
+def token_budget(max_new_tokens, cap: int, who: str, hint: str = "") -> int:
+    """max_new_tokens as the device counts it (at least the first token); more than the ids buffer keeps is an error."""
+    max_new = max(1, int(max_new_tokens))
+    if max_new > cap:
+        raise ValueError(f"{who} keeps at most {cap} generated ids per sequence (max_new_tokens={max_new}){hint}")
+    return max_new
+
+
+def live_state_rows(bases, seqs, deltas, max_new: int, set_row: int = 0):
+    """Device state rows [next cache row, next rope row, first cache row, finished, generated, budget, stop set, 0] of sequences
+    (off, L, ...) that were just relocated to cache rows `bases`."""
+    return [[b + L, L + d, b, 0, 0, max_new, set_row, 0] for b, (_, L, *_), d in zip(bases, seqs, deltas)]
+
+
+def empty_state_rows(bases):
+    """State rows of empty slots = "finished": a step skips their attention and ignores their ids, and the K / V^T rows it still
+    appends for them land inside their own slot (at `base`)."""
+    return [[b, 0, b, 1, 0, 0, 0, 0] for b in bases]
 
 
 class BatchDecoder:
@@ -742,13 +751,8 @@ class BatchDecoder:
         B = len(seqs)
         if B > self.MAX_BATCH:
             raise ValueError(f"BatchDecoder handles at most {self.MAX_BATCH} sequences")
-        # no silent truncation: the HF-like contract is "exactly these stop ids, exactly this budget"
-        stop_ids = sorted(set(int(t) for t in stop_ids))
-        if len(stop_ids) > self.MAX_STOP:
-            raise ValueError(f"BatchDecoder evaluates at most {self.MAX_STOP} stop ids on the device (got {len(stop_ids)}); use the host loop")
-        if int(max_new_tokens) > self.IDS_CAP:
-            raise ValueError(f"BatchDecoder keeps at most {self.IDS_CAP} generated ids per sequence (max_new_tokens={int(max_new_tokens)}); use the host loop")
-        max_new = max(1, int(max_new_tokens))
+        stop_ids = stop_id_list(stop_ids, self.MAX_STOP, "BatchDecoder", "; use the host loop")
+        max_new = token_budget(max_new_tokens, self.IDS_CAP, "BatchDecoder", "; use the host loop")
         need = max(L for _, L, *_ in seqs) + max_new + 1
         slot = 1024
         while slot < need:
@@ -762,8 +766,7 @@ class BatchDecoder:
         self.len0, self.steps = max(L for _, L, *_ in seqs), 0      # host-side bound on any sequence's keys: len0 + steps + 1
         reloc = torch.tensor(reloc_rows(seqs, [b * slot for b in range(B)]), dtype=torch.int32)
         nr = reloc.shape[0]
-        state = torch.tensor([[b * slot + L, L + d, b * slot, 0, 0, max_new, 0, 0] for b, ((o, L, *_), d) in enumerate(zip(seqs, deltas))],
-                             dtype=torch.int32)
+        state = torch.tensor(live_state_rows([b * slot for b in range(B)], seqs, deltas, max_new), dtype=torch.int32)
         stop = torch.tensor(stop_ids + [0] * (self.MAX_STOP - len(stop_ids)), dtype=torch.int32)
         self.n_stop = len(stop_ids)
         self.reloc[:nr].copy_(reloc, non_blocking=True)
@@ -834,24 +837,9 @@ class BatchDecoder:
         # them (grow_rope) while this decoder's graphs survive — a replay would read the freed table
         key = (self.B, self.slot, self.n_stop, self.kv_bucket(), self.llm.rope_epoch, self.llm.rope_cos.data_ptr(), self.sampled)
         ent = self._graphs.get(key)
-        if ent is None:
-            with ops.graph_lock.capture(), torch.inference_mode(False):
-                snap = (self.state.clone(), self.plan.clone(), self.ids.clone(), self.done.clone())
-                s = torch.cuda.Stream()
-                s.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(s):
-                    self._step_device()          # warm-up (allocates scratch); its effects are rolled back below
-                torch.cuda.current_stream().wait_stream(s)
-                torch.cuda.synchronize()
-                for dst, src in zip((self.state, self.plan, self.ids, self.done), snap):
-                    dst.copy_(src)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    logits = self._step_device()
-                ent = (g, logits)
-                self._graphs[key] = ent
-        with ops.graph_lock.replay():
-            ent[0].replay()
+        if ent is None:      # (ops.capture_graph: the warm-up step is rolled back)
+            ent = self._graphs[key] = ops.capture_graph(self._step_device, rollback=(self.state, self.plan, self.ids, self.done))
+        ops.replay_graph(ent[0])
         self.steps += 1
         return ent[1]
 
@@ -871,9 +859,7 @@ class BatchDecoder:
             if i % poll == 0 and int(self.done.item()) >= B:     # the only host read in the loop, every `poll` steps
                 break
             self.step(use_graph)
-        n = self.state[:B, 4].cpu().tolist()
-        ids = self.ids[:B, :max(n)].cpu().tolist()
-        return [row[:k] for row, k in zip(ids, n)]
+        return self.results()
 
 
 def run_decoders(decs: Sequence["BatchDecoder"], streams: Sequence, max_new_tokens: int, use_graph: bool = True, poll: int = 8) -> List[List[List[int]]]:
@@ -935,9 +921,7 @@ class DecodePool:
         dev = llm.dev
         P = slots
         with torch.inference_mode(False):
-            st = torch.zeros(P, 8, dtype=torch.int32)
-            st[:, 3] = 1                               # every slot starts empty = "finished": its attention is skipped, its ids ignored
-            self.state = st.to(dev)
+            self.state = torch.tensor(empty_state_rows([0] * P), dtype=torch.int32).to(dev)      # every slot starts empty (_ensure places them)
             self.plan = torch.zeros(P, 2, dtype=torch.int32, device=dev)
             self.ids = torch.zeros(P, self.IDS_CAP, dtype=torch.int32, device=dev)
             self.done = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -980,11 +964,8 @@ class DecodePool:
             self._graphs = {}
             # an empty / finished slot still runs every step: its (ignored) K / V^T rows must land inside ITS OWN slot — row 0 of the
             # cache is slot 0's first prompt token
-            st = torch.zeros(self.P, 8, dtype=torch.int32)
-            st[:, 0] = st[:, 2] = torch.arange(self.P, dtype=torch.int32) * rows
-            st[:, 3] = 1
             with torch.inference_mode(False):
-                self.state.copy_(st)
+                self.state.copy_(torch.tensor(empty_state_rows([s * rows for s in range(self.P)]), dtype=torch.int32))
         if self.llm.rope_cos.shape[0] < self.slot_rows:
             self.llm.grow_rope(self.slot_rows)
             self._graphs = {}
@@ -999,13 +980,8 @@ class DecodePool:
         on the CURRENT stream (the pool's), the relocation of every sequence into a free slot and the on-device accept of its first
         token.  Returns the slots.  Raises if there is no room (callers check `len(pool.free)` / `fits()` first)."""
         B = len(seqs)
-        stop_ids = tuple(sorted(set(int(t) for t in stop_ids)))
-        if len(stop_ids) > self.MAX_STOP:
-            raise ValueError(f"DecodePool evaluates at most {self.MAX_STOP} stop ids on the device (got {len(stop_ids)})")
-        set_row = self._stop_set_row(stop_ids)
-        max_new = max(1, int(max_new_tokens))
-        if max_new > self.IDS_CAP:
-            raise ValueError(f"DecodePool keeps at most {self.IDS_CAP} generated ids per sequence (max_new_tokens={max_new})")
+        set_row = self._stop_set_row(tuple(stop_id_list(stop_ids, self.MAX_STOP, "DecodePool")))
+        max_new = token_budget(max_new_tokens, self.IDS_CAP, "DecodePool")
         if B > len(self.free):
             raise RuntimeError(f"DecodePool: {B} sequences, {len(self.free)} free slots")
         if not self.fits(seqs, max_new):
@@ -1017,9 +993,7 @@ class DecodePool:
         except BaseException:
             # nothing of this submission is live: its slots go back (their device state may be half written — the next occupant's
             # join rewrites state, plan and K / V^T rows; until then the slot is marked finished so that no step reads it)
-            done = torch.zeros(len(slots), 8, dtype=torch.int32)
-            done[:, 0] = done[:, 2] = torch.tensor(slots, dtype=torch.int32) * self.slot_rows
-            done[:, 3] = 1
+            done = torch.tensor(empty_state_rows([s * self.slot_rows for s in slots]), dtype=torch.int32)
             self._keep.append(done)
             try:
                 for k, sl in enumerate(slots):
@@ -1062,7 +1036,7 @@ class DecodePool:
     def _join_slots(self, slots, kcache, vtcache, seqs, deltas, first_tokens, max_new, set_row):
         B = len(slots)
         R = self.slot_rows
-        state = torch.tensor([[s * R + L, L + d, s * R, 0, 0, max_new, set_row, 0] for s, (_, L, *_), d in zip(slots, seqs, deltas)], dtype=torch.int32)
+        state = torch.tensor(live_state_rows([s * R for s in slots], seqs, deltas, max_new, set_row), dtype=torch.int32)
         first = first_tokens.to(torch.int32).contiguous()
         self._keep += [state]
         if len(self._keep) > 64:
@@ -1168,23 +1142,10 @@ class DecodePool:
             key = (self.slot_rows, bucket, self.llm.rope_epoch, self.llm.rope_cos.data_ptr(), bool(self.FUSED_SPLITK), tuple(sorted(self.SPLITS.items())), bool(self.TILED_WEIGHTS))
             ent = self._graphs.get(key)
             if ent is None:
-                with ops.graph_lock.capture(), torch.inference_mode(False):
-                    snap = (self.state.clone(), self.plan.clone(), self.ids.clone(), self.done.clone())
-                    s = torch.cuda.Stream()
-                    s.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(s):
-                        self._step_device(bucket)      # warm-up (allocates scratch); rolled back below.  The K / V^T it appends land on
-                    torch.cuda.current_stream().wait_stream(s)   # the rows the captured step rewrites with the same values
-                    torch.cuda.synchronize()
-                    for dst, src in zip((self.state, self.plan, self.ids, self.done), snap):
-                        dst.copy_(src)
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                        logits = self._step_device(bucket)
-                    ent = (g, logits)
-                    self._graphs[key] = ent
-            with ops.graph_lock.replay():
-                ent[0].replay()
+                # (ops.capture_graph: the warm-up step is rolled back; the K / V^T rows it appended are the ones the first replay
+                # rewrites with the same values)
+                ent = self._graphs[key] = ops.capture_graph(lambda: self._step_device(bucket), rollback=(self.state, self.plan, self.ids, self.done))
+            ops.replay_graph(ent[0])
             out = ent[1]
         self.steps_run += 1
         for s in self.live:

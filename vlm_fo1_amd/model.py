@@ -461,14 +461,8 @@ class FO1Engine:
         key = (meta["grids"], tuple(tuple(a.shape) for a in auxs), tuple(n_reg), meta["seqs"], meta["want"], meta["img_of"], pix.dtype, auxs[0].dtype,
                self.llm.cache_epoch)
         ent = self._graphs.get(key) if use_graph else None
-        if use_graph and ent is None:
-            seen = self._seen.get(key, 0)
-            if seen >= self.CAPTURE_AFTER:
-                ent = self._capture(key, pix, auxs, boxes, host, meta)
-            else:
-                if len(self._seen) >= 4096:
-                    self._seen.pop(next(iter(self._seen)))
-                self._seen[key] = seen + 1
+        if use_graph and ent is None and ops.seen_enough(self._seen, key, self.CAPTURE_AFTER):
+            ent = self._capture(key, pix, auxs, boxes, host, meta)
         if ent is None:
             st = dict(pix=pix, aux=auxs, boxes=boxes, **{k: v.to(self.dev) for k, v in host.items()})
             if len({tuple(a.shape) for a in auxs}) == 1:      # same-size aux images: one DaViT pass over the stack (input staging)
@@ -496,8 +490,7 @@ class FO1Engine:
             keep.append(host)
             if len(keep) > 8:
                 del keep[0]
-            with ops.graph_lock.replay():
-                g.replay()
+            ops.replay_graph(g)
         outs = []
         for i, (o, L, Lp, *pre) in enumerate(hp["seqs"]):
             r0, r1 = res["region_ranges"][i]
@@ -642,36 +635,21 @@ class FO1Engine:
         return self._dec
 
     def _capture(self, key, pix, auxs, boxes, host, meta):
-        # Captures always run with inference mode OFF: the CUDA generator's graph bookkeeping tensors are created by the first live
-        # capture and updated in place by later ones — if the first ran under the caller's torch.inference_mode() (the reference's
-        # inference.py:46) a later capture outside it fails ("Inplace update to inference tensor outside InferenceMode").
-        with ops.graph_lock.capture(), torch.inference_mode(False):   # exclusive: no other thread captures or launches meanwhile
-            # static input buffers must be ordinary tensors even when the caller runs under torch.inference_mode()
-            # (the reference's inference.py:46 does): they are updated in place later
-            with torch.inference_mode(False):
-                st = dict(pix=pix.clone(), boxes=[b.clone() for b in boxes], **{k: v.clone().to(self.dev) for k, v in host.items()})
-                if len({tuple(a.shape) for a in auxs}) == 1:
-                    st["aux_stack"] = torch.stack([a.to(self.dev) for a in auxs], 0)
-                    st["aux"] = list(st["aux_stack"].unbind(0))       # views: refreshing them refreshes the stack
-                    if len(auxs) > 1 and all(meta["want"]):
-                        st["boxes_cat"] = torch.cat(st["boxes"], 0)
-                        st["boxes"] = list(st["boxes_cat"].split([b.shape[0] for b in boxes], 0))
-                else:
-                    st["aux"] = [a.clone() for a in auxs]
-            s = torch.cuda.Stream()   # warm-up on a side stream (allocates every lazily-created scratch buffer), then capture
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                self._device_batch(st, meta)
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):   # RCCL watchdog threads may touch the runtime meanwhile
-                res = self._device_batch(st, meta)
-            ent = (g, st, res, [])
-            self._graphs[key] = ent
-            while len(self._graphs) > self.GRAPH_CACHE:      # LRU: the evicted graph's private pool is released with it
-                self._graphs.popitem(last=False)
-            return ent
+        # static input buffers must be ordinary tensors even when the caller runs under torch.inference_mode()
+        # (the reference's inference.py:46 does): they are updated in place later
+        with torch.inference_mode(False):
+            st = dict(pix=pix.clone(), boxes=[b.clone() for b in boxes], **{k: v.clone().to(self.dev) for k, v in host.items()})
+            if len({tuple(a.shape) for a in auxs}) == 1:
+                st["aux_stack"] = torch.stack([a.to(self.dev) for a in auxs], 0)
+                st["aux"] = list(st["aux_stack"].unbind(0))       # views: refreshing them refreshes the stack
+                if len(auxs) > 1 and all(meta["want"]):
+                    st["boxes_cat"] = torch.cat(st["boxes"], 0)
+                    st["boxes"] = list(st["boxes_cat"].split([b.shape[0] for b in boxes], 0))
+            else:
+                st["aux"] = [a.clone() for a in auxs]
+        # (ops.capture_graph; no rollback: the pass advances no state, and every replay rewrites its cache rows)
+        g, res = ops.capture_graph(lambda: self._device_batch(st, meta))
+        return ops.lru_put(self._graphs, key, (g, st, res, []), self.GRAPH_CACHE)
 
     def prefill(self, input_ids: Sequence[int], pixel_values: torch.Tensor, grid_hw: Tuple[int, int], aux_image: torch.Tensor,
                 boxes: Optional[torch.Tensor], use_graph: bool = False):

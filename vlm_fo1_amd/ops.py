@@ -126,6 +126,68 @@ class _CaptureLock:
 graph_lock = _CaptureLock()
 
 
+def capture_graph(run, rollback: Sequence[torch.Tensor] = ()):
+    """The one recipe every hipGraph of the package is captured with -> (graph, what the captured `run()` returned: static
+    buffers of the graph).  `run` enqueues the work on the current stream and is called twice: an eager warm-up, then under
+    capture.  `rollback` names the persistent tensors the work updates in place (a decode step's state, plan, ids, done
+    counter): they are restored after the warm-up, so the capture starts from, and the caller's first replay executes, the
+    step the caller asked for.  What `rollback` does not name stays as the warm-up left it.  Static INPUTS are the caller's:
+    cloned before the call, under the caller's own torch.inference_mode(False), and refreshed in place before each replay.
+    The helper owns no cache, and when `run` raises the lock and the mode are released and nothing else is undone."""
+    # * graph_lock.capture(): exclusive against every other capture, warm-up and replay of the process (_CaptureLock).
+    # * inference mode OFF: the CUDA generator's graph bookkeeping tensors are created by the first live capture and updated in
+    #   place by later ones — if the first ran under the caller's torch.inference_mode() (the reference's inference.py:46) a
+    #   later capture outside it fails ("Inplace update to inference tensor outside InferenceMode"); and what `run` returns
+    #   must be ordinary tensors, the callers hand them out for the life of the graph.
+    with graph_lock.capture(), torch.inference_mode(False):
+        snap = [t.clone() for t in rollback]
+        # warm-up on a fresh side stream: every lazily created scratch buffer (_workspace, zero_framed, plans) exists before
+        # the capture — an allocation inside a capture would land in the graph's private pool, or fail it
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            run()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        for t, t0 in zip(rollback, snap):      # once: the capture below executes nothing, so there is nothing to undo after it
+            t.copy_(t0)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):   # RCCL watchdog threads may touch the runtime meanwhile
+            out = run()
+    return g, out
+
+
+def replay_graph(g) -> None:
+    """Launch a captured graph on the current stream: shared with other replays, excluded by a capture (_CaptureLock)."""
+    with graph_lock.replay():
+        g.replay()
+
+
+SEEN_MAX = 4096      # signatures whose sightings are remembered (a dataset has thousands of distinct image sizes)
+
+
+def seen_enough(seen: dict, key, after: int) -> bool:
+    """Capture policy of the engines' graph caches: is this sighting of `key` the one to capture on?  A signature runs eagerly
+    `after` times (one-off shapes never pay a capture) and is captured on the next sighting — also every later one, should its
+    graph have been evicted meanwhile.  `seen` counts the eager sightings; at SEEN_MAX keys the oldest is dropped."""
+    n = seen.get(key, 0)
+    if n >= after:
+        return True
+    if len(seen) >= SEEN_MAX:
+        seen.pop(next(iter(seen)))
+    seen[key] = n + 1
+    return False
+
+
+def lru_put(cache, key, value, cap: int):
+    """Insert into an OrderedDict kept as an LRU of `cap` entries (a hit is cache.move_to_end(key)) -> value.  An evicted graph's
+    private pool is released with it."""
+    cache[key] = value
+    while len(cache) > cap:
+        cache.popitem(last=False)
+    return value
+
+
 class workspace_scope:
     def __init__(self, owner):
         self.owner = owner

@@ -466,34 +466,18 @@ class UPNEngine:
         key = (tuple(img.shape), prompt_type)
         ent = self._graphs.get(key)
         if ent is None:
-            n = self._seen.get(key, 0)
-            if len(self._seen) >= 4096:                  # bounded: a dataset has thousands of distinct image sizes
-                self._seen.pop(next(iter(self._seen)))
-            self._seen[key] = n + 1
-            if n < self.CAPTURE_AFTER:
+            if not ops.seen_enough(self._seen, key, self.CAPTURE_AFTER):
                 with ops.workspace_scope(self._ws_owner):
                     return self.forward(img, prompt_type)
-            with ops.graph_lock.capture(), torch.inference_mode(False), ops.workspace_scope(self._ws_owner):
+            with torch.inference_mode(False), ops.workspace_scope(self._ws_owner):
                 static = img.clone()
-                side = torch.cuda.Stream()           # warm-up on a side stream (allocates every lazily-created scratch buffer), then capture
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    self.forward(static, prompt_type)
-                torch.cuda.current_stream().wait_stream(side)
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    out = self.forward(static, prompt_type)
-                ent = (g, static, dict(pred_boxes=out["pred_boxes"], pred_logits=out["pred_logits"]))
-                self._graphs[key] = ent
-                while len(self._graphs) > self.GRAPH_CACHE:
-                    self._graphs.popitem(last=False)
+                g, out = ops.capture_graph(lambda: self.forward(static, prompt_type))
+            ent = ops.lru_put(self._graphs, key, (g, static, dict(pred_boxes=out["pred_boxes"], pred_logits=out["pred_logits"])), self.GRAPH_CACHE)
         else:
             self._graphs.move_to_end(key)
         g, static, out = ent
         static.copy_(img)
-        with ops.graph_lock.replay():
-            g.replay()
+        ops.replay_graph(g)
         return out
 
     def forward(self, img: torch.Tensor, prompt_type: str = "fine_grained_prompt") -> dict:
