@@ -26,7 +26,7 @@ extern "C" {
 #pragma GCC visibility push(default) /* libfo1hip*.so are built with -fvisibility=hidden: exactly the declarations of this header are exported */
 #endif
 
-#define FO1_ABI_VERSION 9   /* 9: (additive: fo1_sample_params_t, fo1_sample_rows_workspace_bytes, fo1_sample_rows_bf16, fo1_decode_sample_accept — the sampled decode head) fo1_window_attention_bf16 (DaViT window attention on the q/k/v rows: no V^T copy), fo1_window_attention_map_bf16 / _var (the same on un-partitioned pixel rows: no window partition / reverse), fo1_attention_windows_bf16 (single-tile work lists in a software pipeline; fo1_vit_plan_t.q_block_win 0 selects it); 8: fo1_attention_decode_batch_partials_bf16 + fo1_gemv_attn_combine_bf16 (decode step at <= 2 sequences: the o-projection sums the split-KV partials in its prologue, no combine launch); 7: fo1_vit_block_t gained wqkv_hm / bqkv_hm (optional head-major q/k/v copy: fo1_vit_forward then takes the fused q/k/v epilogue); 6: attention q_block 128 / 256 (32x32-MFMA prefill kernel); fo1_qkv_proj_rope_bf16 (q/k/v projection with RoPE / K append / V^T in the GEMM epilogue); fo1_gemm_bf16_wtiled, fo1_splitk_swiglu_bf16 (measured no-gain forms), fo1_mfma_clock_probe, fo1_gemm_profile_shapes (instruments) moved to fo1_ab.h; 5: split-K planes consumed by fused kernels in the decode pool (fo1_gemm_bf16_partials, fo1_splitk_residual_rmsnorm_bf16, fo1_pool_qkv_post_partials_bf16, fo1_splitk_swiglu_bf16), fo1_gemm_bf16_wtiled, fo1_mfma_clock_probe; 4: decode pool (fo1_pool_qkv_post_bf16; fo1_decode_argmax_accept up to 256 rows): continuous batching of 33..128 sequences; 3: fo1_hfre_opts_t grew out_bf16 / out_bf16_ld; fo1_img_seg + the *_var spatial entry points */
+#define FO1_ABI_VERSION 9   /* 9: (additive: fo1_seen_mark, fo1_sample_rows_seen_bf16, fo1_decode_head_accept — the general decode head: per-row greedy flag and repetition penalty in fo1_sample_params_t's former reserved words) (additive: fo1_sample_params_t, fo1_sample_rows_workspace_bytes, fo1_sample_rows_bf16, fo1_decode_sample_accept — the sampled decode head) fo1_window_attention_bf16 (DaViT window attention on the q/k/v rows: no V^T copy), fo1_window_attention_map_bf16 / _var (the same on un-partitioned pixel rows: no window partition / reverse), fo1_attention_windows_bf16 (single-tile work lists in a software pipeline; fo1_vit_plan_t.q_block_win 0 selects it); 8: fo1_attention_decode_batch_partials_bf16 + fo1_gemv_attn_combine_bf16 (decode step at <= 2 sequences: the o-projection sums the split-KV partials in its prologue, no combine launch); 7: fo1_vit_block_t gained wqkv_hm / bqkv_hm (optional head-major q/k/v copy: fo1_vit_forward then takes the fused q/k/v epilogue); 6: attention q_block 128 / 256 (32x32-MFMA prefill kernel); fo1_qkv_proj_rope_bf16 (q/k/v projection with RoPE / K append / V^T in the GEMM epilogue); fo1_gemm_bf16_wtiled, fo1_splitk_swiglu_bf16 (measured no-gain forms), fo1_mfma_clock_probe, fo1_gemm_profile_shapes (instruments) moved to fo1_ab.h; 5: split-K planes consumed by fused kernels in the decode pool (fo1_gemm_bf16_partials, fo1_splitk_residual_rmsnorm_bf16, fo1_pool_qkv_post_partials_bf16, fo1_splitk_swiglu_bf16), fo1_gemm_bf16_wtiled, fo1_mfma_clock_probe; 4: decode pool (fo1_pool_qkv_post_bf16; fo1_decode_argmax_accept up to 256 rows): continuous batching of 33..128 sequences; 3: fo1_hfre_opts_t grew out_bf16 / out_bf16_ld; fo1_img_seg + the *_var spatial entry points */
 #define FO1_OK 0
 #define FO1_ERR_ARG (-1)       /* bad argument / unsupported shape */
 #define FO1_ERR_WORKSPACE (-2) /* workspace too small */
@@ -491,12 +491,29 @@ int fo1_argmax_rows_bf16(const void* logits, long long ld_logits, int n_vocab, i
  *                              element b * counter_stride for row b); u != NULL: explicit draws, device fp32 [B], instead of Philox
  *   fo1_decode_sample_accept   the sampled form of fo1_decode_argmax_accept: counter = state[b][4], same bookkeeping, same contract for a
  *                              finished row (nothing recorded, state untouched, plan[1] = 0 whatever its logits hold)
- * params: DEVICE table, one row per sequence. */
+ * params: DEVICE table, one row per sequence.
+ *
+ * The general head (fo1_sample_rows_seen_bf16, fo1_decode_head_accept) additionally honours the last two words of a row; the two entries above
+ * ignore them, as they always have.
+ *   flags & FO1_SAMPLE_GREEDY: the id is the first index, in vocabulary order, of the largest (penalised) finite entry; nothing is drawn and
+ *     temperature, top_p, top_k and the Philox words are ignored.  The ids of fo1_argmax_rows_bf16 on rows without +inf / NaN.
+ *   repetition_penalty p: on iff p is finite, > 0 and != 1 (0, the all-zero tail, is off).  seen: DEVICE bitmap uint32 [rows][ld_words], bit
+ *     t & 31 of word t >> 5 of row b = token t occurs in sequence b's prompt or among its generated ids; ld_words >= ceil(n_vocab / 32) and a
+ *     multiple of 4.  For a seen token i with a finite logit, l'_i = bf16_rne(l_i < 0 ? fp32(l_i) * p : fp32(l_i) / p) (IEEE division) replaces
+ *     l_i in every pass of the definition above; unseen and non-finite entries are unchanged; a penalised value that is not finite counts as a
+ *     non-finite entry.  HF's RepetitionPenaltyLogitsProcessor in front of the warpers, the score rounded back to bf16.
+ *     seen == NULL is allowed only when no row has the penalty on: the rows live on the device, the host cannot check it.
+ *   fo1_seen_mark               sets the bits of n (row, id) pairs (device int32 each); ids outside [0, n_vocab) and negative rows are skipped
+ *   fo1_sample_rows_seen_bf16   fo1_sample_rows_bf16 + flags, penalty
+ *   fo1_decode_head_accept      fo1_decode_sample_accept + flags, penalty; sets the accepted token's bit in row b of `seen` (when given).
+ *                               A finished row touches nothing, its bitmap row included. */
+#define FO1_SAMPLE_GREEDY 1u
 typedef struct fo1_sample_params {
     float temperature, top_p;
     int32_t top_k;                      /* 0 = off */
     uint32_t seed_lo, seed_hi, stream;  /* Philox key and counter word 1 */
-    uint32_t reserved[2];
+    uint32_t flags;                     /* FO1_SAMPLE_GREEDY; read by the general head only */
+    float repetition_penalty;           /* read by the general head only; 0 = off */
 } fo1_sample_params_t;                  /* 32 bytes */
 size_t fo1_sample_rows_workspace_bytes(int n_vocab, int B);
 int fo1_sample_rows_bf16(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params,
@@ -505,6 +522,15 @@ int fo1_sample_rows_bf16(const void* logits, long long ld_logits, int n_vocab, i
 int fo1_decode_sample_accept(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params,
                              int32_t* state, int32_t* plan, int32_t* ids_out, int ids_ld, const int32_t* stop_ids, int n_stop,
                              int32_t* done, void* workspace, size_t workspace_bytes, void* stream);
+int fo1_seen_mark(uint32_t* seen, long long ld_words, int n_vocab, const int32_t* rows /* [n] */, const int32_t* ids /* [n] */, int n,
+                       void* stream);
+int fo1_sample_rows_seen_bf16(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params,
+                              const int32_t* counter /* NULL = 0 */, int counter_stride, const float* u /* device [B]; NULL = Philox */,
+                              int32_t* out /* [B] */, void* workspace, size_t workspace_bytes, const uint32_t* seen, long long ld_words,
+                              void* stream);
+int fo1_decode_head_accept(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params,
+                           int32_t* state, int32_t* plan, int32_t* ids_out, int ids_ld, const int32_t* stop_ids, int n_stop,
+                           int32_t* done, void* workspace, size_t workspace_bytes, uint32_t* seen, long long ld_words, void* stream);
 int fo1_kv_relocate(const void* ksrc, void* kdst, long long ks_layer, long long ks_head, long long kd_layer,
                     long long kd_head, const void* vsrc, void* vdst, long long vs_layer, long long vs_row,
                     long long vd_layer, long long vd_row, const int32_t* seqs, int B, int max_len, int n_kv_heads,

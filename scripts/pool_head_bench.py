@@ -1,0 +1,92 @@
+#!/usr/bin/env python3
+"""Decode-pool step time by head, on the GPU: ms per step of llm.DecodePool with every slot live at the metric configuration's context
+(the 3B shapes, 651-token prompts; scripts/pool_bench.py's workload), the step ending in
+  greedy     fo1_decode_argmax_accept (every sequence plain greedy),
+  sampled    the general head fo1_decode_head_accept, every sequence sampled (T = 0.7, top_k = 50, top_p = 0.9),
+  penalised  the same with repetition_penalty = 1.3 on every sequence (seen bitmap read in every pass).
+The heads are timed alternately, `--rounds` times each in one process, so the spread of a figure is the spread between its rounds; the pool is
+drained and re-joined for every timing.  Prints one JSON object.
+
+    python scripts/pool_head_bench.py [--slots 128] [--steps 64] [--rounds 5] [--heads greedy sampled penalised] [--root DIR]
+
+--root DIR imports the package from another checkout (e.g. the parent commit, for the greedy figure of both on one box; only `greedy`
+exists there)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--slots", type=int, default=128)
+    ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--heads", nargs="+", default=["greedy", "sampled", "penalised"], choices=["greedy", "sampled", "penalised"])
+    ap.add_argument("--root", default=None, help="import vlm_fo1_amd from this checkout instead of the script's own")
+    args = ap.parse_args()
+    sys.path.insert(0, HERE)                 # bench.py (the workload builder)
+    if args.root:
+        sys.path.insert(0, os.path.abspath(args.root))
+    import torch
+    import vlm_fo1_amd                       # (first: bench.py puts its own checkout in front of sys.path, the package is then already bound)
+    import bench as B
+    from vlm_fo1_amd.llm import DecodePool
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    cases = [B.build_workload(dev, n_boxes=100, seed=1234 + i) for i in range(32)]
+    pipe = B.Pipeline(cases[0], dev, inflight=1, batch=32, cases=cases)
+    eng = pipe.eng
+    eng.prefill_batch(pipe.requests, use_graph=False)
+    torch.cuda.synchronize()
+    hp, first = eng._last_batch, eng._last_next_tokens.clone()
+    prompts = [list(r["ids"]) for r in pipe.requests]
+    P = args.slots
+    pool = DecodePool(eng.llm, slots=P)
+    sampling = dict(greedy=None,
+                    sampled=dict(temperature=0.7, top_p=0.9, top_k=50, seed=11),
+                    penalised=dict(temperature=0.7, top_p=0.9, top_k=50, seed=11, repetition_penalty=1.3))
+    budget = 4 + args.steps + 8
+
+    def one(head):
+        left, base = P, 0
+        while left > 0:
+            n = min(32, left)
+            kw = {} if sampling[head] is None else dict(sampling=dict(sampling[head], stream=base), prompt_ids=prompts[:n])
+            pool.join(eng.llm.kcache, eng.llm.vtcache, hp["seqs"][:n], hp["delta"][:n], first[:n], budget, (), **kw)
+            left -= n
+            base += n
+        for _ in range(4):
+            pool.step(True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            pool.step(True)
+        torch.cuda.synchronize()
+        t = (time.perf_counter() - t0) / args.steps
+        live = len(pool.live)
+        pool.drain(poll=8)                   # to the budget: every slot is free again for the next timing
+        return t * 1e3, live
+
+    for h in args.heads:                     # captures and first touches outside the timed rounds
+        one(h)
+    times = {h: [] for h in args.heads}
+    for _ in range(args.rounds):
+        for h in args.heads:
+            ms, live = one(h)
+            assert live == P, f"{live} of {P} sequences were live through the timed steps"
+            times[h].append(round(ms, 4))
+    out = dict(package=os.path.dirname(os.path.abspath(vlm_fo1_amd.__file__)), slots=P, live=P, steps=args.steps, rounds=args.rounds,
+               prompt_tokens=hp["seqs"][0][1], vocab=eng.cfg.llm.vocab_size, heads={})
+    for h, v in times.items():
+        out["heads"][h] = dict(ms_per_step=v, median=round(statistics.median(v), 4), min=min(v), max=max(v),
+                               spread_pct=round(100.0 * (max(v) - min(v)) / statistics.median(v), 3))
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -237,24 +237,63 @@ class FO1ForCausalLM:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
         return dict(temperature=tv, top_p=top_p, top_k=top_k, seed=int(seed) & (2 ** 64 - 1))
 
+    @staticmethod
+    def _penalty_plan(kwargs: dict) -> Optional[float]:
+        """generate()'s repetition_penalty -> None (off: None or 1.0) or the value.  Off unless the caller passes one, whatever the
+        checkpoint's generation_config.json says: nothing that decodes without the argument may change."""
+        import math
+        p = kwargs.get("repetition_penalty")
+        if p is None:
+            return None
+        try:
+            pv = None if isinstance(p, bool) else float(p)
+        except (TypeError, ValueError):
+            pv = None
+        p32 = None if pv is None else float(torch.tensor(pv, dtype=torch.float32))      # (the device holds it as fp32)
+        if pv is None or not (math.isfinite(p32) and p32 > 0):
+            raise ValueError(f"repetition_penalty must be a positive finite number, 1.0 switches it off (got {p!r})")
+        return None if p32 == 1.0 else pv
+
+    @classmethod
+    def _decode_plan(cls, kwargs: dict, generation_config: Optional[dict] = None) -> Optional[dict]:
+        """_sampling_plan and _penalty_plan as the one dict the engine takes per request: None = plain greedy; a sampled request's dict
+        gains repetition_penalty; a greedy request with a penalty is dict(greedy=True, repetition_penalty=p)."""
+        sampling, pen = cls._sampling_plan(kwargs, generation_config), cls._penalty_plan(kwargs)
+        if pen is None:
+            return sampling
+        return dict(greedy=True, repetition_penalty=pen) if sampling is None else dict(sampling, repetition_penalty=pen)
+
     def _batch_plan(self, requests_kwargs: List[dict]):
         """Validation shared by generate_many / generate_many_async -> (engine requests, max_new_tokens, device stop ids, sampling), or None
-        when the batch must take the one-by-one host loop (a stop criterion the device rule cannot express, a budget beyond its id buffer)."""
+        when the batch must take the one-by-one host loop (a stop criterion the device rule cannot express, a budget beyond its id buffer).
+        sampling: None, the batch's one dict, or — with the decode pool enabled, whose slots each carry their own parameters — a list with
+        one dict or None per request when the requests differ (request i draws on stream i of its own seed)."""
         k0 = requests_kwargs[0]
+        gen = getattr(self.config, "_gen", None)
         stop = self._device_stop_ids(k0.get("stopping_criteria"))
         if stop is None or not self._fits_device_loop(k0.get("max_new_tokens", 512)):
             return None
-        sampling = self._sampling_plan(k0, getattr(self.config, "_gen", None))
-        values = None if sampling is None else (sampling["temperature"], sampling["top_p"], sampling["top_k"])
-        for kw in requests_kwargs[1:]:       # one budget, one stop rule and one sampling per packed batch: refuse a mixed batch rather than apply the first's
+        pooled = getattr(getattr(self, "engine", None), "_pool_svc", None) is not None
+
+        def values(kw):      # what a packed batch without the pool must share
+            sp = self._sampling_plan(dict(kw, seed=0), gen)
+            return (None if sp is None else (sp["temperature"], sp["top_p"], sp["top_k"])), self._penalty_plan(kw)
+        v0 = values(k0)
+        mixed = False
+        for kw in requests_kwargs[1:]:       # one budget and one stop rule per packed batch: refuse a mixed batch rather than apply the first's
             if int(kw.get("max_new_tokens", 512)) != int(k0.get("max_new_tokens", 512)) or \
                     self._device_stop_ids(kw.get("stopping_criteria")) != stop:
                 raise ValueError("generate_many: every request of a batch must share max_new_tokens and stopping criteria")
-            other = self._sampling_plan(dict(kw, seed=0), getattr(self.config, "_gen", None))
-            if (None if other is None else (other["temperature"], other["top_p"], other["top_k"])) != values:
-                raise ValueError("generate_many: every request of a batch must share do_sample, temperature, top_p and top_k")
-            if other is not None and kw.get("seed") != k0.get("seed"):      # one seed per batch: request i draws on stream i of it
+            v = values(kw)
+            if v != v0 or (v[0] is not None and kw.get("seed") != k0.get("seed")):
+                mixed = True
+                if pooled:
+                    continue
+                if v != v0:      # without the pool one BatchDecoder group decodes the batch with one sampling
+                    raise ValueError("generate_many: every request of a batch must share do_sample, temperature, top_p and top_k "
+                                     "(and repetition_penalty) unless the decode pool is enabled")
                 raise ValueError("generate_many: every request of a sampled batch must share seed (request i draws on stream i of the one seed)")
+        sampling = [self._decode_plan(kw, gen) for kw in requests_kwargs] if mixed else self._decode_plan(k0, gen)
         reqs = [self._request(kw.get("inputs"), kw.get("images"), kw.get("images_aux"), kw.get("image_grid_thws"), kw.get("bbox_list"))
                 for kw in requests_kwargs]
         return reqs, int(k0.get("max_new_tokens", 512)), stop, sampling
@@ -305,10 +344,14 @@ class FO1ForCausalLM:
             return _Ready([])
         eng = self.engine
         plan = self._batch_plan(requests_kwargs) if getattr(eng, "_pool_svc", None) is not None else None
-        if plan is None or plan[3] is not None:      # (the decode pool stays greedy: a sampled batch decodes in its own groups, now)
+        if plan is None:
             return _Ready(self.generate_many(requests_kwargs))
-        reqs, max_new, stop, _ = plan
-        handles = [eng.submit_batch(grp, max_new, stop, self.use_graph) for grp in eng.split_passes(reqs)]      # <= 32 requests and <= 64k ViT rows per pass
+        reqs, max_new, stop, sampling = plan      # (sampled and penalised requests join the pool too: every slot has its own parameters)
+        handles, base = [], 0
+        for grp in eng.split_passes(reqs):        # <= 32 requests and <= 64k ViT rows per pass
+            part = sampling if sampling is None or isinstance(sampling, dict) else sampling[base:base + len(grp)]
+            handles.append(eng.submit_batch(grp, max_new, stop, self.use_graph, sampling=part, stream_base=base))
+            base += len(grp)
         model = self
 
         class _Pending:
@@ -323,15 +366,13 @@ class FO1ForCausalLM:
         BatchDecoder of ONE sequence stepped token by token — the kernels of the device loop, so the same seed draws the same ids whether or
         not a streamer listens (the single-sequence step of QwenLLM runs other GEMV / attention kernels: its logits differ in last bits, and
         a draw near an interval's end would then fall on the neighbouring token)."""
-        from vlm_fo1_amd import ops
         eng, dev = self.engine, self.device
         eng.prefill_batch([req], use_graph=self.use_graph)
         hp = eng._last_batch
-        with ops.workspace_scope(eng._ws_owner):
-            tok = ops.sample_rows(eng._last_logits[:1], ops.sample_params([(sampling["temperature"], sampling["top_p"], sampling["top_k"],
-                                                                            sampling["seed"], stream)], dev))
+        per = [dict(sampling, stream=stream)]      # (a greedy request with a repetition penalty takes this loop too: dict(greedy=True, ...))
+        tok = eng._first_tokens(per, [req])
         dec = eng._decoder()
-        dec.start(hp["seqs"], hp["delta"], tok, n_max, (), sampling=dict(sampling, streams=[stream]))
+        dec.start(hp["seqs"], hp["delta"], tok, n_max, (), sampling=per, prompt_ids=[req["ids"]])
         eos = set(self.config.eos_ids())
         all_ids = inputs.to(dev)
         if streamer is not None:
@@ -355,21 +396,24 @@ class FO1ForCausalLM:
     @torch.no_grad()
     def generate(self, inputs=None, images=None, images_aux=None, image_grid_thws=None, bbox_list=None, do_sample=False,
                  temperature=0.0, max_new_tokens=512, streamer=None, top_p=1.0, use_cache=True, stopping_criteria=None,
-                 pad_token_id=None, top_k=None, seed=None, _stream=0, **unused) -> torch.LongTensor:
+                 pad_token_id=None, top_k=None, seed=None, repetition_penalty=None, _stream=0, **unused) -> torch.LongTensor:
         """Decoding of one prompt: greedy, or with do_sample=True temperature / top-k / top-p sampling on the device (_sampling_plan).
         Returns [1, L_in + new] like HF generate (the reference slices `output_ids[0, inputs.shape[1]:]`, inference.py:47-48).  Without a
         streamer and with id-set stop criteria the whole loop runs on the device (BatchDecoder, no per-token host read); otherwise tokens
         are handed to the host one by one — the picks are made on the device either way, and both loops draw the same ids.  A sampled
         generation records its ids in the BatchDecoder's buffer: max_new_tokens beyond BatchDecoder.IDS_CAP is a ValueError.  _stream: the
-        Philox stream of the draws (generate_many's one-by-one loop passes the request's index)."""
-        sampling = self._sampling_plan(dict(do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k, seed=seed), getattr(self.config, "_gen", None))
+        Philox stream of the draws (generate_many's one-by-one loop passes the request's index).  repetition_penalty: None or 1.0 = off
+        (the default, whatever generation_config.json holds); else HF's RepetitionPenaltyLogitsProcessor in front of the pick, over the
+        prompt's and the generated ids, on the device; not finite or <= 0 is a ValueError."""
+        sampling = self._decode_plan(dict(do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k, seed=seed,
+                                          repetition_penalty=repetition_penalty), getattr(self.config, "_gen", None))
         req = self._request(inputs, images, images_aux, image_grid_thws, bbox_list)
         dev = self.device
         stop = self._device_stop_ids(stopping_criteria) if streamer is None else None
         if sampling is not None and not self._fits_device_loop(max_new_tokens):
             from vlm_fo1_amd.llm import BatchDecoder
-            raise ValueError(f"do_sample=True draws at most {BatchDecoder.IDS_CAP} tokens per request (max_new_tokens={int(max_new_tokens)})")
-        if stop is not None and (sampling is None or _stream == 0) and self._fits_device_loop(max_new_tokens):
+            raise ValueError(f"do_sample=True (and a repetition penalty) draws at most {BatchDecoder.IDS_CAP} tokens per request (max_new_tokens={int(max_new_tokens)})")
+        if stop is not None and (sampling is None or _stream == 0 or sampling.get("greedy")) and self._fits_device_loop(max_new_tokens):
             ids = self.engine.generate_batch([req], max_new_tokens=int(max_new_tokens), stop_ids=stop, use_graph=self.use_graph, sampling=sampling)[0]
             return torch.cat([inputs.to(dev), torch.tensor([ids], dtype=inputs.dtype, device=dev)], dim=1).to(inputs.device)
         eng = self.engine

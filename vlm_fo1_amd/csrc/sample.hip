@@ -21,6 +21,13 @@
 //      u Z2 walks it again to the slice, the lane and the token.  Prefixes are fp32, the comparison against u Z2 is made in fp64 (u has 25
 //      significant bits: its product with an fp32 Z2 is exact there), so flat rows reproduce floor(u V) bit for bit.
 // top_k == 0 and top_p >= 1 skip 1's counters and 2-4 altogether.
+//
+// The general head (PEN instantiations: fo1_sample_rows_seen_bf16, fo1_decode_head_accept) reads two more words of a row's parameters.  A
+// repetition penalty p (on iff finite, > 0, != 1) replaces the logit of every token whose bit is set in the row's `seen` bitmap by
+// l' = bf16_rne(l < 0 ? l * p : l / p) wherever a pass reads a key (sp_load8p: a lane's 8 logits and the matching byte of the bitmap), so every
+// pass still works on the 65 536 bf16 values; a penalised value that is not finite has no key.  A row with FO1_SAMPLE_GREEDY takes pass 1 without
+// counters and a first-index reduction, then leaves: the first index, in vocabulary order, of the largest (penalised) finite entry.  Both are
+// behind the template parameter: the plain instantiations compile to the code they were before it existed.
 #include "decode_common.h"
 
 namespace fo1 {
@@ -59,12 +66,41 @@ __device__ __forceinline__ void sp_load8(const uint16_t* __restrict__ row, int i
     }
 }
 
+// what the penalty needs of a row: its seen bitmap (bytes: bit j of byte i0 / 8 = token i0 + j, i0 a multiple of 8) and p; seen == NULL: off
+struct SpPen {
+    const uint8_t* seen;
+    float p;
+};
+
+// the penalised logit of a seen token with a finite logit: bf16_rne(l < 0 ? l * p : l / p), IEEE fp32 arithmetic
+__device__ __forceinline__ uint32_t sp_penalise(uint32_t b, float p) {
+    if ((b & 0x7f80u) == 0x7f80u) return b;
+    const float l = __uint_as_float(b << 16);
+    return (uint32_t)f32_to_bf16(l < 0.f ? l * p : __fdiv_rn(l, p));
+}
+
+// sp_load8; PEN: seen tokens come back as their penalised logit, so every pass keys the same 16-bit values
+template <bool PEN>
+__device__ __forceinline__ void sp_load8p(const uint16_t* __restrict__ row, const SpPen& pen, int i0, int V, bool vec, uint32_t (&e)[8]) {
+    sp_load8(row, i0, V, vec, e);
+    if constexpr (PEN) {
+        if (pen.seen) {
+            const uint32_t bits = i0 < V ? pen.seen[i0 >> 3] : 0u;
+            if (bits) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if ((bits >> j) & 1u) e[j] = sp_penalise(e[j], pen.p);
+            }
+        }
+    }
+}
+
 // every key of the row, 8 tokens per thread and step (any order: the callers count or take a maximum)
-template <class F>
-__device__ __forceinline__ void sp_for_row(const uint16_t* __restrict__ row, int V, bool vec, F f) {
+template <bool PEN, class F>
+__device__ __forceinline__ void sp_for_row(const uint16_t* __restrict__ row, const SpPen& pen, int V, bool vec, F f) {
     for (int i0 = threadIdx.x * 8; i0 < V; i0 += SP_NT * 8) {
         uint32_t e[8];
-        sp_load8(row, i0, V, vec, e);
+        sp_load8p<PEN>(row, pen, i0, V, vec, e);
 #pragma unroll
         for (int j = 0; j < 8; ++j) f(sp_key(e[j]));
     }
@@ -92,6 +128,11 @@ __device__ __forceinline__ int sp_wave_max(int v) {
     for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
     return v;
 }
+__device__ __forceinline__ int sp_wave_min(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+    return v;
+}
 
 // word 0 of Philox4x32-10 (Salmon et al., SC'11) for ctr = {c0, c1, 0, 0}, key = {k0, k1}
 __device__ __forceinline__ uint32_t sp_philox_x0(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1) {
@@ -113,6 +154,7 @@ struct SampleArgs {
     const float* u;                             // rows form: explicit draws, NULL = Philox
     int* out;                                   // rows form: [B]
     int* state; int* plan; int* ids_out; int ids_ld; const int* stop_ids; int n_stop; int* done;     // accept form
+    uint32_t* seen; long long ld_words;         // general head: the seen bitmap [rows][ld_words] (NULL: no row has a penalty)
 };
 
 // Key scan of the half whose counters sit in `hist` (keys key0 .. key0 + 32767), top key down.  carry_c / carry_m: tokens and mass of the
@@ -157,7 +199,7 @@ __device__ __forceinline__ void sp_key_scan(const uint32_t* hist, int key0, int 
     __syncthreads();
 }
 
-template <bool ACCEPT>
+template <bool ACCEPT, bool PEN>
 __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
     extern __shared__ __align__(16) unsigned char sp_smem[];
     uint32_t* hist = reinterpret_cast<uint32_t*>(sp_smem);
@@ -182,7 +224,16 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
     if (!(T > 0.f) || !(T < INFINITY) || !(1.0f / T < INFINITY)) { T = 1.f; top_k = 1; }      // not a temperature (or one so small that 1 / T overflows): the greedy pick
     const bool use_p = P.top_p > 0.f && P.top_p < 1.f;               // anything else (NaN included): no nucleus cut
     const float inv_t = 1.0f / T;
-    const bool cut = top_k > 0 || use_p;
+    const bool greedy = PEN && (P.flags & FO1_SAMPLE_GREEDY);
+    const bool cut = !greedy && (top_k > 0 || use_p);
+    SpPen pen{nullptr, 1.f};
+    if constexpr (PEN) {
+        const float rp = P.repetition_penalty;
+        if (a.seen && rp > 0.f && rp < INFINITY && rp != 1.f) {
+            pen.seen = reinterpret_cast<const uint8_t*>(a.seen + (long long)b * a.ld_words);
+            pen.p = rp;
+        }
+    }
 
     // 1. largest finite key (+ the non-negative half's counters)
     if (tid == 0) { s_kcut_k = -1; s_range = 0x7fffffff; s_kcut_p = 0; s_tok = 0; s_z1 = 0.f; }
@@ -191,19 +242,35 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
     __syncthreads();
     int kmax = -1;
     if (cut)
-        sp_for_row(row, V, vec, [&](int k) {
+        sp_for_row<PEN>(row, pen, V, vec, [&](int k) {
             kmax = max(kmax, k);
             if (k >= 0x8000) atomicAdd(&hist[sp_slot(k & 0x7fff)], 1u);
         });
     else
-        sp_for_row(row, V, vec, [&](int k) { kmax = max(kmax, k); });
+        sp_for_row<PEN>(row, pen, V, vec, [&](int k) { kmax = max(kmax, k); });
     kmax = sp_wave_max(kmax);
     if (lane == 0) s_wi[wave] = kmax;
     __syncthreads();
     kmax = s_wi[0];
     for (int w = 1; w < SP_NW; ++w) kmax = max(kmax, s_wi[w]);
     int tok = 0;
-    if (kmax >= 0) {      // (a row without a finite entry: id 0)
+    if (greedy) {         // the first index, in vocabulary order, of the largest key (a row without a finite entry: id 0)
+        if (kmax >= 0) {
+            int first = 0x7fffffff;
+            for (int i0 = tid * 8; i0 < V; i0 += SP_NT * 8) {
+                uint32_t e[8];
+                sp_load8p<PEN>(row, pen, i0, V, vec, e);
+#pragma unroll
+                for (int j = 7; j >= 0; --j)
+                    if (sp_key(e[j]) == kmax) first = min(first, i0 + j);
+            }
+            first = sp_wave_min(first);
+            if (lane == 0) s_wl[wave] = first;
+            __syncthreads();
+            tok = s_wl[0];
+            for (int w = 1; w < SP_NW; ++w) tok = min(tok, s_wl[w]);
+        }
+    } else if (kmax >= 0) {      // (a row without a finite entry: id 0)
         const float m = sp_val(kmax);
         int kcut = 0;
         if (cut) {
@@ -215,7 +282,7 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
             if (s_kcut_k < 0) {      // no top-k cut-off yet: the negative half (uniform: shared value read after the scan's barrier)
                 for (int i = tid; i < SP_HALF; i += SP_NT) hist[i] = 0;
                 __syncthreads();
-                sp_for_row(row, V, vec, [&](int k) {
+                sp_for_row<PEN>(row, pen, V, vec, [&](int k) {
                     if (k >= 0 && k < 0x8000) atomicAdd(&hist[sp_slot(k)], 1u);
                 });
                 __syncthreads();
@@ -244,7 +311,7 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
                     if (!resident) {
                         if (tid < SP_KPT) mini[tid] = 0;
                         __syncthreads();
-                        sp_for_row(row, V, vec, [&](int k) {
+                        sp_for_row<PEN>(row, pen, V, vec, [&](int k) {
                             if (k >= key_lo && k < key_lo + SP_KPT) atomicAdd(&mini[k - key_lo], 1u);
                         });
                         __syncthreads();
@@ -282,7 +349,7 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
         for (int s0 = r0; s0 < r0 + region && s0 < V; s0 += SP_SLICE) {
             uint32_t e[8];
             const int i0 = s0 + lane * 8;
-            sp_load8(row, i0, V, vec, e);
+            sp_load8p<PEN>(row, pen, i0, V, vec, e);
             float s = 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -316,7 +383,7 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
             for (int s0 = r0; s0 < r0 + region && s0 < V && pick < 0; s0 += SP_SLICE) {
                 uint32_t e[8];
                 const int i0 = s0 + lane * 8;
-                sp_load8(row, i0, V, vec, e);
+                sp_load8p<PEN>(row, pen, i0, V, vec, e);
                 float wj[8], s = 0.f;
                 int lm = -1;
 #pragma unroll
@@ -362,6 +429,9 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
             // the step that produced this token consumed row `pos`: the NEXT fed token goes one row further (as the greedy head does)
             st[0] += 1; st[1] += 1;
             accept_token(tok, st, a.plan + 2 * b, a.ids_out + (long long)b * a.ids_ld, a.ids_ld, a.stop_ids, a.n_stop, a.done);
+            if constexpr (PEN) {      // the accepted token joins the row's seen set (tok < V: an index of the row)
+                if (a.seen) atomicOr(a.seen + (long long)b * a.ld_words + (tok >> 5), 1u << (tok & 31));
+            }
         } else {
             a.out[b] = tok;
         }
@@ -370,10 +440,28 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
 
 constexpr size_t SP_WORKSPACE = 256;      // the one-workgroup-per-row kernel keeps everything in LDS; the argument stays for a split form
 
-template <bool ACCEPT>
+template <bool ACCEPT, bool PEN>
 static int launch_sample(const SampleArgs& a, int B, hipStream_t st) {
-    FO1_DYNAMIC_LDS_ONCE(SP_SMEM, sample_rows_kernel<ACCEPT>);
-    FO1_LAUNCH(ACCEPT ? "sample_accept" : "sample_rows", (double)B * a.V * 2.0, sample_rows_kernel<ACCEPT>, dim3(B), dim3(SP_NT), SP_SMEM, st, a);
+    FO1_DYNAMIC_LDS_ONCE(SP_SMEM, sample_rows_kernel<ACCEPT, PEN>);
+    FO1_LAUNCH(PEN ? (ACCEPT ? "head_accept" : "sample_rows_seen") : (ACCEPT ? "sample_accept" : "sample_rows"), (double)B * a.V * 2.0,
+               (sample_rows_kernel<ACCEPT, PEN>), dim3(B), dim3(SP_NT), SP_SMEM, st, a);
+    return FO1_OK;
+}
+
+// (row, id) pairs -> bits of the seen bitmap; ids outside [0, V) and negative rows are skipped
+__global__ __launch_bounds__(256) void seen_mark_kernel(uint32_t* __restrict__ seen, long long ld_words, int V, const int* __restrict__ rows,
+                                                             const int* __restrict__ ids, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int r = rows[i], t = ids[i];
+    if (r < 0 || t < 0 || t >= V) return;
+    atomicOr(seen + (long long)r * ld_words + (t >> 5), 1u << (t & 31));
+}
+
+static int check_seen(const char* who, const void* seen, long long ld_words, int V) {
+    FO1_CHECK_ARG(!seen || (ld_words % 4 == 0 && ld_words >= ((long long)V + 31) / 32), "%s: ld_words=%lld (a multiple of 4, >= ceil(n_vocab / 32) = %d)", who,
+                  ld_words, (V + 31) / 32);
+    FO1_CHECK_ARG(!seen || ((uintptr_t)seen & 3) == 0, "%s: seen must be 4-byte aligned", who);
     return FO1_OK;
 }
 
@@ -401,7 +489,7 @@ int fo1_sample_rows_bf16(const void* logits, long long ld_logits, int n_vocab, i
     SampleArgs a{};
     a.logits = (const uint16_t*)logits; a.ld = ld_logits; a.V = n_vocab; a.params = params; a.counter = (const int*)counter;
     a.counter_stride = counter_stride; a.u = u; a.out = (int*)out;
-    return launch_sample<false>(a, B, (hipStream_t)stream);
+    return launch_sample<false, false>(a, B, (hipStream_t)stream);
 }
 
 // The sampled head of a decode step: pick (counter = state[b][4], the number of tokens generated so far) + the bookkeeping of
@@ -416,7 +504,51 @@ int fo1_decode_sample_accept(const void* logits, long long ld_logits, int n_voca
     a.logits = (const uint16_t*)logits; a.ld = ld_logits; a.V = n_vocab; a.params = params;
     a.state = (int*)state; a.plan = (int*)plan; a.ids_out = (int*)ids_out; a.ids_ld = ids_ld; a.stop_ids = (const int*)stop_ids; a.n_stop = n_stop;
     a.done = (int*)done;
-    return launch_sample<true>(a, B, (hipStream_t)stream);
+    return launch_sample<true, false>(a, B, (hipStream_t)stream);
+}
+
+// fo1_sample_rows_bf16 through the general head: a row's flags (FO1_SAMPLE_GREEDY) and repetition penalty are honoured.  seen: the bitmap
+// [rows >= B][ld_words]; NULL is allowed only when no row has the penalty on (the rows are device data: the host cannot check it — a row with
+// a penalty and no bitmap is sampled without it).
+int fo1_sample_rows_seen_bf16(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params, const int32_t* counter,
+                              int counter_stride, const float* u, int32_t* out, void* workspace, size_t workspace_bytes, const uint32_t* seen,
+                              long long ld_words, void* stream) {
+    using namespace fo1;
+    if (int rc = check_sample("sample_rows_seen", logits, ld_logits, n_vocab, B, params, workspace, workspace_bytes)) return rc;
+    if (int rc = check_seen("sample_rows_seen", seen, ld_words, n_vocab)) return rc;
+    FO1_CHECK_ARG(out != nullptr, "sample_rows_seen: NULL out");
+    SampleArgs a{};
+    a.logits = (const uint16_t*)logits; a.ld = ld_logits; a.V = n_vocab; a.params = params; a.counter = (const int*)counter;
+    a.counter_stride = counter_stride; a.u = u; a.out = (int*)out; a.seen = const_cast<uint32_t*>(seen); a.ld_words = ld_words;
+    return launch_sample<false, true>(a, B, (hipStream_t)stream);
+}
+
+// The general head of a decode step: fo1_decode_sample_accept's pick and bookkeeping with the row's flags and penalty honoured; the accepted
+// token's bit is set in row b of `seen` (when given).  A finished row touches nothing, its bitmap row included.
+int fo1_decode_head_accept(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params, int32_t* state,
+                           int32_t* plan, int32_t* ids_out, int ids_ld, const int32_t* stop_ids, int n_stop, int32_t* done, void* workspace,
+                           size_t workspace_bytes, uint32_t* seen, long long ld_words, void* stream) {
+    using namespace fo1;
+    if (int rc = check_sample("decode_head_accept", logits, ld_logits, n_vocab, B, params, workspace, workspace_bytes)) return rc;
+    if (int rc = check_seen("decode_head_accept", seen, ld_words, n_vocab)) return rc;
+    FO1_CHECK_ARG(state && plan && ids_out && done && ids_ld > 0 && n_stop >= -1 && (n_stop == 0 || stop_ids), "decode_head_accept: bad arguments");
+    SampleArgs a{};
+    a.logits = (const uint16_t*)logits; a.ld = ld_logits; a.V = n_vocab; a.params = params;
+    a.state = (int*)state; a.plan = (int*)plan; a.ids_out = (int*)ids_out; a.ids_ld = ids_ld; a.stop_ids = (const int*)stop_ids; a.n_stop = n_stop;
+    a.done = (int*)done; a.seen = seen; a.ld_words = ld_words;
+    return launch_sample<true, true>(a, B, (hipStream_t)stream);
+}
+
+// Sets bit ids[i] of row rows[i] of the seen bitmap for i < n (device int32 each; duplicates are fine).  Ids outside [0, n_vocab) and negative
+// rows are skipped; the caller vouches for rows[i] < the bitmap's rows.
+int fo1_seen_mark(uint32_t* seen, long long ld_words, int n_vocab, const int32_t* rows, const int32_t* ids, int n, void* stream) {
+    using namespace fo1;
+    FO1_CHECK_ARG(seen && n >= 0 && n_vocab >= 1 && (n == 0 || (rows && ids)), "seen_mark: bad arguments");
+    if (int rc = check_seen("seen_mark", seen, ld_words, n_vocab)) return rc;
+    if (n == 0) return FO1_OK;
+    FO1_LAUNCH("seen_mark", (double)n * 12.0, seen_mark_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, seen, ld_words,
+               n_vocab, (const int*)rows, (const int*)ids, n);
+    return FO1_OK;
 }
 
 }  // extern "C"

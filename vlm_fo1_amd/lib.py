@@ -273,6 +273,11 @@ SIGNATURES = {
     "fo1_sample_rows_bf16": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fo1_decode_sample_accept": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                          c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fo1_seen_mark": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "fo1_sample_rows_seen_bf16": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
+                                          c_longlong, c_void_p]),
+    "fo1_decode_head_accept": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                       c_void_p, c_void_p, c_size_t, c_void_p, c_longlong, c_void_p]),
     "fo1_kv_relocate": (c_int, [c_void_p, c_void_p, c_longlong, c_longlong, c_longlong, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong,
                                 c_longlong, c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "fo1_gather_rows_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,

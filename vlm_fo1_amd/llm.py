@@ -689,6 +689,34 @@ def empty_state_rows(bases):
     return [[b, 0, b, 1, 0, 0, 0, 0] for b in bases]
 
 
+def sampling_table(sampling, B: int):
+    """The `sampling` argument of BatchDecoder.start / DecodePool.join -> (rows, kinds): the 7-field rows of ops.sample_params, one per
+    sequence, and per sequence "plain" (None: greedy, no penalty), "sampled" (a draw, no penalty) or "general" (greedy flag or a penalty).
+    sampling: None; one dict for the submission (temperature, top_p, top_k, seed — optional when greedy=True — plus greedy,
+    repetition_penalty; sequence b draws on stream streams[b], or stream + b, default b); or a list with one such dict (its own `stream`,
+    default b) or None per sequence."""
+    if sampling is None:
+        per = [None] * B
+    elif isinstance(sampling, dict):
+        streams = list(sampling.get("streams") or [int(sampling.get("stream", 0)) + b for b in range(B)])
+        if len(streams) != B:
+            raise ValueError(f"sampling: {len(streams)} streams for {B} sequences")
+        per = [dict(sampling, stream=st) for st in streams]
+    else:
+        per = list(sampling)
+        if len(per) != B:
+            raise ValueError(f"sampling: {len(per)} entries for {B} sequences")
+    rows = [ops.sampling_row(sp, b) for b, sp in enumerate(per)]
+    kinds = ["plain" if sp is None else ("general" if (r[5] or ops.penalty_on(r[6])) else "sampled") for sp, r in zip(per, rows)]
+    return rows, kinds
+
+
+def new_seen(rows: int, n_vocab: int, dev) -> torch.Tensor:
+    """A cleared seen bitmap int32 [rows, ld_words] (csrc/sample.hip: bit t & 31 of word t >> 5 of row b = token t occurs in sequence b)."""
+    with torch.inference_mode(False):
+        return torch.zeros(rows, ops.seen_words(n_vocab), dtype=torch.int32, device=dev)
+
+
 class BatchDecoder:
     """Greedy decode of up to 32 sequences at once: the weights are streamed ONCE per step for all sequences
     (fo1_gemv_batch_bf16), 5 launches per layer, and the whole step — embedding gather, 36 layers, lm_head, argmax, stop check,
@@ -715,7 +743,9 @@ class BatchDecoder:
             self.stop = torch.zeros(self.MAX_STOP, dtype=torch.int32, device=dev)
             self.reloc = torch.zeros(2 * B, 4, dtype=torch.int32, device=dev)      # (a shared-prefix sequence moves in two pieces)
             self.sparams = torch.zeros(B, 8, dtype=torch.int32, device=dev)        # fo1_sample_params_t per sequence (sampled head)
-        self.sampled = False
+        self.sampled = False       # the step ends in a head that reads self.sparams (the sampled or the general one)
+        self.general = False       # ... in the general head: some row has the greedy flag or a repetition penalty
+        self.seen = None           # seen bitmap [MAX_BATCH, ld_words], allocated by the first start() with a penalty
         self.n_stop = 0
         self.dk = self.dvt = None
         self.rows = 0
@@ -741,12 +771,15 @@ class BatchDecoder:
             self.llm.grow_rope(slot)
             self._graphs = {}
 
-    def start(self, seqs, deltas, first_tokens: torch.Tensor, max_new_tokens: int, stop_ids: Sequence[int] = (), sampling: Optional[dict] = None):
+    def start(self, seqs, deltas, first_tokens: torch.Tensor, max_new_tokens: int, stop_ids: Sequence[int] = (), sampling=None,
+              prompt_ids: Optional[Sequence[Sequence[int]]] = None):
         """seqs: [(cache row offset, L, ...)] of the packed prefill that just ran on llm.kcache / llm.vtcache; first_tokens: device
         int32 [B] (the prefill's picks: greedy, or drawn with counter 0).  Moves every sequence to its own slot and accepts the first tokens
         on the device.  sampling: None = greedy steps; dict(temperature, top_p, top_k, seed[, streams]) = every step ends in the device
         sampler (fo1_decode_sample_accept), sequence b drawing Philox(tokens generated so far, streams[b]; seed) — streams defaults to
-        0 .. B - 1, the sequence's index in its request list."""
+        0 .. B - 1, the sequence's index in its request list.  A dict with greedy=True or a repetition_penalty, or a list with one dict or
+        None per sequence (sampling_table), ends every step in the general head (fo1_decode_head_accept); a penalty needs prompt_ids, the
+        ids each request passed: they and the first tokens seed the sequence's seen set (the caller picked the first tokens with it)."""
         llm = self.llm
         B = len(seqs)
         if B > self.MAX_BATCH:
@@ -773,18 +806,28 @@ class BatchDecoder:
         self.state[:B].copy_(state, non_blocking=True)
         self.stop.copy_(stop, non_blocking=True)
         self._keep = [reloc, state, stop]                 # sources of the async uploads stay alive
-        self.sampled = sampling is not None
+        srows, kinds = sampling_table(sampling, B)
+        self.sampled = any(k != "plain" for k in kinds)
+        self.general = self.sampled and any(k != "sampled" for k in kinds)
+        penalised = any(ops.penalty_on(r[6]) for r in srows)
+        if penalised and (prompt_ids is None or len(prompt_ids) != B):
+            raise ValueError("BatchDecoder: a repetition penalty needs prompt_ids, one list per sequence")
         if self.sampled:
-            streams = list(sampling.get("streams") or range(B))
-            assert len(streams) == B
-            sp = ops.sample_params([(sampling["temperature"], sampling["top_p"], sampling["top_k"], sampling["seed"], s) for s in streams])
+            sp = ops.sample_params(srows)
             self.sparams[:B].copy_(sp, non_blocking=True)
             self._keep.append(sp)
+        if penalised and self.seen is None:
+            self.seen = new_seen(self.MAX_BATCH, llm.cfg.vocab_size, llm.dev)
         self.done.zero_()
+        first = first_tokens.to(torch.int32).contiguous()
         with ops.workspace_scope(self._ws_owner):
             ops.kv_relocate(llm.kcache, self.dk, llm.vtcache, self.dvt, self.reloc[:nr], max(L for _, L, *_ in seqs))
-            ops.decode_argmax_accept(None, first_tokens.to(torch.int32).contiguous(), self.state[:B], self.plan[:B], self.ids[:B],
-                                     self.stop[:self.n_stop], self.done)
+            ops.decode_argmax_accept(None, first, self.state[:B], self.plan[:B], self.ids[:B], self.stop[:self.n_stop], self.done)
+            if penalised:      # the seen sets: the prompts' ids, then the first tokens
+                self._keep += ops.mark_prompts(self.seen, llm.cfg.vocab_size, list(range(B)), prompt_ids)
+                rt = torch.arange(B, dtype=torch.int32)
+                self._keep.append(rt)
+                ops.seen_mark(self.seen, llm.cfg.vocab_size, rt.to(first.device, non_blocking=True), first)
 
     KV_BUCKET = 2048
 
@@ -821,7 +864,9 @@ class BatchDecoder:
                 a = ops.gemv_batch(x, w["wgu"], mode=ops.GB_SWIGLU, norm_weight=w["ln2"], norm_eps=c.rms_norm_eps)
                 x = ops.gemv_batch(a, w["wdown"], residual=x)
             logits = ops.gemv_batch(x, llm.lm_head, norm_weight=llm.norm, norm_eps=c.rms_norm_eps)
-            if self.sampled:
+            if self.general:
+                ops.decode_head_accept(logits, self.sparams[:B], st, self.plan[:B], self.ids[:B], self.stop[:self.n_stop], self.done, seen=self.seen)
+            elif self.sampled:
                 ops.decode_sample_accept(logits, self.sparams[:B], st, self.plan[:B], self.ids[:B], self.stop[:self.n_stop], self.done)
             else:
                 ops.decode_argmax_accept(logits, None, st, self.plan[:B], self.ids[:B], self.stop[:self.n_stop], self.done)
@@ -836,9 +881,13 @@ class BatchDecoder:
         # the rope tables' identity is part of the key: QwenLLM.reserve() on a larger later batch or a sibling decoder may re-allocate
         # them (grow_rope) while this decoder's graphs survive — a replay would read the freed table
         key = (self.B, self.slot, self.n_stop, self.kv_bucket(), self.llm.rope_epoch, self.llm.rope_cos.data_ptr(), self.sampled)
+        seen = ()
+        if self.general:     # (one more form; the bitmap's identity is baked into its graph, and the warm-up step sets bits in it)
+            seen = () if self.seen is None else (self.seen,)
+            key += ("general", self.seen.data_ptr() if seen else 0)
         ent = self._graphs.get(key)
         if ent is None:      # (ops.capture_graph: the warm-up step is rolled back)
-            ent = self._graphs[key] = ops.capture_graph(self._step_device, rollback=(self.state, self.plan, self.ids, self.done))
+            ent = self._graphs[key] = ops.capture_graph(self._step_device, rollback=(self.state, self.plan, self.ids, self.done, *seen))
         ops.replay_graph(ent[0])
         self.steps += 1
         return ent[1]
@@ -929,6 +978,11 @@ class DecodePool:
             # with different stop ids / templates share the pool (before: one set per pool, anything else waited for a full drain)
             self.stop = torch.zeros(self.MAX_SETS, 1 + self.MAX_STOP, dtype=torch.int32, device=dev)
             self.reloc = torch.zeros(2 * P, 4, dtype=torch.int32, device=dev)     # (a shared-prefix sequence moves in two pieces)
+            # per-slot fo1_sample_params_t rows, read by the general head only: a plain slot rides as a greedy row without penalty
+            self.sparams = ops.sample_params([ops.sampling_row(None)] * P, dev)
+        self.seen = None                               # seen bitmap [P, ld_words], allocated when the first penalised sequence joins
+        self.kind = ["plain"] * P                      # what each slot's sparams row holds: "plain", "sampled" or "general"
+        self.n_general = 0                             # live slots that are not plain: > 0 ends the step in the general head
         self._sets: Dict[tuple, int] = {}              # stop-id tuple -> row of self.stop
         self._set_users = [0] * self.MAX_SETS          # live slots per row (a row with users is never rewritten)
         self.slot_set = [0] * P
@@ -975,11 +1029,21 @@ class DecodePool:
 
     # ---- join ------------------------------------------------------------------------------------------------------------------
     def join(self, kcache: torch.Tensor, vtcache: torch.Tensor, seqs, deltas, first_tokens: torch.Tensor, max_new_tokens: int,
-             stop_ids: Sequence[int] = (), tags: Optional[Sequence] = None) -> List[int]:
+             stop_ids: Sequence[int] = (), tags: Optional[Sequence] = None, sampling=None,
+             prompt_ids: Optional[Sequence[Sequence[int]]] = None) -> List[int]:
         """seqs [(cache row offset, L, ...)] of a packed prefill that ran on (kcache, vtcache); first_tokens device int32 [B].  Enqueues,
         on the CURRENT stream (the pool's), the relocation of every sequence into a free slot and the on-device accept of its first
-        token.  Returns the slots.  Raises if there is no room (callers check `len(pool.free)` / `fits()` first)."""
+        token.  Returns the slots.  Raises if there is no room (callers check `len(pool.free)` / `fits()` first).
+        sampling (sampling_table): None = plain greedy sequences, which join exactly as they always have; one dict for the submission or a
+        list with one dict or None per sequence = that sequence's row of the per-slot parameter table — temperature / top-k / top-p draws
+        on Philox(tokens generated so far, stream; seed), greedy=True, repetition_penalty.  A penalty needs prompt_ids (the ids each request
+        passed): the slot's seen-bitmap row is cleared and marked with them and with the first token, which the caller picked with the
+        prompt's set.  While any live slot is not plain the step ends in the general head (step())."""
         B = len(seqs)
+        srows, kinds = sampling_table(sampling, B)
+        penalised = [ops.penalty_on(r[6]) for r in srows]
+        if any(penalised) and (prompt_ids is None or len(prompt_ids) != B):
+            raise ValueError("DecodePool: a repetition penalty needs prompt_ids, one list per sequence")
         set_row = self._stop_set_row(tuple(stop_id_list(stop_ids, self.MAX_STOP, "DecodePool")))
         max_new = token_budget(max_new_tokens, self.IDS_CAP, "DecodePool")
         if B > len(self.free):
@@ -990,6 +1054,7 @@ class DecodePool:
         slots = [self.free.pop(0) for _ in range(B)]
         try:
             self._join_slots(slots, kcache, vtcache, seqs, deltas, first_tokens, max_new, set_row)
+            self._join_sampling(slots, srows, kinds, penalised, first_tokens, prompt_ids)
         except BaseException:
             # nothing of this submission is live: its slots go back (their device state may be half written — the next occupant's
             # join rewrites state, plan and K / V^T rows; until then the slot is marked finished so that no step reads it)
@@ -1010,7 +1075,30 @@ class DecodePool:
             self.budget[s] = max_new
             self.slot_set[s] = set_row
             self._set_users[set_row] += 1
+            self.n_general += kinds[k] != "plain"
         return slots
+
+    def _join_sampling(self, slots, srows, kinds, penalised, first_tokens, prompt_ids):
+        """The parameter rows and seen sets of a submission's slots.  Nothing is enqueued for a plain sequence whose slot still holds the
+        plain row: a pool that only ever sees plain sequences issues exactly the launches it always has."""
+        write = [k for k, s in enumerate(slots) if kinds[k] != "plain" or self.kind[s] != "plain"]
+        if write:
+            sp = ops.sample_params([srows[k] for k in write])
+            self._keep.append(sp)
+            for j, k in enumerate(write):
+                self.sparams[slots[k]:slots[k] + 1].copy_(sp[j:j + 1], non_blocking=True)
+                self.kind[slots[k]] = kinds[k]
+        pen = [k for k in range(len(slots)) if penalised[k]]
+        if pen:
+            V = self.llm.cfg.vocab_size
+            if self.seen is None:      # (a general-head graph captured without the bitmap is unreachable from here on: its key holds the pointer)
+                self.seen = new_seen(self.P, V, self.llm.dev)
+            first = first_tokens.to(torch.int32).contiguous()
+            rt = torch.tensor([slots[k] if penalised[k] else -1 for k in range(len(slots))], dtype=torch.int32)      # (row -1: skipped)
+            self._keep.append(rt)
+            with ops.workspace_scope(self._ws_owner):
+                self._keep += ops.mark_prompts(self.seen, V, [slots[k] for k in pen], [prompt_ids[k] for k in pen])
+                ops.seen_mark(self.seen, V, rt.to(first.device, non_blocking=True), first)
 
     def can_take(self, stop_ids: Sequence[int]) -> bool:
         """Is there a table row for this stop-id set (its own, or one no live slot uses)?"""
@@ -1089,7 +1177,12 @@ class DecodePool:
             self.llm._pool_tiled_w = t
         return t
 
-    def _step_device(self, bucket: int):
+    def graph_key(self, bucket: int) -> tuple:
+        """Key of the all-greedy step's graph (the general head's key is this plus a flag and the bitmap's identity)."""
+        # (the step's form is part of the key: FUSED_SPLITK / SPLITS may be set per pool, scripts/pool_bench.py and the A/B test do)
+        return (self.slot_rows, bucket, self.llm.rope_epoch, self.llm.rope_cos.data_ptr(), bool(self.FUSED_SPLITK), tuple(sorted(self.SPLITS.items())), bool(self.TILED_WEIGHTS))
+
+    def _step_device(self, bucket: int, general: bool = False):
         llm, P = self.llm, self.P
         c = llm.cfg
         H, KV, HD = c.num_heads, c.num_kv_heads, c.head_dim
@@ -1129,17 +1222,31 @@ class DecodePool:
                     a = ops.gemm(ops.rmsnorm(x, w["ln2"], c.rms_norm_eps), w["wgu"], act=ops.ACT_SWIGLU16)
                     x = ops.gemm(a, w["wdown"], residual=x)
                 logits = ops.gemm(ops.rmsnorm(x, llm.norm, c.rms_norm_eps), llm.lm_head)
-            ops.decode_argmax_accept(logits, None, st, self.plan, self.ids, self.stop, self.done, per_sequence_sets=True)
+            if general:      # plain slots ride as greedy rows without penalty; empty and finished slots return early, as in the greedy head
+                ops.decode_head_accept(logits, self.sparams, st, self.plan, self.ids, self.stop, self.done, seen=self.seen, per_sequence_sets=True)
+            else:
+                ops.decode_argmax_accept(logits, None, st, self.plan, self.ids, self.stop, self.done, per_sequence_sets=True)
             return logits
 
     def step(self, use_graph: bool = True):
-        """One token for every live sequence (all P rows are computed)."""
+        """One token for every live sequence (all P rows are computed).  The head: fo1_decode_argmax_accept while every live slot is plain
+        greedy, else the general head over all P rows (fo1_decode_head_accept) — the count changes in join() and harvest() only, so a
+        (bucket, step form) has at most one graph more."""
         bucket = self.kv_bucket()
+        general = self.n_general > 0
         if not use_graph:
-            out = self._step_device(bucket)
+            out = self._step_device(bucket, general)
+        elif general:
+            seen = () if self.seen is None else (self.seen,)
+            key = self.graph_key(bucket) + ("general", self.seen.data_ptr() if seen else 0)
+            ent = self._graphs.get(key)
+            if ent is None:      # (the warm-up step also sets bits of the bitmap: rolled back with the rest)
+                ent = self._graphs[key] = ops.capture_graph(lambda: self._step_device(bucket, True),
+                                                            rollback=(self.state, self.plan, self.ids, self.done, *seen))
+            ops.replay_graph(ent[0])
+            out = ent[1]
         else:
-            # (the step's form is part of the key: FUSED_SPLITK / SPLITS may be set per pool, scripts/pool_bench.py and the A/B test do)
-            key = (self.slot_rows, bucket, self.llm.rope_epoch, self.llm.rope_cos.data_ptr(), bool(self.FUSED_SPLITK), tuple(sorted(self.SPLITS.items())), bool(self.TILED_WEIGHTS))
+            key = self.graph_key(bucket)
             ent = self._graphs.get(key)
             if ent is None:
                 # (ops.capture_graph: the warm-up step is rolled back; the K / V^T rows it appended are the ones the first replay
@@ -1177,6 +1284,7 @@ class DecodePool:
                 del self.live[s]
                 self.free.append(s)
                 self._set_users[self.slot_set[s]] -= 1
+                self.n_general -= self.kind[s] != "plain"
         return out
 
     def drain(self, use_graph: bool = True, poll: int = 8) -> List[Tuple[int, object, List[int]]]:

@@ -514,40 +514,78 @@ class FO1Engine:
             self.llm.rope_delta = hp["delta"][0]
         return outs
 
+    def _per_request(self, sampling, n: int, base: int) -> list:
+        """`sampling` of n requests whose first has index `base` in its request list -> one dict (with its `stream`, default the request's
+        index) or None per request.  sampling: None, one dict for all, or a list with one dict or None per request."""
+        if sampling is None:
+            return [None] * n
+        if isinstance(sampling, dict):
+            common = {k: v for k, v in sampling.items() if k != "streams"}
+            return [dict(common, stream=base + i) for i in range(n)]
+        per = list(sampling)
+        if len(per) != n:
+            raise ValueError(f"sampling: {len(per)} entries for {n} requests")
+        return [None if sp is None else dict(sp, stream=sp.get("stream", base + i)) for i, sp in enumerate(per)]
+
+    def _first_tokens(self, per: list, requests: Sequence[dict]) -> torch.Tensor:
+        """The first token of every sequence of the pass that just ran, from the prefill's logits: its greedy picks when every request is
+        plain; else one launch of the device sampler with counter 0 — the general head (greedy rows, penalties against the prompts' seen
+        sets, marked into a scratch bitmap first) unless every row is a plain draw."""
+        from .llm import new_seen, sampling_table
+        n = len(requests)
+        rows, kinds = sampling_table(per, n)
+        if all(k == "plain" for k in kinds):
+            return self._last_next_tokens[:n]
+        with ops.workspace_scope(self._ws_owner):
+            table = ops.sample_params(rows, self.dev)
+            if all(k == "sampled" for k in kinds):
+                return ops.sample_rows(self._last_logits[:n], table)
+            seen = None
+            if any(ops.penalty_on(r[6]) for r in rows):
+                if getattr(self, "_seen_scratch", None) is None or self._seen_scratch.shape[0] < n:
+                    self._seen_scratch = new_seen(max(n, self.PREFILL_MAX), self.cfg.llm.vocab_size, self.dev)
+                seen = self._seen_scratch
+                self._seen_keep = ops.mark_prompts(seen, self.cfg.llm.vocab_size, list(range(n)), [r["ids"] for r in requests])
+            return ops.sample_rows(self._last_logits[:n], table, seen=seen, general=True)
+
     def generate_batch(self, requests: Sequence[dict], max_new_tokens: int = 512, stop_ids: Sequence[int] = (), use_graph: bool = True,
-                       sampling: Optional[dict] = None) -> List[List[int]]:
+                       sampling=None) -> List[List[int]]:
         """Generation for a batch of requests: one packed prefill, then the batched decode loop (vlm_fo1_amd.llm.BatchDecoder):
         weights streamed once per step for all sequences, stop rule and bookkeeping on the device.  Returns the new ids per request
         (stop token included, like HF generate).  sampling: None = greedy; dict(temperature, top_p, top_k, seed) = temperature / top-k / top-p
         sampling on the device (csrc/sample.hip): request i draws Philox(tokens generated so far, i; seed) — the first token from the prefill's
-        logits with counter 0.  Sampled batches take the BatchDecoder groups; the decode pool stays greedy."""
+        logits with counter 0.  A dict may also hold greedy=True and repetition_penalty, and a list gives every request
+        its own dict or None.  With the decode pool enabled every kind of request joins the pool; without it the BatchDecoder groups take
+        the same dicts."""
         from .llm import BatchDecoder, run_decoders
         out: List[List[int]] = []
         base = 0      # index of the pass's first request in the request list (the sampler's stream ids)
-        if sampling is None and getattr(self, "_pool_svc", None) is not None:
+        if getattr(self, "_pool_svc", None) is not None:
             # decode pool: every pass's sequences join the shared pool; this call's later passes prefill while its earlier ones decode
-            handles = [self.submit_batch(grp, max_new_tokens, stop_ids, use_graph) for grp in self.split_passes(requests)]
+            handles = []
+            for grp in self.split_passes(requests):
+                part = sampling if sampling is None or isinstance(sampling, dict) else list(sampling)[base:base + len(grp)]
+                handles.append(self.submit_batch(grp, max_new_tokens, stop_ids, use_graph, sampling=part, stream_base=base))
+                base += len(grp)
             for h in handles:
                 out += h.result()
             return out
         for grp in self.split_passes(requests):
             self.prefill_batch(grp, use_graph=use_graph)          # ONE packed pass for the whole group (its GEMMs see every image's rows)
             hp = self._last_batch
-            first = self._last_next_tokens
             n = len(grp)
+            per = self._per_request(sampling if sampling is None or isinstance(sampling, dict) else list(sampling)[base:base + n], n, base)
+            first = self._first_tokens(per, grp)
+            plain = all(sp is None for sp in per)
+            prompts = [r["ids"] for r in grp]
 
-            def samp(a, b, b0=base):      # the sampling of sequences a .. b of this pass
-                return None if sampling is None else dict(sampling, streams=list(range(b0 + a, b0 + b)))
-            if sampling is not None:
-                with ops.workspace_scope(self._ws_owner):
-                    s0 = samp(0, n)
-                    table = ops.sample_params([(s0["temperature"], s0["top_p"], s0["top_k"], s0["seed"], s) for s in s0["streams"]], self.dev)
-                    first = ops.sample_rows(self._last_logits[:n], table)
+            def samp(a, b):      # the sampling of sequences a .. b of this pass
+                return None if plain else per[a:b]
             base += n
             gmax = min(BatchDecoder.MAX_BATCH, self.DECODE_MAX_GROUP)
             if n <= gmax:
                 dec = self._decoder()
-                dec.start(hp["seqs"], hp["delta"], first[:n], max_new_tokens, stop_ids, sampling=samp(0, n))
+                dec.start(hp["seqs"], hp["delta"], first[:n], max_new_tokens, stop_ids, sampling=samp(0, n), prompt_ids=prompts)
                 out += dec.run(max_new_tokens, use_graph=use_graph)
                 continue
             # more sequences than one decode group carries (32 = two 16-column MFMA groups per weight fragment; DECODE_MAX_GROUP = 16
@@ -559,7 +597,7 @@ class FO1Engine:
                 dec = self._decoder()
                 for j in range(k):
                     a, b = cuts[j], cuts[j + 1]
-                    dec.start(hp["seqs"][a:b], hp["delta"][a:b], first[a:b], max_new_tokens, stop_ids, sampling=samp(a, b))
+                    dec.start(hp["seqs"][a:b], hp["delta"][a:b], first[a:b], max_new_tokens, stop_ids, sampling=samp(a, b), prompt_ids=prompts[a:b])
                     out += dec.run(max_new_tokens, use_graph=use_graph)
                 continue
             decs, streams = self._decoders(k)
@@ -568,7 +606,7 @@ class FO1Engine:
                 a, b = cuts[j], cuts[j + 1]
                 streams[j].wait_stream(cur)                       # the prefill (and its first tokens) are on the caller's stream
                 with torch.cuda.stream(streams[j]):
-                    decs[j].start(hp["seqs"][a:b], hp["delta"][a:b], first[a:b], max_new_tokens, stop_ids, sampling=samp(a, b))
+                    decs[j].start(hp["seqs"][a:b], hp["delta"][a:b], first[a:b], max_new_tokens, stop_ids, sampling=samp(a, b), prompt_ids=prompts[a:b])
             for ids in run_decoders(decs[:k], streams[:k], max_new_tokens, use_graph=use_graph):
                 out += ids
             for j in range(k):
@@ -598,18 +636,26 @@ class FO1Engine:
             svc.close()
         self._pool_svc = None
 
-    def submit_batch(self, requests: Sequence[dict], max_new_tokens: int = 512, stop_ids: Sequence[int] = (), use_graph: bool = True):
+    def submit_batch(self, requests: Sequence[dict], max_new_tokens: int = 512, stop_ids: Sequence[int] = (), use_graph: bool = True,
+                     sampling=None, stream_base: int = 0):
         """One packed prefill pass (<= PREFILL_MAX requests), then its sequences join the decode pool.  Returns a serving.PoolHandle as
         soon as the pool has taken the K / V^T rows over: the caller may start its next pass while these sequences decode;
-        handle.result() -> the new ids per request (stop token included, like HF generate)."""
+        handle.result() -> the new ids per request (stop token included, like HF generate).  sampling: as generate_batch, for this pass's
+        requests; request i draws on stream stream_base + i unless its dict names one.  The first tokens are drawn here from the prefill's
+        logits (counter 0, the prompt's seen set when a penalty is on), the pool draws the rest."""
         svc = getattr(self, "_pool_svc", None)
         if svc is None:
             raise RuntimeError("submit_batch needs enable_decode_pool()")
         if len(requests) > self.PREFILL_MAX:
             raise ValueError(f"submit_batch takes one prefill pass (<= {self.PREFILL_MAX} requests)")
+        per = self._per_request(sampling, len(requests), int(stream_base))
         self.prefill_batch(requests, use_graph=use_graph)
         hp = self._last_batch
-        h = svc.submit(self.llm, hp["seqs"], hp["delta"], self._last_next_tokens[:len(requests)], max_new_tokens, stop_ids)
+        if all(sp is None for sp in per):
+            h = svc.submit(self.llm, hp["seqs"], hp["delta"], self._last_next_tokens[:len(requests)], max_new_tokens, stop_ids)
+        else:
+            h = svc.submit(self.llm, hp["seqs"], hp["delta"], self._first_tokens(per, requests), max_new_tokens, stop_ids, sampling=per,
+                           prompt_ids=[list(r["ids"]) for r in requests])
         h.wait_relocated()
         return h
 

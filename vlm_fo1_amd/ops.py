@@ -957,14 +957,78 @@ def decode_argmax_accept(logits: Optional[torch.Tensor], first_tokens: Optional[
     _L.check(rc, "fo1_decode_argmax_accept")
 
 
+SAMPLE_GREEDY = 1      # fo1_sample_params_t.flags bit 0 (FO1_SAMPLE_GREEDY)
+
+
 def sample_params(rows: Sequence[Sequence], device=None) -> torch.Tensor:
-    """The fo1_sample_params_t table (int32 [B, 8] = 32 bytes per sequence) from rows of (temperature, top_p, top_k, seed, stream): seed is an
-    integer of up to 64 bits (the Philox key), stream the sequence's index in its request list.  On `device` when given, else a host tensor."""
+    """The fo1_sample_params_t table (int32 [B, 8] = 32 bytes per sequence) from rows of (temperature, top_p, top_k, seed, stream) or
+    (temperature, top_p, top_k, seed, stream, greedy, repetition_penalty): seed is an integer of up to 64 bits (the Philox key), stream the
+    sequence's index in its request list; greedy sets flags bit 0 and repetition_penalty (None = 0 = off) fills the last word, both read by the
+    general head only (sample_rows(seen=...), decode_head_accept).  On `device` when given, else a host tensor."""
     import struct
-    buf = b"".join(struct.pack("<ffiIIIII", float(t), float(p), int(k), int(seed) & 0xffffffff, (int(seed) >> 32) & 0xffffffff,
-                               int(stream) & 0xffffffff, 0, 0) for t, p, k, seed, stream in rows)
-    tab = torch.frombuffer(bytearray(buf), dtype=torch.int32).view(-1, 8)
+
+    def pack(r):
+        t, p, k, seed, stream = r[:5]
+        if len(r) == 5:
+            flags, rp = 0, 0.0
+        elif len(r) == 7:
+            flags, rp = (SAMPLE_GREEDY if r[5] else 0), float(r[6] or 0.0)
+        else:
+            raise ValueError("sample_params: a row has 5 fields, or 7 (..., greedy, repetition_penalty)")
+        return struct.pack("<ffiIIIIf", float(t), float(p), int(k), int(seed) & 0xffffffff, (int(seed) >> 32) & 0xffffffff,
+                           int(stream) & 0xffffffff, flags, rp)
+    tab = torch.frombuffer(bytearray(b"".join(pack(r) for r in rows)), dtype=torch.int32).view(-1, 8)
     return tab if device is None else tab.to(device)
+
+
+def sampling_row(s: Optional[dict], stream: int = 0):
+    """One sequence's sampling dict (temperature, top_p, top_k, seed, stream — optional when greedy — plus greedy, repetition_penalty) -> the
+    7-field row of sample_params; None = the plain greedy row.  `stream` is the default for a dict without one."""
+    if s is None:
+        return (0.0, 1.0, 0, 0, 0, True, 0.0)
+    greedy = bool(s.get("greedy", False))
+    if not greedy and "temperature" not in s:
+        raise ValueError("a sampled sequence needs a temperature (or greedy=True)")
+    return (s.get("temperature", 0.0), s.get("top_p", 1.0), s.get("top_k", 0), s.get("seed", 0), s.get("stream", stream), greedy,
+            s.get("repetition_penalty") or 0.0)
+
+
+def penalty_on(p) -> bool:
+    """The device's rule: a repetition penalty is on iff it is finite, > 0 and != 1."""
+    import math
+    return p is not None and math.isfinite(float(p)) and float(p) > 0 and float(p) != 1.0
+
+
+def seen_words(n_vocab: int) -> int:
+    """Words per row of a seen bitmap: ceil(V / 32) rounded up to a multiple of 4."""
+    return -(-(-(-int(n_vocab) // 32)) // 4) * 4
+
+
+def seen_mark(seen: torch.Tensor, n_vocab: int, rows: torch.Tensor, ids: torch.Tensor) -> None:
+    """Sets bit ids[i] of row rows[i] of the seen bitmap (int32 [R, ld_words], fo1_seen_mark); ids outside [0, n_vocab) are skipped."""
+    assert seen.dtype == torch.int32 and seen.is_cuda and seen.dim() == 2 and seen.is_contiguous()
+    assert rows.dtype == ids.dtype == torch.int32 and rows.is_cuda and ids.is_cuda and rows.is_contiguous() and ids.is_contiguous() and rows.numel() == ids.numel()
+    rc = _L.load().fo1_seen_mark(seen.data_ptr(), seen.shape[1], int(n_vocab), _ptr(rows), _ptr(ids), rows.numel(), _stream())
+    _L.check(rc, "fo1_seen_mark")
+
+
+def mark_prompts(seen: torch.Tensor, n_vocab: int, rows: Sequence[int], prompts: Sequence[Sequence[int]]) -> list:
+    """Clears the bitmap rows `rows` and marks row rows[k] with the ids of prompts[k] (ids outside [0, n_vocab) are skipped on the device) ->
+    the host tensors of the asynchronous uploads, for the caller to keep alive."""
+    r = torch.tensor([row for row, pr in zip(rows, prompts) for _ in pr], dtype=torch.int32)
+    t = torch.tensor([int(x) for pr in prompts for x in pr], dtype=torch.int64).clamp_(-1, int(n_vocab)).to(torch.int32)
+    for row in rows:
+        seen[row].zero_()
+    if r.numel():
+        seen_mark(seen, n_vocab, r.to(seen.device, non_blocking=True), t.to(seen.device, non_blocking=True))
+    return [r, t]
+
+
+def _seen_operand(seen: Optional[torch.Tensor], B: int, V: int):
+    if seen is None:
+        return None, 0
+    assert seen.dtype == torch.int32 and seen.is_cuda and seen.dim() == 2 and seen.is_contiguous() and seen.shape[0] >= B
+    return seen.data_ptr(), seen.shape[1]
 
 
 def _sample_operands(logits: torch.Tensor, params: torch.Tensor):
@@ -978,10 +1042,12 @@ def _sample_operands(logits: torch.Tensor, params: torch.Tensor):
 
 
 def sample_rows(logits: torch.Tensor, params: torch.Tensor, counter: Optional[torch.Tensor] = None, counter_stride: int = 1,
-                u: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                u: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, seen: Optional[torch.Tensor] = None,
+                general: bool = False) -> torch.Tensor:
     """int32 [B]: one sampled id per row of logits [B, V] bf16 (fo1_sample_rows_bf16): temperature / top-k / top-p per row from `params`
     (sample_params), draw = Philox(counter, stream; seed) with counter = counter[b * counter_stride] (device int32; None = 0), or the explicit
-    u [B] fp32."""
+    u [B] fp32.  seen (int32 [>= B, ld_words] bitmap) or general=True: the general head (fo1_sample_rows_seen_bf16), which also honours a
+    row's greedy flag and its repetition penalty; without a bitmap no row may have a penalty on."""
     head, tail = _sample_operands(logits, params)
     B = head[3]
     if out is None:
@@ -991,6 +1057,11 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, counter: Optional[to
         assert counter.dtype == torch.int32 and counter.is_cuda and counter.numel() > (B - 1) * counter_stride
     if u is not None:
         assert u.dtype == torch.float32 and u.is_cuda and u.is_contiguous() and u.numel() == B
+    if seen is not None or general:
+        ps, ldw = _seen_operand(seen, B, head[2])
+        rc = _L.load().fo1_sample_rows_seen_bf16(*head, _ptr(counter), int(counter_stride), _ptr(u), out.data_ptr(), *tail[:2], ps, ldw, tail[2])
+        _L.check(rc, "fo1_sample_rows_seen_bf16")
+        return out
     rc = _L.load().fo1_sample_rows_bf16(*head, _ptr(counter), int(counter_stride), _ptr(u), out.data_ptr(), *tail)
     _L.check(rc, "fo1_sample_rows_bf16")
     return out
@@ -1008,6 +1079,26 @@ def decode_sample_accept(logits: torch.Tensor, params: torch.Tensor, state: torc
     rc = _L.load().fo1_decode_sample_accept(*head, state.data_ptr(), plan.data_ptr(), ids_out.data_ptr(), ids_out.shape[1],
                                             stop_ids.data_ptr() if n_stop else None, n_stop, done.data_ptr(), *tail)
     _L.check(rc, "fo1_decode_sample_accept")
+
+
+def decode_head_accept(logits: torch.Tensor, params: torch.Tensor, state: torch.Tensor, plan: torch.Tensor, ids_out: torch.Tensor,
+                       stop_ids: Optional[torch.Tensor], done: torch.Tensor, seen: Optional[torch.Tensor] = None,
+                       per_sequence_sets: bool = False) -> None:
+    """The general head of a decode step (fo1_decode_head_accept): decode_sample_accept with each row's greedy flag and repetition penalty
+    honoured; the accepted token's bit is set in the row's `seen` bitmap (int32 [>= B, ld_words]; None only when no row has a penalty).
+    per_sequence_sets: as decode_argmax_accept."""
+    B = state.shape[0]
+    assert state.dtype == plan.dtype == ids_out.dtype == done.dtype == torch.int32 and ids_out.is_contiguous() and plan.is_contiguous()
+    assert state.is_contiguous() and logits.shape[0] == B
+    head, tail = _sample_operands(logits, params)
+    n_stop = int(stop_ids.numel()) if stop_ids is not None else 0
+    if per_sequence_sets:
+        assert stop_ids is not None and stop_ids.dim() == 2 and stop_ids.shape[1] == 17 and stop_ids.is_contiguous() and stop_ids.dtype == torch.int32
+        n_stop = -1
+    ps, ldw = _seen_operand(seen, B, head[2])
+    rc = _L.load().fo1_decode_head_accept(*head, state.data_ptr(), plan.data_ptr(), ids_out.data_ptr(), ids_out.shape[1],
+                                          stop_ids.data_ptr() if n_stop else None, n_stop, done.data_ptr(), *tail[:2], ps, ldw, tail[2])
+    _L.check(rc, "fo1_decode_head_accept")
 
 
 def kv_relocate(ksrc: torch.Tensor, kdst: torch.Tensor, vsrc: torch.Tensor, vdst: torch.Tensor, seqs: torch.Tensor, max_len: int) -> None:

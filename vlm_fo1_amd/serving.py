@@ -1,4 +1,4 @@
-"""Continuous batching of the greedy decode loop: ONE decode pool per GPU (llm.DecodePool: 64 / 128
+"""Continuous batching of the decode loop: ONE decode pool per GPU (llm.DecodePool: 64 / 128
 sequence slots advancing through one stream of the weights per step), fed by the packed prefill passes of any number of engine
 replicas.  The reference decodes one image at a time (`model.generate`, omchat_qwen2_5_vl.py:143-155 + HF greedy search); here a
 prefill pass of up to 32 images hands its sequences to the pool as soon as its first tokens exist and goes on with the next pass while
@@ -89,9 +89,11 @@ class PoolService:
             raise self._fatal
 
     # ---- caller side ----------------------------------------------------------------------------------------------------------
-    def submit(self, src_llm: QwenLLM, seqs, deltas, first_tokens: torch.Tensor, max_new_tokens: int, stop_ids: Sequence[int] = ()) -> PoolHandle:
+    def submit(self, src_llm: QwenLLM, seqs, deltas, first_tokens: torch.Tensor, max_new_tokens: int, stop_ids: Sequence[int] = (),
+               sampling=None, prompt_ids=None) -> PoolHandle:
         """Hand the sequences of a finished packed prefill (K / V^T in src_llm.kcache / vtcache at the packed rows `seqs`) to the pool.
-        The prefill must have been enqueued on the CURRENT stream: an event recorded here orders the pool's relocation after it."""
+        The prefill must have been enqueued on the CURRENT stream: an event recorded here orders the pool's relocation after it.
+        sampling / prompt_ids: per-sequence sampling and repetition penalty, as DecodePool.join takes them (None = plain greedy)."""
         if self._fatal is not None:
             raise self._fatal
         if self._closed or self._stop or not self._thread.is_alive():
@@ -102,7 +104,7 @@ class PoolService:
         h = PoolHandle(n)
         ev = torch.cuda.Event()
         ev.record()
-        self._q.put((h, src_llm.kcache, src_llm.vtcache, list(seqs), list(deltas), first_tokens, int(max_new_tokens), tuple(stop_ids), ev))
+        self._q.put((h, src_llm.kcache, src_llm.vtcache, list(seqs), list(deltas), first_tokens, int(max_new_tokens), tuple(stop_ids), ev, sampling, prompt_ids))
         if self._closed or not self._thread.is_alive():      # raced close() / the scheduler's fatal path: nobody will ever serve the queue
             self._fail_queued(self._fatal or RuntimeError("decode pool: closed while the submission was being queued"))
         return h
@@ -128,7 +130,7 @@ class PoolService:
     # ---- scheduler thread -----------------------------------------------------------------------------------------------------
     def _admit(self, pool: DecodePool, waiting: list) -> None:
         while waiting:
-            h, kc, vt, seqs, deltas, first, max_new, stop_ids, ev = waiting[0]
+            h, kc, vt, seqs, deltas, first, max_new, stop_ids, ev, sampling, prompt_ids = waiting[0]
             if len(seqs) > len(pool.free):
                 return
             if not pool.can_take(stop_ids):
@@ -138,7 +140,7 @@ class PoolService:
             waiting.pop(0)
             try:
                 torch.cuda.current_stream().wait_event(ev)       # the prefill that produced the rows and the first tokens
-                pool.join(kc, vt, seqs, deltas, first, max_new, stop_ids, tags=[(h, k) for k in range(len(seqs))])
+                pool.join(kc, vt, seqs, deltas, first, max_new, stop_ids, tags=[(h, k) for k in range(len(seqs))], sampling=sampling, prompt_ids=prompt_ids)
                 h._reloc_event = torch.cuda.Event()
                 h._reloc_event.record()
                 h._joined.set()
@@ -244,11 +246,12 @@ class PoolGroup:
         out["pools"] = len(self.services)
         return out
 
-    def submit(self, src_llm: QwenLLM, seqs, deltas, first_tokens: torch.Tensor, max_new_tokens: int, stop_ids: Sequence[int] = ()) -> PoolHandle:
+    def submit(self, src_llm: QwenLLM, seqs, deltas, first_tokens: torch.Tensor, max_new_tokens: int, stop_ids: Sequence[int] = (),
+               sampling=None, prompt_ids=None) -> PoolHandle:
         with self._lock:
             k = min(range(len(self.services)), key=lambda i: (self._submitted[i] - self.services[i].stats["finished"], i))
             self._submitted[k] += len(seqs)
-        return self.services[k].submit(src_llm, seqs, deltas, first_tokens, max_new_tokens, stop_ids)
+        return self.services[k].submit(src_llm, seqs, deltas, first_tokens, max_new_tokens, stop_ids, sampling=sampling, prompt_ids=prompt_ids)
 
     def close(self):
         for s in self.services:
