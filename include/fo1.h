@@ -26,7 +26,7 @@ extern "C" {
 #pragma GCC visibility push(default) /* libfo1hip*.so are built with -fvisibility=hidden: exactly the declarations of this header are exported */
 #endif
 
-#define FO1_ABI_VERSION 9   /* 9: (additive: fo1_seen_mark, fo1_sample_rows_seen_bf16, fo1_decode_head_accept — the general decode head: per-row greedy flag and repetition penalty in fo1_sample_params_t's former reserved words) (additive: fo1_sample_params_t, fo1_sample_rows_workspace_bytes, fo1_sample_rows_bf16, fo1_decode_sample_accept — the sampled decode head) fo1_window_attention_bf16 (DaViT window attention on the q/k/v rows: no V^T copy), fo1_window_attention_map_bf16 / _var (the same on un-partitioned pixel rows: no window partition / reverse), fo1_attention_windows_bf16 (single-tile work lists in a software pipeline; fo1_vit_plan_t.q_block_win 0 selects it); 8: fo1_attention_decode_batch_partials_bf16 + fo1_gemv_attn_combine_bf16 (decode step at <= 2 sequences: the o-projection sums the split-KV partials in its prologue, no combine launch); 7: fo1_vit_block_t gained wqkv_hm / bqkv_hm (optional head-major q/k/v copy: fo1_vit_forward then takes the fused q/k/v epilogue); 6: attention q_block 128 / 256 (32x32-MFMA prefill kernel); fo1_qkv_proj_rope_bf16 (q/k/v projection with RoPE / K append / V^T in the GEMM epilogue); fo1_gemm_bf16_wtiled, fo1_splitk_swiglu_bf16 (measured no-gain forms), fo1_mfma_clock_probe, fo1_gemm_profile_shapes (instruments) moved to fo1_ab.h; 5: split-K planes consumed by fused kernels in the decode pool (fo1_gemm_bf16_partials, fo1_splitk_residual_rmsnorm_bf16, fo1_pool_qkv_post_partials_bf16, fo1_splitk_swiglu_bf16), fo1_gemm_bf16_wtiled, fo1_mfma_clock_probe; 4: decode pool (fo1_pool_qkv_post_bf16; fo1_decode_argmax_accept up to 256 rows): continuous batching of 33..128 sequences; 3: fo1_hfre_opts_t grew out_bf16 / out_bf16_ld; fo1_img_seg + the *_var spatial entry points */
+#define FO1_ABI_VERSION 9   /* 9: (additive: FO1_LOGPROB_TOP_MAX, fo1_logprob_rows_bf16, fo1_decode_logprob_record — per-token log-probabilities and top-n alternatives of the decode loops) (additive: fo1_seen_mark, fo1_sample_rows_seen_bf16, fo1_decode_head_accept — the general decode head: per-row greedy flag and repetition penalty in fo1_sample_params_t's former reserved words) (additive: fo1_sample_params_t, fo1_sample_rows_workspace_bytes, fo1_sample_rows_bf16, fo1_decode_sample_accept — the sampled decode head) fo1_window_attention_bf16 (DaViT window attention on the q/k/v rows: no V^T copy), fo1_window_attention_map_bf16 / _var (the same on un-partitioned pixel rows: no window partition / reverse), fo1_attention_windows_bf16 (single-tile work lists in a software pipeline; fo1_vit_plan_t.q_block_win 0 selects it); 8: fo1_attention_decode_batch_partials_bf16 + fo1_gemv_attn_combine_bf16 (decode step at <= 2 sequences: the o-projection sums the split-KV partials in its prologue, no combine launch); 7: fo1_vit_block_t gained wqkv_hm / bqkv_hm (optional head-major q/k/v copy: fo1_vit_forward then takes the fused q/k/v epilogue); 6: attention q_block 128 / 256 (32x32-MFMA prefill kernel); fo1_qkv_proj_rope_bf16 (q/k/v projection with RoPE / K append / V^T in the GEMM epilogue); fo1_gemm_bf16_wtiled, fo1_splitk_swiglu_bf16 (measured no-gain forms), fo1_mfma_clock_probe, fo1_gemm_profile_shapes (instruments) moved to fo1_ab.h; 5: split-K planes consumed by fused kernels in the decode pool (fo1_gemm_bf16_partials, fo1_splitk_residual_rmsnorm_bf16, fo1_pool_qkv_post_partials_bf16, fo1_splitk_swiglu_bf16), fo1_gemm_bf16_wtiled, fo1_mfma_clock_probe; 4: decode pool (fo1_pool_qkv_post_bf16; fo1_decode_argmax_accept up to 256 rows): continuous batching of 33..128 sequences; 3: fo1_hfre_opts_t grew out_bf16 / out_bf16_ld; fo1_img_seg + the *_var spatial entry points */
 #define FO1_OK 0
 #define FO1_ERR_ARG (-1)       /* bad argument / unsupported shape */
 #define FO1_ERR_WORKSPACE (-2) /* workspace too small */
@@ -531,6 +531,30 @@ int fo1_sample_rows_seen_bf16(const void* logits, long long ld_logits, int n_voc
 int fo1_decode_head_accept(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params,
                            int32_t* state, int32_t* plan, int32_t* ids_out, int ids_ld, const int32_t* stop_ids, int n_stop,
                            int32_t* done, void* workspace, size_t workspace_bytes, uint32_t* seen, long long ld_words, void* stream);
+/* Log-probabilities of generated tokens.  For a bf16 logits row l[0..V) with F = { i : l_i finite }:
+ *   m = max_F l,  S = sum_{i in F} exp(l_i - m) (fp32, a fixed order),  lp_i = (l_i - m) - log S as fp32 for i in F,  lp_i = -inf otherwise
+ * (the sampler's rule: a non-finite entry has weight 0); a row with empty F gives -inf everywhere.  This is the log-softmax of the RAW logits:
+ * before temperature, top-k / top-p and the repetition penalty (HF's output_logits + compute_transition_scores, not the post-warper
+ * output_scores), so the record does not depend on the sampling parameters or on the head that picked the token.
+ *   chosen token: lp_c of the id c the head accepted; c outside [0, n_vocab) or l_c not finite gives -inf, never an out-of-range read.
+ *   top-n, 0 <= n <= FO1_LOGPROB_TOP_MAX: the n entries of F with the largest l, in descending order, equal logits by smaller vocabulary
+ *     index first, with their lp; fewer than n finite entries: padded with (id = -1, lp = -inf).
+ * One launch of one workgroup per row, B <= 256, no host read, no workspace, capturable; the same row gives the same bits whatever row b or
+ * batch B it sits in.  Columns [n_vocab, ld_logits) of a row are never read as data.
+ *   fo1_logprob_rows_bf16      row b: chosen id ids[b] -> lp_out[b]; top_n entries -> top_ids_out / top_lp_out[b * top_ld + k], k < top_n
+ *                              (top_n = 0: the top outputs may be NULL).  Scores the head of a prefill: the first token of every sequence.
+ *   fo1_decode_logprob_record  launched AFTER the head a decode step ends in (fo1_decode_argmax_accept, fo1_decode_sample_accept,
+ *                              fo1_decode_head_accept), on the same stream.  want[b] (device int32): -1 = off, the row returns before it
+ *                              touches the logits; 0 .. 8 = top-n.  With n = state[b][4] after the accept: n <= n_rec[b] or n > ids_ld means
+ *                              nothing was accepted this step (finished earlier, empty slot) and the row writes nothing; otherwise it scores
+ *                              c = ids[b][n - 1] on this step's logits, writes column n - 1 of lp[B][ids_ld] and of top_ids / top_lp
+ *                              [B][ids_ld][FO1_LOGPROB_TOP_MAX] (entries past the row's top-n: padding) and sets n_rec[b] = n. */
+#define FO1_LOGPROB_TOP_MAX 8
+int fo1_logprob_rows_bf16(const void* logits, long long ld_logits, int n_vocab, int B, const int32_t* ids /* [B] */, int top_n,
+                          float* lp_out /* [B] */, int32_t* top_ids_out, float* top_lp_out, long long top_ld, void* stream);
+int fo1_decode_logprob_record(const void* logits, long long ld_logits, int n_vocab, int B, const int32_t* want /* [B] */,
+                              const int32_t* state, const int32_t* ids, int ids_ld, int32_t* n_rec /* [B] */, float* lp, int32_t* top_ids,
+                              float* top_lp, void* stream);
 int fo1_kv_relocate(const void* ksrc, void* kdst, long long ks_layer, long long ks_head, long long kd_layer,
                     long long kd_head, const void* vsrc, void* vdst, long long vs_layer, long long vs_row,
                     long long vd_layer, long long vd_row, const int32_t* seqs, int B, int max_len, int n_kv_heads,

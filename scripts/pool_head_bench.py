@@ -3,11 +3,15 @@
 (the 3B shapes, 651-token prompts; scripts/pool_bench.py's workload), the step ending in
   greedy     fo1_decode_argmax_accept (every sequence plain greedy),
   sampled    the general head fo1_decode_head_accept, every sequence sampled (T = 0.7, top_k = 50, top_p = 0.9),
-  penalised  the same with repetition_penalty = 1.3 on every sequence (seen bitmap read in every pass).
+  penalised  the same with repetition_penalty = 1.3 on every sequence (seen bitmap read in every pass),
+  greedy_lp0 / greedy_lp8   the greedy head followed by the log-probability record (fo1_decode_logprob_record), every sequence asking for
+             it with top-n = 0 / 8.
 The heads are timed alternately, `--rounds` times each in one process, so the spread of a figure is the spread between its rounds; the pool is
 drained and re-joined for every timing.  Prints one JSON object.
 
-    python scripts/pool_head_bench.py [--slots 128] [--steps 64] [--rounds 5] [--heads greedy sampled penalised] [--root DIR]
+    python scripts/pool_head_bench.py [--slots 128] [--steps 64] [--rounds 5] [--heads greedy sampled penalised greedy_lp0 greedy_lp8] [--root DIR]
+
+With `greedy` among the heads the output also holds each other head's increment over it (difference of the medians of this process).
 
 --root DIR imports the package from another checkout (e.g. the parent commit, for the greedy figure of both on one box; only `greedy`
 exists there)."""
@@ -26,7 +30,8 @@ def main():
     ap.add_argument("--slots", type=int, default=128)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--heads", nargs="+", default=["greedy", "sampled", "penalised"], choices=["greedy", "sampled", "penalised"])
+    HEADS = ["greedy", "sampled", "penalised", "greedy_lp0", "greedy_lp8"]
+    ap.add_argument("--heads", nargs="+", default=HEADS[:3], choices=HEADS)
     ap.add_argument("--root", default=None, help="import vlm_fo1_amd from this checkout instead of the script's own")
     args = ap.parse_args()
     sys.path.insert(0, HERE)                 # bench.py (the workload builder)
@@ -44,12 +49,14 @@ def main():
     eng.prefill_batch(pipe.requests, use_graph=False)
     torch.cuda.synchronize()
     hp, first = eng._last_batch, eng._last_next_tokens.clone()
+    logits0 = eng._last_logits.clone()       # the first tokens' records are scored on the prefill's logits
     prompts = [list(r["ids"]) for r in pipe.requests]
     P = args.slots
     pool = DecodePool(eng.llm, slots=P)
     sampling = dict(greedy=None,
                     sampled=dict(temperature=0.7, top_p=0.9, top_k=50, seed=11),
-                    penalised=dict(temperature=0.7, top_p=0.9, top_k=50, seed=11, repetition_penalty=1.3))
+                    penalised=dict(temperature=0.7, top_p=0.9, top_k=50, seed=11, repetition_penalty=1.3), greedy_lp0=None, greedy_lp8=None)
+    top_n = dict(greedy_lp0=0, greedy_lp8=8)
     budget = 4 + args.steps + 8
 
     def one(head):
@@ -57,6 +64,9 @@ def main():
         while left > 0:
             n = min(32, left)
             kw = {} if sampling[head] is None else dict(sampling=dict(sampling[head], stream=base), prompt_ids=prompts[:n])
+            if head in top_n:
+                from vlm_fo1_amd import ops
+                kw.update(logprobs=top_n[head], first_logprobs=ops.logprob_rows(logits0[:n], first[:n].to(torch.int32).contiguous(), top_n[head]))
             pool.join(eng.llm.kcache, eng.llm.vtcache, hp["seqs"][:n], hp["delta"][:n], first[:n], budget, (), **kw)
             left -= n
             base += n
@@ -85,6 +95,8 @@ def main():
     for h, v in times.items():
         out["heads"][h] = dict(ms_per_step=v, median=round(statistics.median(v), 4), min=min(v), max=max(v),
                                spread_pct=round(100.0 * (max(v) - min(v)) / statistics.median(v), 3))
+    if "greedy" in times:
+        out["increment_over_greedy_ms"] = {h: round(out["heads"][h]["median"] - out["heads"]["greedy"]["median"], 4) for h in times if h != "greedy"}
     print(json.dumps(out))
 
 

@@ -87,6 +87,14 @@ class FO1HFConfig:
         return list(e) if isinstance(e, (list, tuple)) else [int(e)]
 
 
+class GenerateLogprobsOutput:
+    """What generate(output_logprobs=True) returns: .sequences = the tensor generate() returns otherwise ([1, L_in + new]), .logprobs float32
+    [1, new], .top_ids int64 [1, new, n] and .top_logprobs float32 [1, new, n] with n = top_logprobs."""
+
+    def __init__(self, sequences, logprobs, top_ids, top_logprobs):
+        self.sequences, self.logprobs, self.top_ids, self.top_logprobs = sequences, logprobs, top_ids, top_logprobs
+
+
 class _TowerHandle:
     """What callers get from `get_vision_tower()` / `get_vision_tower_aux()`: loaded flag, config, processor."""
 
@@ -263,13 +271,35 @@ class FO1ForCausalLM:
             return sampling
         return dict(greedy=True, repetition_penalty=pen) if sampling is None else dict(sampling, repetition_penalty=pen)
 
+    @staticmethod
+    def _logprob_plan(kwargs: dict) -> Optional[int]:
+        """generate()'s output_logprobs / top_logprobs -> None (off, the default) or the top-n (0 .. 8) of the record the engine keeps."""
+        on = bool(kwargs.get("output_logprobs", False))
+        n = kwargs.get("top_logprobs", 0)
+        n = 0 if n is None else n
+        from vlm_fo1_amd.ops import LOGPROB_TOP_MAX
+        if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= LOGPROB_TOP_MAX:
+            raise ValueError(f"top_logprobs must be an integer in 0..{LOGPROB_TOP_MAX} (got {n!r})")
+        if n and not on:
+            raise ValueError("top_logprobs needs output_logprobs=True")
+        return n if on else None
+
+    @staticmethod
+    def _with_logprobs(sequences: torch.Tensor, rec) -> "GenerateLogprobsOutput":
+        dev = sequences.device
+        return GenerateLogprobsOutput(sequences=sequences, logprobs=rec.logprob.unsqueeze(0).to(dev),
+                                      top_ids=rec.top_ids.to(torch.int64).unsqueeze(0).to(dev), top_logprobs=rec.top_logprobs.unsqueeze(0).to(dev))
+
     def _batch_plan(self, requests_kwargs: List[dict]):
         """Validation shared by generate_many / generate_many_async -> (engine requests, max_new_tokens, device stop ids, sampling), or None
         when the batch must take the one-by-one host loop (a stop criterion the device rule cannot express, a budget beyond its id buffer).
+        Requests may differ in output_logprobs / top_logprobs, pool or not (they are checked here; the callers read them per request).
         sampling: None, the batch's one dict, or — with the decode pool enabled, whose slots each carry their own parameters — a list with
         one dict or None per request when the requests differ (request i draws on stream i of its own seed)."""
         k0 = requests_kwargs[0]
         gen = getattr(self.config, "_gen", None)
+        for kw in requests_kwargs:
+            self._logprob_plan(kw)
         stop = self._device_stop_ids(k0.get("stopping_criteria"))
         if stop is None or not self._fits_device_loop(k0.get("max_new_tokens", 512)):
             return None
@@ -299,13 +329,15 @@ class FO1ForCausalLM:
         return reqs, int(k0.get("max_new_tokens", 512)), stop, sampling
 
     @staticmethod
-    def _assemble(requests_kwargs, reqs, new) -> List[torch.LongTensor]:
+    def _assemble(requests_kwargs, reqs, new, recs=None) -> list:
         out = []
-        for kw, req, ids in zip(requests_kwargs, reqs, new):
+        for i, (kw, req, ids) in enumerate(zip(requests_kwargs, reqs, new)):
             inp = kw["inputs"]
             # [1, L_in + new] on the inputs' device, like HF generate — assembled on the host from the id lists both sides already hold
             # (one upload per request instead of an upload, a device concat and a read back)
-            out.append(torch.tensor([list(req["ids"]) + list(ids)], dtype=inp.dtype).to(inp.device))
+            seq = torch.tensor([list(req["ids"]) + list(ids)], dtype=inp.dtype).to(inp.device)
+            rec = None if recs is None else recs[i]
+            out.append(seq if rec is None else FO1ForCausalLM._with_logprobs(seq, rec))      # (a request with output_logprobs: the object generate() returns)
         return out
 
     @torch.no_grad()
@@ -324,8 +356,12 @@ class FO1ForCausalLM:
                 return [self.generate(**kw) for kw in requests_kwargs]
             return [self.generate(**dict(kw, seed=sampling["seed"]), _stream=i) for i, kw in enumerate(requests_kwargs)]
         reqs, max_new, stop, sampling = plan
-        new = self.engine.generate_batch(reqs, max_new_tokens=max_new, stop_ids=stop, use_graph=self.use_graph, sampling=sampling)
-        return self._assemble(requests_kwargs, reqs, new)
+        lps = [self._logprob_plan(kw) for kw in requests_kwargs]
+        if all(n is None for n in lps):
+            new = self.engine.generate_batch(reqs, max_new_tokens=max_new, stop_ids=stop, use_graph=self.use_graph, sampling=sampling)
+            return self._assemble(requests_kwargs, reqs, new)
+        new, recs = self.engine.generate_batch(reqs, max_new_tokens=max_new, stop_ids=stop, use_graph=self.use_graph, sampling=sampling, logprobs=lps)
+        return self._assemble(requests_kwargs, reqs, new, recs)
 
     @torch.no_grad()
     def generate_many_async(self, requests_kwargs: List[dict]):
@@ -347,32 +383,39 @@ class FO1ForCausalLM:
         if plan is None:
             return _Ready(self.generate_many(requests_kwargs))
         reqs, max_new, stop, sampling = plan      # (sampled and penalised requests join the pool too: every slot has its own parameters)
+        lps = [self._logprob_plan(kw) for kw in requests_kwargs]
         handles, base = [], 0
         for grp in eng.split_passes(reqs):        # <= 32 requests and <= 64k ViT rows per pass
             part = sampling if sampling is None or isinstance(sampling, dict) else sampling[base:base + len(grp)]
-            handles.append(eng.submit_batch(grp, max_new, stop, self.use_graph, sampling=part, stream_base=base))
+            lpart = lps[base:base + len(grp)]
+            handles.append(eng.submit_batch(grp, max_new, stop, self.use_graph, sampling=part, stream_base=base,
+                                            logprobs=None if all(n is None for n in lpart) else lpart))
             base += len(grp)
         model = self
 
         class _Pending:
             def result(self):
                 new = [ids for h in handles for ids in h.result()]
-                return model._assemble(requests_kwargs, reqs, new)
+                recs = [r for h in handles for r in h.logprobs()]
+                return model._assemble(requests_kwargs, reqs, new, recs)
 
         return _Pending()
 
-    def _generate_sampled_host_loop(self, req, inputs, sampling, n_max, streamer, stopping_criteria, stream=0) -> torch.LongTensor:
+    def _generate_sampled_host_loop(self, req, inputs, sampling, n_max, streamer, stopping_criteria, stream=0, logprobs=None):
         """Sampled decoding with the tokens handed to the host one by one (a streamer, or stop criteria the device rule cannot express): a
         BatchDecoder of ONE sequence stepped token by token — the kernels of the device loop, so the same seed draws the same ids whether or
         not a streamer listens (the single-sequence step of QwenLLM runs other GEMV / attention kernels: its logits differ in last bits, and
-        a draw near an interval's end would then fall on the neighbouring token)."""
+        a draw near an interval's end would then fall on the neighbouring token).  logprobs: the top-n of the log-probability record (None = off);
+        a requesting generation takes this loop whatever its head, plain greedy as dict(greedy=True): the record launch belongs to the
+        BatchDecoder's step, the single-sequence step of QwenLLM has none."""
         eng, dev = self.engine, self.device
         eng.prefill_batch([req], use_graph=self.use_graph)
         hp = eng._last_batch
         per = [dict(sampling, stream=stream)]      # (a greedy request with a repetition penalty takes this loop too: dict(greedy=True, ...))
         tok = eng._first_tokens(per, [req])
         dec = eng._decoder()
-        dec.start(hp["seqs"], hp["delta"], tok, n_max, (), sampling=per, prompt_ids=[req["ids"]])
+        lpa = {} if logprobs is None else dict(logprobs=logprobs, first_logprobs=eng._first_logprobs(logprobs, tok, 1))
+        dec.start(hp["seqs"], hp["delta"], tok, n_max, (), sampling=per, prompt_ids=[req["ids"]], **lpa)
         eos = set(self.config.eos_ids())
         all_ids = inputs.to(dev)
         if streamer is not None:
@@ -391,12 +434,13 @@ class FO1ForCausalLM:
             tok = dec.plan[0, 1:2]          # the id the step accepted (its next embedding-gather entry)
         if streamer is not None:
             streamer.end()
-        return all_ids.to(inputs.device)
+        out = all_ids.to(inputs.device)
+        return out if logprobs is None else self._with_logprobs(out, dec.logprobs()[0])
 
     @torch.no_grad()
     def generate(self, inputs=None, images=None, images_aux=None, image_grid_thws=None, bbox_list=None, do_sample=False,
                  temperature=0.0, max_new_tokens=512, streamer=None, top_p=1.0, use_cache=True, stopping_criteria=None,
-                 pad_token_id=None, top_k=None, seed=None, repetition_penalty=None, _stream=0, **unused) -> torch.LongTensor:
+                 pad_token_id=None, top_k=None, seed=None, repetition_penalty=None, _stream=0, output_logprobs=False, top_logprobs=0, **unused):
         """Decoding of one prompt: greedy, or with do_sample=True temperature / top-k / top-p sampling on the device (_sampling_plan).
         Returns [1, L_in + new] like HF generate (the reference slices `output_ids[0, inputs.shape[1]:]`, inference.py:47-48).  Without a
         streamer and with id-set stop criteria the whole loop runs on the device (BatchDecoder, no per-token host read); otherwise tokens
@@ -404,7 +448,16 @@ class FO1ForCausalLM:
         generation records its ids in the BatchDecoder's buffer: max_new_tokens beyond BatchDecoder.IDS_CAP is a ValueError.  _stream: the
         Philox stream of the draws (generate_many's one-by-one loop passes the request's index).  repetition_penalty: None or 1.0 = off
         (the default, whatever generation_config.json holds); else HF's RepetitionPenaltyLogitsProcessor in front of the pick, over the
-        prompt's and the generated ids, on the device; not finite or <= 0 is a ValueError."""
+        prompt's and the generated ids, on the device; not finite or <= 0 is a ValueError.
+        output_logprobs=True: returns a GenerateLogprobsOutput instead of the tensor — .sequences (that tensor), .logprobs float32 [1, new]
+        (log-probability of every generated token under the model's own distribution: the log-softmax of the raw logits, before temperature,
+        top-k / top-p and the penalty), .top_ids int64 / .top_logprobs float32 [1, new, top_logprobs] (the most likely tokens of each step,
+        0 <= top_logprobs <= 8).  The records are kept in the BatchDecoder's buffers: max_new_tokens beyond IDS_CAP is a ValueError, and with
+        a streamer or unexpressible stop criteria the generation steps a BatchDecoder of one (the same ids and records either way)."""
+        lpn = self._logprob_plan(dict(output_logprobs=output_logprobs, top_logprobs=top_logprobs))
+        if lpn is not None and not self._fits_device_loop(max_new_tokens):
+            from vlm_fo1_amd.llm import BatchDecoder
+            raise ValueError(f"output_logprobs=True keeps at most {BatchDecoder.IDS_CAP} records per request (max_new_tokens={int(max_new_tokens)})")
         sampling = self._decode_plan(dict(do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k, seed=seed,
                                           repetition_penalty=repetition_penalty), getattr(self.config, "_gen", None))
         req = self._request(inputs, images, images_aux, image_grid_thws, bbox_list)
@@ -414,11 +467,15 @@ class FO1ForCausalLM:
             from vlm_fo1_amd.llm import BatchDecoder
             raise ValueError(f"do_sample=True (and a repetition penalty) draws at most {BatchDecoder.IDS_CAP} tokens per request (max_new_tokens={int(max_new_tokens)})")
         if stop is not None and (sampling is None or _stream == 0 or sampling.get("greedy")) and self._fits_device_loop(max_new_tokens):
-            ids = self.engine.generate_batch([req], max_new_tokens=int(max_new_tokens), stop_ids=stop, use_graph=self.use_graph, sampling=sampling)[0]
-            return torch.cat([inputs.to(dev), torch.tensor([ids], dtype=inputs.dtype, device=dev)], dim=1).to(inputs.device)
+            res = self.engine.generate_batch([req], max_new_tokens=int(max_new_tokens), stop_ids=stop, use_graph=self.use_graph, sampling=sampling,
+                                             logprobs=lpn)
+            ids = res[0] if lpn is None else res[0][0]
+            seq = torch.cat([inputs.to(dev), torch.tensor([ids], dtype=inputs.dtype, device=dev)], dim=1).to(inputs.device)
+            return seq if lpn is None else self._with_logprobs(seq, res[1][0])
         eng = self.engine
-        if sampling is not None:
-            return self._generate_sampled_host_loop(req, inputs, sampling, int(max_new_tokens), streamer, stopping_criteria, int(_stream))
+        if sampling is not None or lpn is not None:
+            return self._generate_sampled_host_loop(req, inputs, sampling if sampling is not None else dict(greedy=True), int(max_new_tokens),
+                                                    streamer, stopping_criteria, int(_stream), logprobs=lpn)
         out = eng.prefill(req["ids"], req["pix"], req["grid"], req["aux"], req["boxes"], use_graph=self.use_graph)
         eng.llm.reserve(eng.llm.kv_len + int(max_new_tokens))
         tok = out["next_token"]

@@ -153,6 +153,42 @@ __device__ __forceinline__ void accept_token(int tok, int* st, int* plan, int* i
     }
 }
 
+// ---- what the heads that read a bf16 logits row share (sample.hip: the sampled / general head; logprob.hip: the log-probability record) ----
+// bf16 bits -> order-preserving key 0 .. 65535 (larger value = larger key; -0 = +0), -1 for inf / NaN
+__device__ __forceinline__ int sp_key(uint32_t b) {
+    if ((b & 0x7f80u) == 0x7f80u) return -1;
+    if (b == 0x8000u) b = 0;
+    return (int)((b & 0x8000u) ? (b ^ 0xffffu) : (b | 0x8000u));
+}
+__device__ __forceinline__ float sp_val(int key) {
+    const uint32_t b = key >= 0x8000 ? (uint32_t)(key & 0x7fff) : ((uint32_t)key ^ 0xffffu);
+    return __uint_as_float(b << 16);
+}
+// one 16-byte chunk of a row -> its 8 entries as bf16 bits
+__device__ __forceinline__ void sp_unpack8(const uint4& v, uint32_t (&e)[8]) {
+    e[0] = v.x & 0xffffu; e[1] = v.x >> 16; e[2] = v.y & 0xffffu; e[3] = v.y >> 16;
+    e[4] = v.z & 0xffffu; e[5] = v.z >> 16; e[6] = v.w & 0xffffu; e[7] = v.w >> 16;
+}
+// tokens [i0, i0 + 8) of the row as bf16 bits; past the row's end: NaN (no key).  `vec`: the row is 16-byte aligned.
+__device__ __forceinline__ void sp_load8(const uint16_t* __restrict__ row, int i0, int V, bool vec, uint32_t (&e)[8]) {
+    if (vec && i0 + 8 <= V) {
+        sp_unpack8(*reinterpret_cast<const uint4*>(row + i0), e);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) e[j] = i0 + j < V ? (uint32_t)row[i0 + j] : 0x7fc0u;
+    }
+}
+
+// inclusive scan over the 64 lanes of a wave, lane order (Hillis-Steele: a fixed tree, the same bits every run)
+__device__ __forceinline__ float sp_scan_f(float v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float t = __shfl_up(v, o, 64);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+
 // decode_mfma.hip
 #ifdef FO1_ENABLE_AB
 extern int g_gemv_half;   // decode_mfma.hip: bit 0 = 8-row units at M <= 8 (HALF), bit 1 = at 9..32 sequences (R8)

@@ -39,32 +39,10 @@ constexpr int SP_KPT = SP_HALF / SP_NT;     // keys per thread in the key scan (
 constexpr int SP_SLICE = 512;               // tokens per wave slice of the pick: 8 per lane
 constexpr int SP_SMEM = SP_HALF * 4 + (2 * SP_NT + 4) * 4;      // counters + the exclusive mass in front of every 32-key range (+ the total)
 
-// bf16 bits -> order-preserving key 0 .. 65535 (larger value = larger key; -0 = +0), -1 for inf / NaN
-__device__ __forceinline__ int sp_key(uint32_t b) {
-    if ((b & 0x7f80u) == 0x7f80u) return -1;
-    if (b == 0x8000u) b = 0;
-    return (int)((b & 0x8000u) ? (b ^ 0xffffu) : (b | 0x8000u));
-}
-__device__ __forceinline__ float sp_val(int key) {
-    const uint32_t b = key >= 0x8000 ? (uint32_t)(key & 0x7fff) : ((uint32_t)key ^ 0xffffu);
-    return __uint_as_float(b << 16);
-}
 // counter slot of a half's key: rotated inside each thread's 32-key range, so the 64 threads of a wave walking their ranges hit 32 banks
 __device__ __forceinline__ int sp_slot(int local) { return (local & ~31) | ((local + (local >> 5)) & 31); }
 
 __device__ __forceinline__ float sp_weight(int key, float m, float inv_t) { return expf((sp_val(key) - m) * inv_t); }
-
-// tokens [i0, i0 + 8) of the row as bf16 bits; past the row's end: NaN (no key).  `vec`: the row is 16-byte aligned.
-__device__ __forceinline__ void sp_load8(const uint16_t* __restrict__ row, int i0, int V, bool vec, uint32_t (&e)[8]) {
-    if (vec && i0 + 8 <= V) {
-        const uint4 v = *reinterpret_cast<const uint4*>(row + i0);
-        e[0] = v.x & 0xffffu; e[1] = v.x >> 16; e[2] = v.y & 0xffffu; e[3] = v.y >> 16;
-        e[4] = v.z & 0xffffu; e[5] = v.z >> 16; e[6] = v.w & 0xffffu; e[7] = v.w >> 16;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) e[j] = i0 + j < V ? (uint32_t)row[i0 + j] : 0x7fc0u;
-    }
-}
 
 // what the penalty needs of a row: its seen bitmap (bytes: bit j of byte i0 / 8 = token i0 + j, i0 a multiple of 8) and p; seen == NULL: off
 struct SpPen {
@@ -106,15 +84,6 @@ __device__ __forceinline__ void sp_for_row(const uint16_t* __restrict__ row, con
     }
 }
 
-// inclusive scan over the 64 lanes of a wave, lane order (Hillis-Steele: a fixed tree, the same bits every run)
-__device__ __forceinline__ float sp_scan_f(float v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
 __device__ __forceinline__ int sp_scan_i(int v, int lane) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {

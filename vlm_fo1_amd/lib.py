@@ -278,6 +278,9 @@ SIGNATURES = {
                                           c_longlong, c_void_p]),
     "fo1_decode_head_accept": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                        c_void_p, c_void_p, c_size_t, c_void_p, c_longlong, c_void_p]),
+    "fo1_logprob_rows_bf16": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
+    "fo1_decode_logprob_record": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p]),
     "fo1_kv_relocate": (c_int, [c_void_p, c_void_p, c_longlong, c_longlong, c_longlong, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong,
                                 c_longlong, c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "fo1_gather_rows_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -717,6 +717,81 @@ def new_seen(rows: int, n_vocab: int, dev) -> torch.Tensor:
         return torch.zeros(rows, ops.seen_words(n_vocab), dtype=torch.int32, device=dev)
 
 
+class LogprobRecord(NamedTuple):
+    """What a request with `logprobs=n` gets back per sequence (host tensors; `new` = generated tokens, the first included): the
+    log-probability of each generated token under the model's own distribution (the log-softmax of the raw logits) and
+    the n most likely tokens of each step with theirs, descending, (id = -1, -inf) where a step had fewer than n finite logits."""
+    logprob: torch.Tensor          # float32 [new]
+    top_ids: torch.Tensor          # int32 [new, n]
+    top_logprobs: torch.Tensor     # float32 [new, n]
+
+
+def logprob_wants(logprobs, B: int) -> List[int]:
+    """The `logprobs` argument of BatchDecoder.start / DecodePool.join -> per sequence -1 (off) or its top-n (0 .. ops.LOGPROB_TOP_MAX).
+    logprobs: None; one int for every sequence; or a list with None or an int per sequence."""
+    per = [logprobs] * B if logprobs is None or isinstance(logprobs, int) else list(logprobs)
+    if len(per) != B:
+        raise ValueError(f"logprobs: {len(per)} entries for {B} sequences")
+    out = []
+    for w in per:
+        if w is None:
+            out.append(-1)
+            continue
+        if isinstance(w, bool) or int(w) != w or not 0 <= int(w) <= ops.LOGPROB_TOP_MAX:
+            raise ValueError(f"logprobs: top-n must be an integer in 0..{ops.LOGPROB_TOP_MAX} or None (got {w!r})")
+        out.append(int(w))
+    return out
+
+
+class LogprobBuffers:
+    """Device side of the log-probability records of a decoder's rows: lp [rows, cap], top_ids / top_lp [rows, cap, LOGPROB_TOP_MAX], the
+    per-row request `want` (-1 = off) and the per-row count of recorded tokens `n_rec` (fo1_decode_logprob_record).  Allocated by the first
+    requesting sequence, as the seen bitmap is by the first penalised one."""
+
+    def __init__(self, rows: int, cap: int, dev):
+        T = ops.LOGPROB_TOP_MAX
+        with torch.inference_mode(False):
+            self.lp = torch.zeros(rows, cap, dtype=torch.float32, device=dev)
+            self.top_ids = torch.zeros(rows, cap, T, dtype=torch.int32, device=dev)
+            self.top_lp = torch.zeros(rows, cap, T, dtype=torch.float32, device=dev)
+            self.want = torch.full((rows,), -1, dtype=torch.int32, device=dev)
+            self.n_rec = torch.zeros(rows, dtype=torch.int32, device=dev)
+
+    def written(self):
+        """What a step writes: part of a capture's rollback tuple."""
+        return self.lp, self.top_ids, self.top_lp, self.n_rec
+
+    def set_rows(self, rows: Sequence[int], wants: Sequence[int], first, src: Sequence[int]) -> list:
+        """Rows `rows` get the requests `wants`; a requesting row's column 0 is the first token's record — row src[k] of first = (lp [B],
+        top_ids [B, n], top_lp [B, n]), the rows form's output on the prefill's logits — and its n_rec = 1.  -> the uploads' host tensors."""
+        dev = self.lp.device
+        r = torch.tensor(list(rows), dtype=torch.int64)
+        w = torch.tensor(list(wants), dtype=torch.int32)
+        rd = r.to(dev, non_blocking=True)
+        self.want[rd] = w.to(dev, non_blocking=True)
+        keep = [r, w]
+        req = [k for k, x in enumerate(wants) if x >= 0]
+        if req:
+            lp0, tid0, tlp0 = first
+            n = tid0.shape[1]
+            if n < max(wants):
+                raise ValueError(f"logprobs: the first tokens were scored with top-{n}, a sequence asks for top-{max(wants)}")
+            rr = torch.tensor([rows[k] for k in req], dtype=torch.int64)
+            sr = torch.tensor([src[k] for k in req], dtype=torch.int64)
+            keep += [rr, sr]
+            rr, sr = rr.to(dev, non_blocking=True), sr.to(dev, non_blocking=True)
+            self.lp[rr, 0] = lp0[sr]
+            self.top_ids[rr, 0] = torch.nn.functional.pad(tid0[sr], (0, ops.LOGPROB_TOP_MAX - n), value=-1)
+            self.top_lp[rr, 0] = torch.nn.functional.pad(tlp0[sr], (0, ops.LOGPROB_TOP_MAX - n), value=float("-inf"))
+            self.n_rec[rr] = 1
+        return keep
+
+    @staticmethod
+    def record(lp, top_ids, top_lp, row: int, n: int, want: int) -> LogprobRecord:
+        """Row `row` of host copies of the three tables -> the record of its first n tokens."""
+        return LogprobRecord(lp[row, :n].clone(), top_ids[row, :n, :want].clone(), top_lp[row, :n, :want].clone())
+
+
 class BatchDecoder:
     """Greedy decode of up to 32 sequences at once: the weights are streamed ONCE per step for all sequences
     (fo1_gemv_batch_bf16), 5 launches per layer, and the whole step — embedding gather, 36 layers, lm_head, argmax, stop check,
@@ -746,6 +821,8 @@ class BatchDecoder:
         self.sampled = False       # the step ends in a head that reads self.sparams (the sampled or the general one)
         self.general = False       # ... in the general head: some row has the greedy flag or a repetition penalty
         self.seen = None           # seen bitmap [MAX_BATCH, ld_words], allocated by the first start() with a penalty
+        self.lpb = None            # log-probability records (LogprobBuffers), allocated by the first start() that asks for them
+        self.lp_want: List[int] = []       # per sequence of the current start(): -1 = no record, else its top-n
         self.n_stop = 0
         self.dk = self.dvt = None
         self.rows = 0
@@ -772,16 +849,22 @@ class BatchDecoder:
             self._graphs = {}
 
     def start(self, seqs, deltas, first_tokens: torch.Tensor, max_new_tokens: int, stop_ids: Sequence[int] = (), sampling=None,
-              prompt_ids: Optional[Sequence[Sequence[int]]] = None):
+              prompt_ids: Optional[Sequence[Sequence[int]]] = None, logprobs=None, first_logprobs=None):
         """seqs: [(cache row offset, L, ...)] of the packed prefill that just ran on llm.kcache / llm.vtcache; first_tokens: device
         int32 [B] (the prefill's picks: greedy, or drawn with counter 0).  Moves every sequence to its own slot and accepts the first tokens
         on the device.  sampling: None = greedy steps; dict(temperature, top_p, top_k, seed[, streams]) = every step ends in the device
         sampler (fo1_decode_sample_accept), sequence b drawing Philox(tokens generated so far, streams[b]; seed) — streams defaults to
         0 .. B - 1, the sequence's index in its request list.  A dict with greedy=True or a repetition_penalty, or a list with one dict or
         None per sequence (sampling_table), ends every step in the general head (fo1_decode_head_accept); a penalty needs prompt_ids, the
-        ids each request passed: they and the first tokens seed the sequence's seen set (the caller picked the first tokens with it)."""
+        ids each request passed: they and the first tokens seed the sequence's seen set (the caller picked the first tokens with it).
+        logprobs (logprob_wants): None, one int or a list with None / int per sequence = the top-n of the log-probability record kept for that
+        sequence (logprobs()); orthogonal to `sampling`: the record launch follows whichever head the step ends in.  first_logprobs: the first
+        tokens' records, ops.logprob_rows on the prefill's logits with the largest requested n (FO1Engine._first_logprobs)."""
         llm = self.llm
         B = len(seqs)
+        wants = logprob_wants(logprobs, B)
+        if any(w >= 0 for w in wants) and first_logprobs is None:
+            raise ValueError("BatchDecoder: logprobs needs first_logprobs, the first tokens' records")
         if B > self.MAX_BATCH:
             raise ValueError(f"BatchDecoder handles at most {self.MAX_BATCH} sequences")
         stop_ids = stop_id_list(stop_ids, self.MAX_STOP, "BatchDecoder", "; use the host loop")
@@ -818,6 +901,11 @@ class BatchDecoder:
             self._keep.append(sp)
         if penalised and self.seen is None:
             self.seen = new_seen(self.MAX_BATCH, llm.cfg.vocab_size, llm.dev)
+        self.lp_want = wants
+        if any(w >= 0 for w in wants):
+            if self.lpb is None:
+                self.lpb = LogprobBuffers(self.MAX_BATCH, self.IDS_CAP, llm.dev)
+            self._keep += self.lpb.set_rows(list(range(B)), wants, first_logprobs, list(range(B)))
         self.done.zero_()
         first = first_tokens.to(torch.int32).contiguous()
         with ops.workspace_scope(self._ws_owner):
@@ -845,7 +933,7 @@ class BatchDecoder:
         scale = 1.0 / math.sqrt(HD)
         st = self.state[:B]
         from . import stage_abi
-        if stage_abi.enabled() and not self.sampled:      # the same launches, sequenced by fo1_llm_decode_step (csrc/stages.hip: the greedy head)
+        if stage_abi.enabled() and not self.sampled and not self.recording:      # the same launches, sequenced by fo1_llm_decode_step (csrc/stages.hip: the greedy head, no records)
             with ops.workspace_scope(self._ws_owner):
                 return stage_abi.llm_stage(llm).decode_step(self)
         with ops.workspace_scope(self._ws_owner):
@@ -870,7 +958,15 @@ class BatchDecoder:
                 ops.decode_sample_accept(logits, self.sparams[:B], st, self.plan[:B], self.ids[:B], self.stop[:self.n_stop], self.done)
             else:
                 ops.decode_argmax_accept(logits, None, st, self.plan[:B], self.ids[:B], self.stop[:self.n_stop], self.done)
+            if self.recording:      # after the head, whichever it was: the accepted ids' log-probabilities on this step's raw logits
+                lb = self.lpb
+                ops.decode_logprob_record(logits, lb.want[:B], st, self.ids[:B], lb.n_rec[:B], lb.lp[:B], lb.top_ids[:B], lb.top_lp[:B])
             return logits
+
+    @property
+    def recording(self) -> bool:
+        """Some sequence of the current start() asked for log-probabilities: every step ends in the record launch."""
+        return any(w >= 0 for w in self.lp_want)
 
     def step(self, use_graph: bool = True):
         """One token for every live sequence."""
@@ -885,6 +981,9 @@ class BatchDecoder:
         if self.general:     # (one more form; the bitmap's identity is baked into its graph, and the warm-up step sets bits in it)
             seen = () if self.seen is None else (self.seen,)
             key += ("general", self.seen.data_ptr() if seen else 0)
+        if self.recording:   # (and one more: the record launch bakes the buffers' identity in, and the warm-up step writes them)
+            key += ("logprobs", self.lpb.lp.data_ptr())
+            seen += self.lpb.written()
         ent = self._graphs.get(key)
         if ent is None:      # (ops.capture_graph: the warm-up step is rolled back)
             ent = self._graphs[key] = ops.capture_graph(self._step_device, rollback=(self.state, self.plan, self.ids, self.done, *seen))
@@ -898,6 +997,16 @@ class BatchDecoder:
         n = self.state[:B, 4].cpu().tolist()
         ids = self.ids[:B, :max(n)].cpu().tolist()
         return [row[:k] for row, k in zip(ids, n)]
+
+    def logprobs(self) -> List[Optional[LogprobRecord]]:
+        """The log-probability record of every sequence so far (first token included); None for a sequence that did not ask."""
+        B = self.B
+        if not self.recording:
+            return [None] * B
+        n = self.state[:B, 4].cpu().tolist()
+        lb = self.lpb
+        lp, ti, tl = (t[:B, :max(n)].cpu() for t in (lb.lp, lb.top_ids, lb.top_lp))
+        return [None if w < 0 else LogprobBuffers.record(lp, ti, tl, b, n[b], w) for b, w in enumerate(self.lp_want)]
 
     def run(self, max_new_tokens: int, use_graph: bool = True, poll: int = 8) -> List[List[int]]:
         """Decode until every sequence has stopped (or max_new_tokens).  Returns the generated ids per sequence, the first
@@ -983,6 +1092,10 @@ class DecodePool:
         self.seen = None                               # seen bitmap [P, ld_words], allocated when the first penalised sequence joins
         self.kind = ["plain"] * P                      # what each slot's sparams row holds: "plain", "sampled" or "general"
         self.n_general = 0                             # live slots that are not plain: > 0 ends the step in the general head
+        self.lpb = None                                # log-probability records (LogprobBuffers), allocated when the first requesting sequence joins
+        self.lp_want = [-1] * P                        # a live slot's request: -1 = no record, else its top-n
+        self.lp_dev = [-1] * P                         # what each slot's `want` word on the device holds (tracked as `kind` is)
+        self.n_logprob = 0                             # live requesting slots: > 0 adds the record launch to the step
         self._sets: Dict[tuple, int] = {}              # stop-id tuple -> row of self.stop
         self._set_users = [0] * self.MAX_SETS          # live slots per row (a row with users is never rewritten)
         self.slot_set = [0] * P
@@ -1030,7 +1143,7 @@ class DecodePool:
     # ---- join ------------------------------------------------------------------------------------------------------------------
     def join(self, kcache: torch.Tensor, vtcache: torch.Tensor, seqs, deltas, first_tokens: torch.Tensor, max_new_tokens: int,
              stop_ids: Sequence[int] = (), tags: Optional[Sequence] = None, sampling=None,
-             prompt_ids: Optional[Sequence[Sequence[int]]] = None) -> List[int]:
+             prompt_ids: Optional[Sequence[Sequence[int]]] = None, logprobs=None, first_logprobs=None) -> List[int]:
         """seqs [(cache row offset, L, ...)] of a packed prefill that ran on (kcache, vtcache); first_tokens device int32 [B].  Enqueues,
         on the CURRENT stream (the pool's), the relocation of every sequence into a free slot and the on-device accept of its first
         token.  Returns the slots.  Raises if there is no room (callers check `len(pool.free)` / `fits()` first).
@@ -1038,8 +1151,14 @@ class DecodePool:
         list with one dict or None per sequence = that sequence's row of the per-slot parameter table — temperature / top-k / top-p draws
         on Philox(tokens generated so far, stream; seed), greedy=True, repetition_penalty.  A penalty needs prompt_ids (the ids each request
         passed): the slot's seen-bitmap row is cleared and marked with them and with the first token, which the caller picked with the
-        prompt's set.  While any live slot is not plain the step ends in the general head (step())."""
+        prompt's set.  While any live slot is not plain the step ends in the general head (step()).
+        logprobs / first_logprobs: as BatchDecoder.start takes them; while any live slot asks for a record the record launch follows the head
+        (step()), and harvest(records=True) hands the finished slots' records out.  A pool no requesting sequence ever joined holds no
+        record buffer and issues exactly the launches and copies it always has."""
         B = len(seqs)
+        wants = logprob_wants(logprobs, B)
+        if any(w >= 0 for w in wants) and first_logprobs is None:
+            raise ValueError("DecodePool: logprobs needs first_logprobs, the first tokens' records")
         srows, kinds = sampling_table(sampling, B)
         penalised = [ops.penalty_on(r[6]) for r in srows]
         if any(penalised) and (prompt_ids is None or len(prompt_ids) != B):
@@ -1055,6 +1174,7 @@ class DecodePool:
         try:
             self._join_slots(slots, kcache, vtcache, seqs, deltas, first_tokens, max_new, set_row)
             self._join_sampling(slots, srows, kinds, penalised, first_tokens, prompt_ids)
+            self._join_logprobs(slots, wants, first_logprobs)
         except BaseException:
             # nothing of this submission is live: its slots go back (their device state may be half written — the next occupant's
             # join rewrites state, plan and K / V^T rows; until then the slot is marked finished so that no step reads it)
@@ -1076,7 +1196,21 @@ class DecodePool:
             self.slot_set[s] = set_row
             self._set_users[set_row] += 1
             self.n_general += kinds[k] != "plain"
+            self.lp_want[s] = wants[k]
+            self.n_logprob += wants[k] >= 0
         return slots
+
+    def _join_logprobs(self, slots, wants, first_logprobs):
+        """The record requests of a submission's slots.  Nothing is enqueued for a non-requesting sequence whose slot's `want` word is off
+        already: a slot a requesting sequence has left gets -1 back when a non-requesting one reuses it."""
+        write = [k for k, s in enumerate(slots) if wants[k] >= 0 or self.lp_dev[s] >= 0]
+        if not write:
+            return
+        if self.lpb is None:      # (graphs captured before are unreachable for a recording step: its key holds the buffers' identity)
+            self.lpb = LogprobBuffers(self.P, self.IDS_CAP, self.llm.dev)
+        self._keep += self.lpb.set_rows([slots[k] for k in write], [wants[k] for k in write], first_logprobs, write)
+        for k in write:
+            self.lp_dev[slots[k]] = wants[k]
 
     def _join_sampling(self, slots, srows, kinds, penalised, first_tokens, prompt_ids):
         """The parameter rows and seen sets of a submission's slots.  Nothing is enqueued for a plain sequence whose slot still holds the
@@ -1182,7 +1316,16 @@ class DecodePool:
         # (the step's form is part of the key: FUSED_SPLITK / SPLITS may be set per pool, scripts/pool_bench.py and the A/B test do)
         return (self.slot_rows, bucket, self.llm.rope_epoch, self.llm.rope_cos.data_ptr(), bool(self.FUSED_SPLITK), tuple(sorted(self.SPLITS.items())), bool(self.TILED_WEIGHTS))
 
-    def _step_device(self, bucket: int, general: bool = False):
+    def step_key(self, bucket: int) -> tuple:
+        """Key of the graph the coming step replays: graph_key(bucket), plus a flag and the buffers' identity per extra launch form."""
+        key = self.graph_key(bucket)
+        if self.n_general > 0:
+            key += ("general", self.seen.data_ptr() if self.seen is not None else 0)
+        if self.n_logprob > 0:
+            key += ("logprobs", self.lpb.lp.data_ptr())
+        return key
+
+    def _step_device(self, bucket: int, general: bool = False, record: bool = False):
         llm, P = self.llm, self.P
         c = llm.cfg
         H, KV, HD = c.num_heads, c.num_kv_heads, c.head_dim
@@ -1226,32 +1369,34 @@ class DecodePool:
                 ops.decode_head_accept(logits, self.sparams, st, self.plan, self.ids, self.stop, self.done, seen=self.seen, per_sequence_sets=True)
             else:
                 ops.decode_argmax_accept(logits, None, st, self.plan, self.ids, self.stop, self.done, per_sequence_sets=True)
+            if record:       # after the head, whichever it was; rows whose `want` is off, finished and empty slots return at once
+                lb = self.lpb
+                ops.decode_logprob_record(logits, lb.want, st, self.ids, lb.n_rec, lb.lp, lb.top_ids, lb.top_lp)
             return logits
 
     def step(self, use_graph: bool = True):
         """One token for every live sequence (all P rows are computed).  The head: fo1_decode_argmax_accept while every live slot is plain
-        greedy, else the general head over all P rows (fo1_decode_head_accept) — the count changes in join() and harvest() only, so a
-        (bucket, step form) has at most one graph more."""
+        greedy, else the general head over all P rows (fo1_decode_head_accept); while a live slot asks for log-probabilities the record
+        launch follows it (fo1_decode_logprob_record) — both counts change in join() and harvest() only, so a bucket has at most four
+        graphs, and with both at zero the step is the all-greedy one under graph_key(bucket)."""
         bucket = self.kv_bucket()
         general = self.n_general > 0
+        record = self.n_logprob > 0
         if not use_graph:
-            out = self._step_device(bucket, general)
-        elif general:
-            seen = () if self.seen is None else (self.seen,)
-            key = self.graph_key(bucket) + ("general", self.seen.data_ptr() if seen else 0)
-            ent = self._graphs.get(key)
-            if ent is None:      # (the warm-up step also sets bits of the bitmap: rolled back with the rest)
-                ent = self._graphs[key] = ops.capture_graph(lambda: self._step_device(bucket, True),
-                                                            rollback=(self.state, self.plan, self.ids, self.done, *seen))
-            ops.replay_graph(ent[0])
-            out = ent[1]
+            out = self._step_device(bucket, general, record)
         else:
-            key = self.graph_key(bucket)
+            # (ops.capture_graph: the warm-up step is rolled back; the K / V^T rows it appended are the ones the first replay rewrites
+            # with the same values.  The warm-up of a general step also sets bits of the bitmap, that of a recording step writes the
+            # record buffers: rolled back with the rest)
+            key = self.step_key(bucket)
+            roll = (self.state, self.plan, self.ids, self.done)
+            if general and self.seen is not None:
+                roll += (self.seen,)
+            if record:
+                roll += self.lpb.written()
             ent = self._graphs.get(key)
             if ent is None:
-                # (ops.capture_graph: the warm-up step is rolled back; the K / V^T rows it appended are the ones the first replay
-                # rewrites with the same values)
-                ent = self._graphs[key] = ops.capture_graph(lambda: self._step_device(bucket), rollback=(self.state, self.plan, self.ids, self.done))
+                ent = self._graphs[key] = ops.capture_graph(lambda: self._step_device(bucket, general, record), rollback=roll)
             ops.replay_graph(ent[0])
             out = ent[1]
         self.steps_run += 1
@@ -1268,30 +1413,49 @@ class DecodePool:
         pinned[0].copy_(self.state, non_blocking=True)
         host_ids = pinned[1][:self.P * cols].view(self.P, cols)            # contiguous on both sides: a plain asynchronous memcpy
         host_ids.copy_(self.ids[:, :cols].contiguous(), non_blocking=True)
+        recs = None
+        if self.n_logprob > 0:      # the record tables ride along while a requesting slot is live (pinned beside the ids, same columns)
+            T = ops.LOGPROB_TOP_MAX
+            if len(pinned) < 5 or pinned[2].numel() < self.P * cols:
+                n = self.P * max(cols, 64)
+                pinned = (pinned[0], pinned[1], torch.empty(n, dtype=torch.float32).pin_memory(), torch.empty(n * T, dtype=torch.int32).pin_memory(),
+                          torch.empty(n * T, dtype=torch.float32).pin_memory())
+            lb = self.lpb
+            recs = (pinned[2][:self.P * cols].view(self.P, cols), pinned[3][:self.P * cols * T].view(self.P, cols, T),
+                    pinned[4][:self.P * cols * T].view(self.P, cols, T))
+            for host, devt in zip(recs, (lb.lp, lb.top_ids, lb.top_lp)):
+                host.copy_(devt[:, :cols].contiguous(), non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
-        return pinned[0], host_ids, ev, dict(self.live), pinned
+        return pinned[0], host_ids, ev, dict(self.live), pinned, recs
 
-    def harvest(self, snap) -> List[Tuple[int, object, List[int]]]:
-        """Sequences that had finished when `snap` was taken (and have not been collected yet): [(slot, tag, ids)]; their slots are free again."""
+    def harvest(self, snap, records: bool = False) -> List[tuple]:
+        """Sequences that had finished when `snap` was taken (and have not been collected yet): [(slot, tag, ids)]; their slots are free again.
+        records=True: [(slot, tag, ids, LogprobRecord or None)] — a requesting sequence's record, None for the others."""
         st, ids, ev, live_then = snap[:4]
+        recs = snap[5] if len(snap) > 5 else None
         ev.synchronize()
         fin, ngen = st[:, 3].tolist(), st[:, 4].tolist()          # one host read of the pinned snapshot, not two per live slot
         out = []
         for s, tag in live_then.items():
             if s in self.live and self.live[s] is tag and fin[s] == 1:
-                out.append((s, tag, ids[s, :ngen[s]].tolist()))
+                item = (s, tag, ids[s, :ngen[s]].tolist())
+                if records:
+                    item += (LogprobBuffers.record(*recs, s, ngen[s], self.lp_want[s]) if self.lp_want[s] >= 0 else None,)
+                out.append(item)
+                self.n_logprob -= self.lp_want[s] >= 0
+                self.lp_want[s] = -1
                 del self.live[s]
                 self.free.append(s)
                 self._set_users[self.slot_set[s]] -= 1
                 self.n_general -= self.kind[s] != "plain"
         return out
 
-    def drain(self, use_graph: bool = True, poll: int = 8) -> List[Tuple[int, object, List[int]]]:
-        """Step until every live sequence has stopped (synchronous convenience for tests / one-shot callers)."""
+    def drain(self, use_graph: bool = True, poll: int = 8, records: bool = False) -> List[tuple]:
+        """Step until every live sequence has stopped (synchronous convenience for tests / one-shot callers); records: as harvest."""
         out = []
         while self.live:
             for _ in range(poll):
                 self.step(use_graph)
-            out += self.harvest(self.snapshot())
+            out += self.harvest(self.snapshot(), records=records)
         return out

@@ -548,36 +548,63 @@ class FO1Engine:
                 self._seen_keep = ops.mark_prompts(seen, self.cfg.llm.vocab_size, list(range(n)), [r["ids"] for r in requests])
             return ops.sample_rows(self._last_logits[:n], table, seen=seen, general=True)
 
+    @staticmethod
+    def _logprob_part(logprobs, a: int, b: int):
+        """`logprobs` (None, one int, or a list per request) for requests a .. b of the list."""
+        return logprobs if logprobs is None or isinstance(logprobs, int) else list(logprobs)[a:b]
+
+    def _first_logprobs(self, logprobs, first: torch.Tensor, n: int):
+        """The first tokens' log-probability records, from the prefill's logits (the sibling of _first_tokens): None when no request of the
+        pass asks; else ops.logprob_rows over the pass's n rows with the largest top-n asked for (a smaller n is a prefix of it)."""
+        from .llm import logprob_wants
+        wants = logprob_wants(logprobs, n)
+        if all(w < 0 for w in wants):
+            return None
+        with ops.workspace_scope(self._ws_owner):
+            return ops.logprob_rows(self._last_logits[:n], first[:n].to(torch.int32).contiguous(), max(wants))
+
     def generate_batch(self, requests: Sequence[dict], max_new_tokens: int = 512, stop_ids: Sequence[int] = (), use_graph: bool = True,
-                       sampling=None) -> List[List[int]]:
+                       sampling=None, logprobs=None):
         """Generation for a batch of requests: one packed prefill, then the batched decode loop (vlm_fo1_amd.llm.BatchDecoder):
         weights streamed once per step for all sequences, stop rule and bookkeeping on the device.  Returns the new ids per request
         (stop token included, like HF generate).  sampling: None = greedy; dict(temperature, top_p, top_k, seed) = temperature / top-k / top-p
         sampling on the device (csrc/sample.hip): request i draws Philox(tokens generated so far, i; seed) — the first token from the prefill's
         logits with counter 0.  A dict may also hold greedy=True and repetition_penalty, and a list gives every request
         its own dict or None.  With the decode pool enabled every kind of request joins the pool; without it the BatchDecoder groups take
-        the same dicts."""
+        the same dicts.  logprobs: None, one int for all, or a list with None / int per request = the top-n (0 .. 8) of the log-probability
+        record kept for that request (llm.LogprobRecord: the log-softmax of the raw logits); the call then returns
+        (ids, records) with None for a request that did not ask.  Without the argument the return value is the list of ids, as ever."""
         from .llm import BatchDecoder, run_decoders
         out: List[List[int]] = []
+        recs: list = []
         base = 0      # index of the pass's first request in the request list (the sampler's stream ids)
         if getattr(self, "_pool_svc", None) is not None:
             # decode pool: every pass's sequences join the shared pool; this call's later passes prefill while its earlier ones decode
             handles = []
             for grp in self.split_passes(requests):
                 part = sampling if sampling is None or isinstance(sampling, dict) else list(sampling)[base:base + len(grp)]
-                handles.append(self.submit_batch(grp, max_new_tokens, stop_ids, use_graph, sampling=part, stream_base=base))
+                handles.append(self.submit_batch(grp, max_new_tokens, stop_ids, use_graph, sampling=part, stream_base=base,
+                                                 logprobs=self._logprob_part(logprobs, base, base + len(grp))))
                 base += len(grp)
             for h in handles:
                 out += h.result()
-            return out
+                recs += h.logprobs()
+            return out if logprobs is None else (out, recs)
         for grp in self.split_passes(requests):
             self.prefill_batch(grp, use_graph=use_graph)          # ONE packed pass for the whole group (its GEMMs see every image's rows)
             hp = self._last_batch
             n = len(grp)
             per = self._per_request(sampling if sampling is None or isinstance(sampling, dict) else list(sampling)[base:base + n], n, base)
             first = self._first_tokens(per, grp)
+            lpp = self._logprob_part(logprobs, base, base + n)
+            first_lp = self._first_logprobs(lpp, first, n)
             plain = all(sp is None for sp in per)
             prompts = [r["ids"] for r in grp]
+
+            def lpa(a, b):       # the record requests of sequences a .. b of this pass (+ their first tokens' records)
+                if first_lp is None:
+                    return {}
+                return dict(logprobs=self._logprob_part(lpp, a, b), first_logprobs=tuple(t[a:b] for t in first_lp))
 
             def samp(a, b):      # the sampling of sequences a .. b of this pass
                 return None if plain else per[a:b]
@@ -585,8 +612,9 @@ class FO1Engine:
             gmax = min(BatchDecoder.MAX_BATCH, self.DECODE_MAX_GROUP)
             if n <= gmax:
                 dec = self._decoder()
-                dec.start(hp["seqs"], hp["delta"], first[:n], max_new_tokens, stop_ids, sampling=samp(0, n), prompt_ids=prompts)
+                dec.start(hp["seqs"], hp["delta"], first[:n], max_new_tokens, stop_ids, sampling=samp(0, n), prompt_ids=prompts, **lpa(0, n))
                 out += dec.run(max_new_tokens, use_graph=use_graph)
+                recs += dec.logprobs()
                 continue
             # more sequences than one decode group carries (32 = two 16-column MFMA groups per weight fragment; DECODE_MAX_GROUP = 16
             # restores round 2's groups for A/B): balanced groups (25 -> 13 + 12), each relocated out of the
@@ -597,8 +625,10 @@ class FO1Engine:
                 dec = self._decoder()
                 for j in range(k):
                     a, b = cuts[j], cuts[j + 1]
-                    dec.start(hp["seqs"][a:b], hp["delta"][a:b], first[a:b], max_new_tokens, stop_ids, sampling=samp(a, b), prompt_ids=prompts[a:b])
+                    dec.start(hp["seqs"][a:b], hp["delta"][a:b], first[a:b], max_new_tokens, stop_ids, sampling=samp(a, b), prompt_ids=prompts[a:b],
+                              **lpa(a, b))
                     out += dec.run(max_new_tokens, use_graph=use_graph)
+                    recs += dec.logprobs()
                 continue
             decs, streams = self._decoders(k)
             cur = torch.cuda.current_stream()
@@ -606,12 +636,15 @@ class FO1Engine:
                 a, b = cuts[j], cuts[j + 1]
                 streams[j].wait_stream(cur)                       # the prefill (and its first tokens) are on the caller's stream
                 with torch.cuda.stream(streams[j]):
-                    decs[j].start(hp["seqs"][a:b], hp["delta"][a:b], first[a:b], max_new_tokens, stop_ids, sampling=samp(a, b), prompt_ids=prompts[a:b])
+                    decs[j].start(hp["seqs"][a:b], hp["delta"][a:b], first[a:b], max_new_tokens, stop_ids, sampling=samp(a, b), prompt_ids=prompts[a:b],
+                                  **lpa(a, b))
             for ids in run_decoders(decs[:k], streams[:k], max_new_tokens, use_graph=use_graph):
                 out += ids
             for j in range(k):
+                with torch.cuda.stream(streams[j]):
+                    recs += decs[j].logprobs()
                 cur.wait_stream(streams[j])                       # the next pass must not overwrite the prefill cache under a relocate
-        return out
+        return out if logprobs is None else (out, recs)
 
     # ---- continuous batching: one decode pool per GPU, shared by every replica (vlm_fo1_amd/serving.py) -------------------------------
     DECODE_POOLS = 1       # decode pools per GPU stepping concurrently on their own streams (serving.PoolGroup); FO1_DECODE_POOLS overrides
@@ -637,25 +670,31 @@ class FO1Engine:
         self._pool_svc = None
 
     def submit_batch(self, requests: Sequence[dict], max_new_tokens: int = 512, stop_ids: Sequence[int] = (), use_graph: bool = True,
-                     sampling=None, stream_base: int = 0):
+                     sampling=None, stream_base: int = 0, logprobs=None):
         """One packed prefill pass (<= PREFILL_MAX requests), then its sequences join the decode pool.  Returns a serving.PoolHandle as
         soon as the pool has taken the K / V^T rows over: the caller may start its next pass while these sequences decode;
         handle.result() -> the new ids per request (stop token included, like HF generate).  sampling: as generate_batch, for this pass's
         requests; request i draws on stream stream_base + i unless its dict names one.  The first tokens are drawn here from the prefill's
-        logits (counter 0, the prompt's seen set when a penalty is on), the pool draws the rest."""
+        logits (counter 0, the prompt's seen set when a penalty is on), the pool draws the rest.  logprobs: as generate_batch, for this pass's
+        requests; the first tokens are scored here, handle.logprobs() returns the records."""
         svc = getattr(self, "_pool_svc", None)
         if svc is None:
             raise RuntimeError("submit_batch needs enable_decode_pool()")
         if len(requests) > self.PREFILL_MAX:
             raise ValueError(f"submit_batch takes one prefill pass (<= {self.PREFILL_MAX} requests)")
+        from .llm import logprob_wants
         per = self._per_request(sampling, len(requests), int(stream_base))
+        logprob_wants(logprobs, len(requests))      # (a bad request fails before the prefill)
         self.prefill_batch(requests, use_graph=use_graph)
         hp = self._last_batch
+        first = self._first_tokens(per, requests)
+        first_lp = self._first_logprobs(logprobs, first, len(requests))
+        lpa = {} if first_lp is None else dict(logprobs=logprobs, first_logprobs=first_lp)
         if all(sp is None for sp in per):
-            h = svc.submit(self.llm, hp["seqs"], hp["delta"], self._last_next_tokens[:len(requests)], max_new_tokens, stop_ids)
+            h = svc.submit(self.llm, hp["seqs"], hp["delta"], first, max_new_tokens, stop_ids, **lpa)
         else:
-            h = svc.submit(self.llm, hp["seqs"], hp["delta"], self._first_tokens(per, requests), max_new_tokens, stop_ids, sampling=per,
-                           prompt_ids=[list(r["ids"]) for r in requests])
+            h = svc.submit(self.llm, hp["seqs"], hp["delta"], first, max_new_tokens, stop_ids, sampling=per,
+                           prompt_ids=[list(r["ids"]) for r in requests], **lpa)
         h.wait_relocated()
         return h
 

@@ -1101,6 +1101,44 @@ def decode_head_accept(logits: torch.Tensor, params: torch.Tensor, state: torch.
     _L.check(rc, "fo1_decode_head_accept")
 
 
+LOGPROB_TOP_MAX = 8      # FO1_LOGPROB_TOP_MAX: top-n alternatives a log-probability record keeps per token
+
+
+def logprob_rows(logits: torch.Tensor, ids: torch.Tensor, top_n: int = 0):
+    """Log-probabilities of the chosen ids (int32 [B], device) on the rows of logits [B, V] bf16, and the top_n alternatives per row
+    (fo1_logprob_rows_bf16: the log-softmax of the raw logits over their finite entries, include/fo1.h) ->
+    (lp float32 [B], top_ids int32 [B, top_n], top_lp float32 [B, top_n])."""
+    _chk(logits, "logits")
+    pl, ld, B, V = _rows(logits, "logits")
+    _chk(ids, "ids", torch.int32)
+    assert ids.is_contiguous() and ids.numel() == B
+    top_n = int(top_n)
+    lp = torch.empty(B, dtype=torch.float32, device=logits.device)
+    tid = torch.empty(B, max(top_n, 0), dtype=torch.int32, device=logits.device)
+    tlp = torch.empty(B, max(top_n, 0), dtype=torch.float32, device=logits.device)
+    rc = _L.load().fo1_logprob_rows_bf16(pl, ld, V, B, ids.data_ptr(), top_n, lp.data_ptr(), tid.data_ptr() if top_n > 0 else None,
+                                         tlp.data_ptr() if top_n > 0 else None, max(top_n, 0), _stream())
+    _L.check(rc, "fo1_logprob_rows_bf16")
+    return lp, tid, tlp
+
+
+def decode_logprob_record(logits: torch.Tensor, want: torch.Tensor, state: torch.Tensor, ids: torch.Tensor, n_rec: torch.Tensor,
+                          lp: torch.Tensor, top_ids: torch.Tensor, top_lp: torch.Tensor) -> None:
+    """The log-probability record of a decode step, launched after its head (fo1_decode_logprob_record): row b with want[b] >= 0 whose
+    state[b, 4] = n has advanced past n_rec[b] scores ids[b, n - 1] on `logits` into column n - 1 of lp [B, ids_ld] and of top_ids / top_lp
+    [B, ids_ld, LOGPROB_TOP_MAX], and sets n_rec[b] = n."""
+    _chk(logits, "logits")
+    pl, ld, B, V = _rows(logits, "logits")
+    cap = ids.shape[1]
+    assert want.dtype == state.dtype == ids.dtype == n_rec.dtype == top_ids.dtype == torch.int32 and lp.dtype == top_lp.dtype == torch.float32
+    assert all(t.is_cuda and t.is_contiguous() for t in (want, state, ids, n_rec, lp, top_ids, top_lp))
+    assert state.shape[0] == B and ids.shape[0] == B and want.numel() == B and n_rec.numel() == B
+    assert tuple(lp.shape) == (B, cap) and tuple(top_ids.shape) == tuple(top_lp.shape) == (B, cap, LOGPROB_TOP_MAX)
+    rc = _L.load().fo1_decode_logprob_record(pl, ld, V, B, want.data_ptr(), state.data_ptr(), ids.data_ptr(), cap, n_rec.data_ptr(),
+                                             lp.data_ptr(), top_ids.data_ptr(), top_lp.data_ptr(), _stream())
+    _L.check(rc, "fo1_decode_logprob_record")
+
+
 def kv_relocate(ksrc: torch.Tensor, kdst: torch.Tensor, vsrc: torch.Tensor, vdst: torch.Tensor, seqs: torch.Tensor, max_len: int) -> None:
     """k*: [layers, n_kv, rows, 128]; v*: [layers, n_kv*128, rows]; seqs int32 [B, 4] = (src0, dst0, len, 0) on the device."""
     for t in (ksrc, kdst, vsrc, vdst):

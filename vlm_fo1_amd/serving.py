@@ -23,19 +23,22 @@ from .llm import DecodePool, QwenLLM
 
 class PoolHandle:
     """The sequences of one submit(): `wait_relocated()` orders the caller's stream after the copy of their K / V^T rows out of the
-    prefill cache; `result()` -> the generated ids per sequence."""
+    prefill cache; `result()` -> the generated ids per sequence; `logprobs()` -> their log-probability records (llm.LogprobRecord, None for a sequence
+    submitted without `logprobs`)."""
 
     def __init__(self, n: int):
         self.n = n
         self._ids: List[Optional[List[int]]] = [None] * n
+        self._lps: list = [None] * n
         self._left = n
         self._done = threading.Event()
         self._joined = threading.Event()
         self._reloc_event: Optional[torch.cuda.Event] = None
         self._error: Optional[BaseException] = None
 
-    def _set(self, k: int, ids: List[int]):
+    def _set(self, k: int, ids: List[int], rec=None):
         self._ids[k] = ids
+        self._lps[k] = rec
         self._left -= 1
         if self._left == 0:
             self._done.set()
@@ -61,6 +64,10 @@ class PoolHandle:
         if self._error is not None:
             raise self._error
         return self._ids
+
+    def logprobs(self, timeout: Optional[float] = None) -> list:
+        self.result(timeout)
+        return self._lps
 
 
 class PoolService:
@@ -90,10 +97,11 @@ class PoolService:
 
     # ---- caller side ----------------------------------------------------------------------------------------------------------
     def submit(self, src_llm: QwenLLM, seqs, deltas, first_tokens: torch.Tensor, max_new_tokens: int, stop_ids: Sequence[int] = (),
-               sampling=None, prompt_ids=None) -> PoolHandle:
+               sampling=None, prompt_ids=None, logprobs=None, first_logprobs=None) -> PoolHandle:
         """Hand the sequences of a finished packed prefill (K / V^T in src_llm.kcache / vtcache at the packed rows `seqs`) to the pool.
         The prefill must have been enqueued on the CURRENT stream: an event recorded here orders the pool's relocation after it.
-        sampling / prompt_ids: per-sequence sampling and repetition penalty, as DecodePool.join takes them (None = plain greedy)."""
+        sampling / prompt_ids: per-sequence sampling and repetition penalty, as DecodePool.join takes them (None = plain greedy).
+        logprobs / first_logprobs: per-sequence log-probability records, as DecodePool.join takes them; read with handle.logprobs()."""
         if self._fatal is not None:
             raise self._fatal
         if self._closed or self._stop or not self._thread.is_alive():
@@ -104,7 +112,7 @@ class PoolService:
         h = PoolHandle(n)
         ev = torch.cuda.Event()
         ev.record()
-        self._q.put((h, src_llm.kcache, src_llm.vtcache, list(seqs), list(deltas), first_tokens, int(max_new_tokens), tuple(stop_ids), ev, sampling, prompt_ids))
+        self._q.put((h, src_llm.kcache, src_llm.vtcache, list(seqs), list(deltas), first_tokens, int(max_new_tokens), tuple(stop_ids), ev, sampling, prompt_ids, logprobs, first_logprobs))
         if self._closed or not self._thread.is_alive():      # raced close() / the scheduler's fatal path: nobody will ever serve the queue
             self._fail_queued(self._fatal or RuntimeError("decode pool: closed while the submission was being queued"))
         return h
@@ -130,7 +138,7 @@ class PoolService:
     # ---- scheduler thread -----------------------------------------------------------------------------------------------------
     def _admit(self, pool: DecodePool, waiting: list) -> None:
         while waiting:
-            h, kc, vt, seqs, deltas, first, max_new, stop_ids, ev, sampling, prompt_ids = waiting[0]
+            h, kc, vt, seqs, deltas, first, max_new, stop_ids, ev, sampling, prompt_ids, logprobs, first_lp = waiting[0]
             if len(seqs) > len(pool.free):
                 return
             if not pool.can_take(stop_ids):
@@ -140,7 +148,8 @@ class PoolService:
             waiting.pop(0)
             try:
                 torch.cuda.current_stream().wait_event(ev)       # the prefill that produced the rows and the first tokens
-                pool.join(kc, vt, seqs, deltas, first, max_new, stop_ids, tags=[(h, k) for k in range(len(seqs))], sampling=sampling, prompt_ids=prompt_ids)
+                pool.join(kc, vt, seqs, deltas, first, max_new, stop_ids, tags=[(h, k) for k in range(len(seqs))], sampling=sampling, prompt_ids=prompt_ids,
+                          logprobs=logprobs, first_logprobs=first_lp)
                 h._reloc_event = torch.cuda.Event()
                 h._reloc_event.record()
                 h._joined.set()
@@ -193,8 +202,8 @@ class PoolService:
                         pinned[rnd & 1] = snap[4]
                         rnd += 1
                     if prev is not None:
-                        for _, (h, k), ids in pool.harvest(prev):
-                            h._set(k, ids)
+                        for _, (h, k), ids, rec in pool.harvest(prev, records=True):
+                            h._set(k, ids, rec)
                             self.stats["finished"] += 1
                     prev = snap
         except BaseException as e:          # a failing step is fatal for every sequence in flight
@@ -247,11 +256,12 @@ class PoolGroup:
         return out
 
     def submit(self, src_llm: QwenLLM, seqs, deltas, first_tokens: torch.Tensor, max_new_tokens: int, stop_ids: Sequence[int] = (),
-               sampling=None, prompt_ids=None) -> PoolHandle:
+               sampling=None, prompt_ids=None, logprobs=None, first_logprobs=None) -> PoolHandle:
         with self._lock:
             k = min(range(len(self.services)), key=lambda i: (self._submitted[i] - self.services[i].stats["finished"], i))
             self._submitted[k] += len(seqs)
-        return self.services[k].submit(src_llm, seqs, deltas, first_tokens, max_new_tokens, stop_ids, sampling=sampling, prompt_ids=prompt_ids)
+        return self.services[k].submit(src_llm, seqs, deltas, first_tokens, max_new_tokens, stop_ids, sampling=sampling, prompt_ids=prompt_ids,
+                                       logprobs=logprobs, first_logprobs=first_logprobs)
 
     def close(self):
         for s in self.services:
