@@ -117,7 +117,9 @@ def test_rmsnorm_layernorm():
         close_bf16(got, ref, ulps=1.01, what=f"rmsnorm D={D}")
         got = ops.layernorm(x, w, b, 1e-5)
         ref = rb(torch.nn.functional.layer_norm(xf, (D,), w.float().cpu(), b.float().cpu(), 1e-5))
-        close_bf16(got, ref, ulps=1.01, atol=2e-3, what=f"layernorm D={D}")
+        # atol: twice the statistics term of tests/small_op_cases.py's bound at these rows (2 x 2^-18 x (|x| + |mean|) rstd |w| <= 2 x 2^-18 x 5.5 x 1.5),
+        # once for the kernel and once for torch's fp32 reference; the rounding itself is the ulp term
+        close_bf16(got, ref, ulps=1.01, atol=6.5e-5, what=f"layernorm D={D}")
 
 
 def test_swiglu_biasact_argmax():

@@ -60,9 +60,11 @@ __global__ __launch_bounds__(256) void mask_rows_kernel(const uint16_t* __restri
 }
 
 // ---- top-k (descending, ties -> lower index first) by a single-workgroup bitonic sort of 64-bit (key, ~index) words ----------
-// n <= 2^17 tokens; one launch, no host round trip.  key = order-preserving map of the fp32 score (NaN sorts last).
+// n <= 2^17 tokens; one launch, no host round trip.  key = order-preserving map of the fp32 score (NaN sorts last); -0.0 takes the key of
+// +0.0 (they compare equal, so their order is the index half's to decide).
 __device__ __forceinline__ unsigned int f32_order(float f) {
     unsigned int u = __float_as_uint(f);
+    if (u == 0x80000000u) u = 0u;
     if ((u & 0x7fffffffu) > 0x7f800000u) return 0u;             // NaN: smallest
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }

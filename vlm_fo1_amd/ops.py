@@ -1536,14 +1536,18 @@ def attention_strided(q: torch.Tensor, q_row0: int, k: torch.Tensor, vt: torch.T
 
 
 # ---- image preprocessing (device side) -------------------------------------------------------------------------------------
-def patchify_u8(image_hwc: torch.Tensor, lut: torch.Tensor, patch: int = 14, merge: int = 2) -> torch.Tensor:
-    """uint8 [H, W, 3] (device) -> bf16 [S, 6*patch^2] normalised patches in merge-block order (fo1_patchify_u8_bf16)."""
+def patchify_u8(image_hwc: torch.Tensor, lut: torch.Tensor, patch: int = 14, merge: int = 2, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [H, W, 3] (device) -> bf16 [S, 6*patch^2] normalised patches in merge-block order (fo1_patchify_u8_bf16); `out` may be a
+    column view of a wider buffer (row stride >= 6*patch^2)."""
     if image_hwc.dtype != torch.uint8 or not image_hwc.is_cuda or image_hwc.dim() != 3 or image_hwc.shape[2] != 3 or not image_hwc.is_contiguous():
         raise ValueError("patchify_u8: need a contiguous device uint8 [H, W, 3] tensor")
     _chk(lut, "lut")
     assert lut.shape == (3, 256) and lut.is_contiguous()
     H, W, _ = image_hwc.shape
-    out = torch.empty((H // patch) * (W // patch), 6 * patch * patch, dtype=torch.bfloat16, device=image_hwc.device)
+    if out is None:
+        out = torch.empty((H // patch) * (W // patch), 6 * patch * patch, dtype=torch.bfloat16, device=image_hwc.device)
+    _chk(out, "out")
+    assert tuple(out.shape) == ((H // patch) * (W // patch), 6 * patch * patch) and out.stride(1) == 1
     _L.check(_L.load().fo1_patchify_u8_bf16(image_hwc.data_ptr(), H, W, lut.data_ptr(), out.data_ptr(), out.stride(0), patch, merge,
                                             _stream()), "fo1_patchify_u8_bf16")
     return out
