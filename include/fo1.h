@@ -531,6 +531,37 @@ int fo1_sample_rows_seen_bf16(const void* logits, long long ld_logits, int n_voc
 int fo1_decode_head_accept(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params,
                            int32_t* state, int32_t* plan, int32_t* ids_out, int ids_ld, const int32_t* stop_ids, int n_stop,
                            int32_t* done, void* workspace, size_t workspace_bytes, uint32_t* seen, long long ld_words, void* stream);
+/* Token rules: per-row bans, allow-lists and a minimum length, in front of everything above.  A row may carry a rule
+ * { always_row, early_row, early_until, first_row }.  The three *_row fields index a DEVICE mask table uint32 masks[mask_rows][mask_ld_words] in
+ * the seen bitmap's layout: bit t & 31 of word t >> 5 stands for token t, mask_ld_words >= ceil(n_vocab / 32) and a multiple of 4; a set bit
+ * means TOKEN BANNED.  A row index outside [0, mask_rows) means "none" (-1 is the canonical value; the kernel never reads out of range); bits
+ * for t >= n_vocab are ignored.  With c the tokens the row's sequence has generated so far — the counter the draw uses: state[b][4] in the
+ * accept form, counter[b * counter_stride] (NULL = 0) in the rows form — the banned set of a pick is the union of
+ *   masks[always_row] at every pick,   masks[early_row] while c < early_until,   masks[first_row] while c == 0.
+ * A banned token counts as a NON-FINITE ENTRY: no key, weight 0, never kept — how NaN / +-inf are treated above.  Everything else applies
+ * unchanged to the remaining entries: the penalty on seen tokens (ban and penalty commute: a banned token has no key either way), the greedy
+ * row's first index of the largest finite entry, the top-k counts, the top-p mass, the vocabulary-order pick.  A row with nothing left gives id
+ * 0, as a row without a finite entry does: a defined fall-back, the callers refuse such rules.  HF's SuppressTokensLogitsProcessor /
+ * NoBadWordsLogitsProcessor (single-token words) / an allow-list's complement (always_row), MinNewTokensLengthLogitsProcessor (early_row = the
+ * EOS ids, early_until = n) and SuppressTokensAtBeginLogitsProcessor (first_row), all in front of the warpers.
+ * The log-probability record below does NOT see the rule: it stays the log-softmax of the raw logits, as it does for the penalty.
+ *   fo1_sample_rows_ruled_bf16    fo1_sample_rows_seen_bf16 + rules
+ *   fo1_decode_head_ruled_accept  fo1_decode_head_accept + rules; the step reads masks and rules and never writes them
+ * rules: DEVICE table, one per row.  rules == NULL or masks == NULL: no row has a rule, the call is the _seen_ / _head_accept entry's.  Still one
+ * launch whatever the data, no host read, capturable, B <= 256; the same row, parameters and rule give the same id in any row of any batch. */
+typedef struct fo1_token_rule {
+    int32_t always_row, early_row, early_until, first_row;
+} fo1_token_rule_t;                     /* 16 bytes */
+int fo1_sample_rows_ruled_bf16(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params,
+                               const int32_t* counter /* NULL = 0 */, int counter_stride, const float* u /* device [B]; NULL = Philox */,
+                               int32_t* out /* [B] */, void* workspace, size_t workspace_bytes, const uint32_t* seen, long long ld_words,
+                               const uint32_t* masks, int mask_rows, long long mask_ld_words, const fo1_token_rule_t* rules /* device [B] */,
+                               void* stream);
+int fo1_decode_head_ruled_accept(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params,
+                                 int32_t* state, int32_t* plan, int32_t* ids_out, int ids_ld, const int32_t* stop_ids, int n_stop,
+                                 int32_t* done, void* workspace, size_t workspace_bytes, uint32_t* seen, long long ld_words,
+                                 const uint32_t* masks, int mask_rows, long long mask_ld_words, const fo1_token_rule_t* rules /* device [B] */,
+                                 void* stream);
 /* Log-probabilities of generated tokens.  For a bf16 logits row l[0..V) with F = { i : l_i finite }:
  *   m = max_F l,  S = sum_{i in F} exp(l_i - m) (fp32, a fixed order),  lp_i = (l_i - m) - log S as fp32 for i in F,  lp_i = -inf otherwise
  * (the sampler's rule: a non-finite entry has weight 0); a row with empty F gives -inf everywhere.  This is the log-softmax of the RAW logits:

@@ -5,13 +5,18 @@
   sampled    the general head fo1_decode_head_accept, every sequence sampled (T = 0.7, top_k = 50, top_p = 0.9),
   penalised  the same with repetition_penalty = 1.3 on every sequence (seen bitmap read in every pass),
   greedy_lp0 / greedy_lp8   the greedy head followed by the log-probability record (fo1_decode_logprob_record), every sequence asking for
-             it with top-n = 0 / 8.
+             it with top-n = 0 / 8,
+  greedy_general   the general head with every sequence a greedy row (no draw, no penalty, no rule): what `banned` and `min_new` add to,
+  banned     the ruled general head fo1_decode_head_ruled_accept, every sequence greedy with one shared mask row of 1000 banned ids,
+  sampled_banned   the same row on every sequence of `sampled`,
+  min_new    every sequence greedy with an early_row (16 ids) that is live on every timed step.
 The heads are timed alternately, `--rounds` times each in one process, so the spread of a figure is the spread between its rounds; the pool is
 drained and re-joined for every timing.  Prints one JSON object.
 
-    python scripts/pool_head_bench.py [--slots 128] [--steps 64] [--rounds 5] [--heads greedy sampled penalised greedy_lp0 greedy_lp8] [--root DIR]
+    python scripts/pool_head_bench.py [--slots 128] [--steps 64] [--rounds 5] [--heads greedy sampled penalised ...] [--root DIR]
 
-With `greedy` among the heads the output also holds each other head's increment over it (difference of the medians of this process).
+With `greedy` among the heads the output also holds each other head's increment over it (difference of the medians of this process), and
+for a ruled head its increment over the same head without a rule (banned, min_new: greedy_general; sampled_banned: sampled).
 
 --root DIR imports the package from another checkout (e.g. the parent commit, for the greedy figure of both on one box; only `greedy`
 exists there)."""
@@ -30,7 +35,7 @@ def main():
     ap.add_argument("--slots", type=int, default=128)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=5)
-    HEADS = ["greedy", "sampled", "penalised", "greedy_lp0", "greedy_lp8"]
+    HEADS = ["greedy", "sampled", "penalised", "greedy_lp0", "greedy_lp8", "greedy_general", "banned", "sampled_banned", "min_new"]
     ap.add_argument("--heads", nargs="+", default=HEADS[:3], choices=HEADS)
     ap.add_argument("--root", default=None, help="import vlm_fo1_amd from this checkout instead of the script's own")
     args = ap.parse_args()
@@ -58,6 +63,11 @@ def main():
                     penalised=dict(temperature=0.7, top_p=0.9, top_k=50, seed=11, repetition_penalty=1.3), greedy_lp0=None, greedy_lp8=None)
     top_n = dict(greedy_lp0=0, greedy_lp8=8)
     budget = 4 + args.steps + 8
+    V = eng.cfg.llm.vocab_size
+    ban = list(range(5, V, max(1, V // 1000)))[:1000]      # one set for every sequence: one shared row of the mask table
+    sampling.update(greedy_general=dict(greedy=True), banned=dict(greedy=True, ban=ban), sampled_banned=dict(sampling["sampled"], ban=ban),
+                    min_new=dict(greedy=True, ban_until=(budget + 1, list(range(3, 19)))))
+    unruled = dict(banned="greedy_general", min_new="greedy_general", sampled_banned="sampled")
 
     def one(head):
         left, base = P, 0
@@ -97,6 +107,9 @@ def main():
                                spread_pct=round(100.0 * (max(v) - min(v)) / statistics.median(v), 3))
     if "greedy" in times:
         out["increment_over_greedy_ms"] = {h: round(out["heads"][h]["median"] - out["heads"]["greedy"]["median"], 4) for h in times if h != "greedy"}
+    ruled = {h: round(out["heads"][h]["median"] - out["heads"][u]["median"], 4) for h, u in unruled.items() if h in times and u in times}
+    if ruled:
+        out["increment_over_unruled_ms"] = ruled
     print(json.dumps(out))
 
 

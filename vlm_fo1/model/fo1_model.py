@@ -262,14 +262,62 @@ class FO1ForCausalLM:
             raise ValueError(f"repetition_penalty must be a positive finite number, 1.0 switches it off (got {p!r})")
         return None if p32 == 1.0 else pv
 
+    @staticmethod
+    def _rule_plan(kwargs: dict, eos_ids=()) -> Optional[dict]:
+        """generate()'s suppress_tokens / begin_suppress_tokens / bad_words_ids / min_new_tokens / allowed_token_ids -> None (all off, the
+        default, whatever generation_config.json holds) or the engine's token-rule keys (vlm_fo1_amd.llm.token_rule, which checks the ids
+        against the vocabulary): ban = suppress_tokens + the single-token bad words (a longer entry is a NotImplementedError naming it),
+        ban_first = begin_suppress_tokens, allow = allowed_token_ids, ban_until = (min_new_tokens, the EOS ids) — HF's
+        MinNewTokensLengthLogitsProcessor: the EOS ids, not the stop keywords.  The values are sorted tuples: equal rules compare equal."""
+        def ids(name):
+            v = kwargs.get(name)
+            if v is None:
+                return None
+            if isinstance(v, torch.Tensor):
+                v = v.reshape(-1).tolist()
+            if isinstance(v, (str, bytes)) or not hasattr(v, "__iter__"):
+                raise ValueError(f"{name}: a list of token ids (got {v!r})")
+            return list(v)
+        plan = {}
+        ban = list(ids("suppress_tokens") or [])
+        words = kwargs.get("bad_words_ids")
+        if words is not None:
+            for w in words:
+                w = w.reshape(-1).tolist() if isinstance(w, torch.Tensor) else list(w)
+                if len(w) != 1:
+                    raise NotImplementedError(f"bad_words_ids: only single-token entries are banned on the device (got {w!r})")
+                ban.append(w[0])
+        if ban:
+            plan["ban"] = ban
+        if ids("begin_suppress_tokens"):
+            plan["ban_first"] = ids("begin_suppress_tokens")
+        if ids("allowed_token_ids") is not None:
+            plan["allow"] = ids("allowed_token_ids")      # (an empty allow-list is the engine's ValueError)
+        n = kwargs.get("min_new_tokens")
+        if n is not None:
+            if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+                raise ValueError(f"min_new_tokens must be an integer >= 0 (got {n!r})")
+            if n > 0 and len(tuple(eos_ids)):
+                plan["ban_until"] = (n, tuple(sorted(int(t) for t in eos_ids)))
+        for k in ("ban", "ban_first", "allow"):
+            if k in plan:
+                if any(isinstance(t, (bool, float)) or not hasattr(t, "__index__") for t in plan[k]):
+                    raise ValueError(f"{k}: token ids are integers (got {plan[k]!r})")
+                plan[k] = tuple(sorted(set(int(t) for t in plan[k])))
+        return plan or None
+
     @classmethod
-    def _decode_plan(cls, kwargs: dict, generation_config: Optional[dict] = None) -> Optional[dict]:
-        """_sampling_plan and _penalty_plan as the one dict the engine takes per request: None = plain greedy; a sampled request's dict
-        gains repetition_penalty; a greedy request with a penalty is dict(greedy=True, repetition_penalty=p)."""
-        sampling, pen = cls._sampling_plan(kwargs, generation_config), cls._penalty_plan(kwargs)
-        if pen is None:
+    def _decode_plan(cls, kwargs: dict, generation_config: Optional[dict] = None, eos_ids=()) -> Optional[dict]:
+        """_sampling_plan, _penalty_plan and _rule_plan as the one dict the engine takes per request: None = plain greedy; a sampled request's
+        dict gains repetition_penalty and the token-rule keys; a greedy request with a penalty or a rule is dict(greedy=True, ...)."""
+        sampling, pen, rule = cls._sampling_plan(kwargs, generation_config), cls._penalty_plan(kwargs), cls._rule_plan(kwargs, eos_ids)
+        if pen is None and rule is None:
             return sampling
-        return dict(greedy=True, repetition_penalty=pen) if sampling is None else dict(sampling, repetition_penalty=pen)
+        plan = dict(greedy=True) if sampling is None else dict(sampling)
+        if pen is not None:
+            plan["repetition_penalty"] = pen
+        plan.update(rule or {})
+        return plan
 
     @staticmethod
     def _logprob_plan(kwargs: dict) -> Optional[int]:
@@ -304,10 +352,12 @@ class FO1ForCausalLM:
         if stop is None or not self._fits_device_loop(k0.get("max_new_tokens", 512)):
             return None
         pooled = getattr(getattr(self, "engine", None), "_pool_svc", None) is not None
+        eos = tuple(self.config.eos_ids())
 
         def values(kw):      # what a packed batch without the pool must share
             sp = self._sampling_plan(dict(kw, seed=0), gen)
-            return (None if sp is None else (sp["temperature"], sp["top_p"], sp["top_k"])), self._penalty_plan(kw)
+            rule = self._rule_plan(kw, eos)
+            return (None if sp is None else (sp["temperature"], sp["top_p"], sp["top_k"])), self._penalty_plan(kw), rule and tuple(sorted(rule.items()))
         v0 = values(k0)
         mixed = False
         for kw in requests_kwargs[1:]:       # one budget and one stop rule per packed batch: refuse a mixed batch rather than apply the first's
@@ -321,9 +371,9 @@ class FO1ForCausalLM:
                     continue
                 if v != v0:      # without the pool one BatchDecoder group decodes the batch with one sampling
                     raise ValueError("generate_many: every request of a batch must share do_sample, temperature, top_p and top_k "
-                                     "(and repetition_penalty) unless the decode pool is enabled")
+                                     "(and repetition_penalty and the token-rule keywords) unless the decode pool is enabled")
                 raise ValueError("generate_many: every request of a sampled batch must share seed (request i draws on stream i of the one seed)")
-        sampling = [self._decode_plan(kw, gen) for kw in requests_kwargs] if mixed else self._decode_plan(k0, gen)
+        sampling = [self._decode_plan(kw, gen, eos) for kw in requests_kwargs] if mixed else self._decode_plan(k0, gen, eos)
         reqs = [self._request(kw.get("inputs"), kw.get("images"), kw.get("images_aux"), kw.get("image_grid_thws"), kw.get("bbox_list"))
                 for kw in requests_kwargs]
         return reqs, int(k0.get("max_new_tokens", 512)), stop, sampling
@@ -440,7 +490,8 @@ class FO1ForCausalLM:
     @torch.no_grad()
     def generate(self, inputs=None, images=None, images_aux=None, image_grid_thws=None, bbox_list=None, do_sample=False,
                  temperature=0.0, max_new_tokens=512, streamer=None, top_p=1.0, use_cache=True, stopping_criteria=None,
-                 pad_token_id=None, top_k=None, seed=None, repetition_penalty=None, _stream=0, output_logprobs=False, top_logprobs=0, **unused):
+                 pad_token_id=None, top_k=None, seed=None, repetition_penalty=None, _stream=0, output_logprobs=False, top_logprobs=0,
+                 suppress_tokens=None, begin_suppress_tokens=None, bad_words_ids=None, min_new_tokens=None, allowed_token_ids=None, **unused):
         """Decoding of one prompt: greedy, or with do_sample=True temperature / top-k / top-p sampling on the device (_sampling_plan).
         Returns [1, L_in + new] like HF generate (the reference slices `output_ids[0, inputs.shape[1]:]`, inference.py:47-48).  Without a
         streamer and with id-set stop criteria the whole loop runs on the device (BatchDecoder, no per-token host read); otherwise tokens
@@ -453,19 +504,25 @@ class FO1ForCausalLM:
         (log-probability of every generated token under the model's own distribution: the log-softmax of the raw logits, before temperature,
         top-k / top-p and the penalty), .top_ids int64 / .top_logprobs float32 [1, new, top_logprobs] (the most likely tokens of each step,
         0 <= top_logprobs <= 8).  The records are kept in the BatchDecoder's buffers: max_new_tokens beyond IDS_CAP is a ValueError, and with
-        a streamer or unexpressible stop criteria the generation steps a BatchDecoder of one (the same ids and records either way)."""
+        a streamer or unexpressible stop criteria the generation steps a BatchDecoder of one (the same ids and records either way).
+        suppress_tokens / bad_words_ids (single-token entries; a longer one is a NotImplementedError) / allowed_token_ids /
+        begin_suppress_tokens / min_new_tokens: HF's processors of those names in front of the pick, on the device (_rule_plan; DESIGN.md
+        section 14).  All default to off, whatever generation_config.json holds.  A constrained generation decodes as a penalised one does:
+        in the BatchDecoder, stepped one by one with a streamer or unexpressible stop criteria; max_new_tokens beyond IDS_CAP is a ValueError."""
         lpn = self._logprob_plan(dict(output_logprobs=output_logprobs, top_logprobs=top_logprobs))
         if lpn is not None and not self._fits_device_loop(max_new_tokens):
             from vlm_fo1_amd.llm import BatchDecoder
             raise ValueError(f"output_logprobs=True keeps at most {BatchDecoder.IDS_CAP} records per request (max_new_tokens={int(max_new_tokens)})")
         sampling = self._decode_plan(dict(do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k, seed=seed,
-                                          repetition_penalty=repetition_penalty), getattr(self.config, "_gen", None))
+                                          repetition_penalty=repetition_penalty, suppress_tokens=suppress_tokens,
+                                          begin_suppress_tokens=begin_suppress_tokens, bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens,
+                                          allowed_token_ids=allowed_token_ids), getattr(self.config, "_gen", None), self.config.eos_ids())
         req = self._request(inputs, images, images_aux, image_grid_thws, bbox_list)
         dev = self.device
         stop = self._device_stop_ids(stopping_criteria) if streamer is None else None
         if sampling is not None and not self._fits_device_loop(max_new_tokens):
             from vlm_fo1_amd.llm import BatchDecoder
-            raise ValueError(f"do_sample=True (and a repetition penalty) draws at most {BatchDecoder.IDS_CAP} tokens per request (max_new_tokens={int(max_new_tokens)})")
+            raise ValueError(f"do_sample=True (and a repetition penalty or a token rule) draws at most {BatchDecoder.IDS_CAP} tokens per request (max_new_tokens={int(max_new_tokens)})")
         if stop is not None and (sampling is None or _stream == 0 or sampling.get("greedy")) and self._fits_device_loop(max_new_tokens):
             res = self.engine.generate_batch([req], max_new_tokens=int(max_new_tokens), stop_ids=stop, use_graph=self.use_graph, sampling=sampling,
                                              logprobs=lpn)

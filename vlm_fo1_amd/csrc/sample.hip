@@ -28,6 +28,13 @@
 // pass still works on the 65 536 bf16 values; a penalised value that is not finite has no key.  A row with FO1_SAMPLE_GREEDY takes pass 1 without
 // counters and a first-index reduction, then leaves: the first index, in vocabulary order, of the largest (penalised) finite entry.  Both are
 // behind the template parameter: the plain instantiations compile to the code they were before it existed.
+//
+// The ruled head (RULE instantiations: fo1_sample_rows_ruled_bf16, fo1_decode_head_ruled_accept) reads one fo1_token_rule_t per row and resolves
+// it, once per workgroup, to the rows of the mask table live at this pick, at most three (bitmaps in the seen bitmap's layout, a set bit = token banned): `always_row`,
+// `early_row` while the row's counter c < early_until, `first_row` while c == 0; a row index outside the table means none.  Wherever a pass loads
+// a lane's 8 logits it also loads the matching byte of each active mask row, ORs them and replaces the banned entries by a NaN (no key) BEFORE
+// the penalty and the keying: a banned token is a non-finite entry to every pass — weight 0, never kept, never the greedy pick.  A row with
+// nothing left gives id 0, as a row without a finite entry does.  Behind a template parameter of its own, as the penalty is.
 #include "decode_common.h"
 
 namespace fo1 {
@@ -57,10 +64,33 @@ __device__ __forceinline__ uint32_t sp_penalise(uint32_t b, float p) {
     return (uint32_t)f32_to_bf16(l < 0.f ? l * p : __fdiv_rn(l, p));
 }
 
-// sp_load8; PEN: seen tokens come back as their penalised logit, so every pass keys the same 16-bit values
-template <bool PEN>
-__device__ __forceinline__ void sp_load8p(const uint16_t* __restrict__ row, const SpPen& pen, int i0, int V, bool vec, uint32_t (&e)[8]) {
+// what the rule needs of a row: the mask rows live at this pick (bytes, as SpPen::seen).  live == false: none; else all three pointers are
+// valid — a field without a live row repeats a live one (OR is idempotent), so a pass issues its three byte loads without a branch between them
+struct SpRule {
+    const uint8_t* m[3];
+    bool live;
+};
+
+// sp_load8; RULE: banned tokens come back as a NaN (no key); PEN: seen tokens come back as their penalised logit, so every pass keys the same
+// 16-bit values
+template <bool PEN, bool RULE>
+__device__ __forceinline__ void sp_load8p(const uint16_t* __restrict__ row, const SpPen& pen, const SpRule& rule, int i0, int V, bool vec,
+                                          uint32_t (&e)[8]) {
+    uint32_t ban = 0u;
+    if constexpr (RULE) {      // in front of the logits' load: the loads are in flight together
+        if (rule.live) {
+            const int i = min(i0, V - 1) >> 3;      // (byte < ceil(V / 8) <= 4 mask_ld_words: inside the mask row; past the row's end the entries are NaN already)
+            ban = (uint32_t)rule.m[0][i] | rule.m[1][i] | rule.m[2][i];
+        }
+    }
     sp_load8(row, i0, V, vec, e);
+    if constexpr (RULE) {
+        if (ban) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if ((ban >> j) & 1u) e[j] = 0x7fc0u;
+        }
+    }
     if constexpr (PEN) {
         if (pen.seen) {
             const uint32_t bits = i0 < V ? pen.seen[i0 >> 3] : 0u;
@@ -74,11 +104,11 @@ __device__ __forceinline__ void sp_load8p(const uint16_t* __restrict__ row, cons
 }
 
 // every key of the row, 8 tokens per thread and step (any order: the callers count or take a maximum)
-template <bool PEN, class F>
-__device__ __forceinline__ void sp_for_row(const uint16_t* __restrict__ row, const SpPen& pen, int V, bool vec, F f) {
+template <bool PEN, bool RULE, class F>
+__device__ __forceinline__ void sp_for_row(const uint16_t* __restrict__ row, const SpPen& pen, const SpRule& rule, int V, bool vec, F f) {
     for (int i0 = threadIdx.x * 8; i0 < V; i0 += SP_NT * 8) {
         uint32_t e[8];
-        sp_load8p<PEN>(row, pen, i0, V, vec, e);
+        sp_load8p<PEN, RULE>(row, pen, rule, i0, V, vec, e);
 #pragma unroll
         for (int j = 0; j < 8; ++j) f(sp_key(e[j]));
     }
@@ -124,6 +154,7 @@ struct SampleArgs {
     int* out;                                   // rows form: [B]
     int* state; int* plan; int* ids_out; int ids_ld; const int* stop_ids; int n_stop; int* done;     // accept form
     uint32_t* seen; long long ld_words;         // general head: the seen bitmap [rows][ld_words] (NULL: no row has a penalty)
+    const uint32_t* masks; int mask_rows; long long mask_ld_words; const fo1_token_rule_t* rules;      // ruled head: the mask table and the rows' rules
 };
 
 // Key scan of the half whose counters sit in `hist` (keys key0 .. key0 + 32767), top key down.  carry_c / carry_m: tokens and mass of the
@@ -168,7 +199,7 @@ __device__ __forceinline__ void sp_key_scan(const uint32_t* hist, int key0, int 
     __syncthreads();
 }
 
-template <bool ACCEPT, bool PEN>
+template <bool ACCEPT, bool PEN, bool RULE = false>
 __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
     extern __shared__ __align__(16) unsigned char sp_smem[];
     uint32_t* hist = reinterpret_cast<uint32_t*>(sp_smem);
@@ -203,6 +234,22 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
             pen.p = rp;
         }
     }
+    SpRule rule{{nullptr, nullptr, nullptr}, false};
+    if constexpr (RULE) {      // the mask rows live at this pick (uniform per row); an index outside the table: none
+        const fo1_token_rule_t R = a.rules[b];
+        const int c = ACCEPT ? st[4] : (a.counter ? a.counter[(long long)b * a.counter_stride] : 0);
+        const int rows3[3] = {R.always_row, c < R.early_until ? R.early_row : -1, c == 0 ? R.first_row : -1};
+        int any = -1;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+            if (rows3[r] >= 0 && rows3[r] < a.mask_rows) any = rows3[r];
+        rule.live = any >= 0;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int k = rows3[r] >= 0 && rows3[r] < a.mask_rows ? rows3[r] : any;
+            if (rule.live) rule.m[r] = reinterpret_cast<const uint8_t*>(a.masks + (long long)k * a.mask_ld_words);
+        }
+    }
 
     // 1. largest finite key (+ the non-negative half's counters)
     if (tid == 0) { s_kcut_k = -1; s_range = 0x7fffffff; s_kcut_p = 0; s_tok = 0; s_z1 = 0.f; }
@@ -211,12 +258,12 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
     __syncthreads();
     int kmax = -1;
     if (cut)
-        sp_for_row<PEN>(row, pen, V, vec, [&](int k) {
+        sp_for_row<PEN, RULE>(row, pen, rule, V, vec, [&](int k) {
             kmax = max(kmax, k);
             if (k >= 0x8000) atomicAdd(&hist[sp_slot(k & 0x7fff)], 1u);
         });
     else
-        sp_for_row<PEN>(row, pen, V, vec, [&](int k) { kmax = max(kmax, k); });
+        sp_for_row<PEN, RULE>(row, pen, rule, V, vec, [&](int k) { kmax = max(kmax, k); });
     kmax = sp_wave_max(kmax);
     if (lane == 0) s_wi[wave] = kmax;
     __syncthreads();
@@ -228,7 +275,7 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
             int first = 0x7fffffff;
             for (int i0 = tid * 8; i0 < V; i0 += SP_NT * 8) {
                 uint32_t e[8];
-                sp_load8p<PEN>(row, pen, i0, V, vec, e);
+                sp_load8p<PEN, RULE>(row, pen, rule, i0, V, vec, e);
 #pragma unroll
                 for (int j = 7; j >= 0; --j)
                     if (sp_key(e[j]) == kmax) first = min(first, i0 + j);
@@ -251,7 +298,7 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
             if (s_kcut_k < 0) {      // no top-k cut-off yet: the negative half (uniform: shared value read after the scan's barrier)
                 for (int i = tid; i < SP_HALF; i += SP_NT) hist[i] = 0;
                 __syncthreads();
-                sp_for_row<PEN>(row, pen, V, vec, [&](int k) {
+                sp_for_row<PEN, RULE>(row, pen, rule, V, vec, [&](int k) {
                     if (k >= 0 && k < 0x8000) atomicAdd(&hist[sp_slot(k)], 1u);
                 });
                 __syncthreads();
@@ -280,7 +327,7 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
                     if (!resident) {
                         if (tid < SP_KPT) mini[tid] = 0;
                         __syncthreads();
-                        sp_for_row<PEN>(row, pen, V, vec, [&](int k) {
+                        sp_for_row<PEN, RULE>(row, pen, rule, V, vec, [&](int k) {
                             if (k >= key_lo && k < key_lo + SP_KPT) atomicAdd(&mini[k - key_lo], 1u);
                         });
                         __syncthreads();
@@ -318,7 +365,7 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
         for (int s0 = r0; s0 < r0 + region && s0 < V; s0 += SP_SLICE) {
             uint32_t e[8];
             const int i0 = s0 + lane * 8;
-            sp_load8p<PEN>(row, pen, i0, V, vec, e);
+            sp_load8p<PEN, RULE>(row, pen, rule, i0, V, vec, e);
             float s = 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -352,7 +399,7 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
             for (int s0 = r0; s0 < r0 + region && s0 < V && pick < 0; s0 += SP_SLICE) {
                 uint32_t e[8];
                 const int i0 = s0 + lane * 8;
-                sp_load8p<PEN>(row, pen, i0, V, vec, e);
+                sp_load8p<PEN, RULE>(row, pen, rule, i0, V, vec, e);
                 float wj[8], s = 0.f;
                 int lm = -1;
 #pragma unroll
@@ -409,11 +456,12 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
 
 constexpr size_t SP_WORKSPACE = 256;      // the one-workgroup-per-row kernel keeps everything in LDS; the argument stays for a split form
 
-template <bool ACCEPT, bool PEN>
+template <bool ACCEPT, bool PEN, bool RULE = false>
 static int launch_sample(const SampleArgs& a, int B, hipStream_t st) {
-    FO1_DYNAMIC_LDS_ONCE(SP_SMEM, sample_rows_kernel<ACCEPT, PEN>);
-    FO1_LAUNCH(PEN ? (ACCEPT ? "head_accept" : "sample_rows_seen") : (ACCEPT ? "sample_accept" : "sample_rows"), (double)B * a.V * 2.0,
-               (sample_rows_kernel<ACCEPT, PEN>), dim3(B), dim3(SP_NT), SP_SMEM, st, a);
+    FO1_DYNAMIC_LDS_ONCE(SP_SMEM, sample_rows_kernel<ACCEPT, PEN, RULE>);
+    FO1_LAUNCH(RULE ? (ACCEPT ? "head_ruled_accept" : "sample_rows_ruled")
+                    : PEN ? (ACCEPT ? "head_accept" : "sample_rows_seen") : (ACCEPT ? "sample_accept" : "sample_rows"),
+               (double)B * a.V * 2.0, (sample_rows_kernel<ACCEPT, PEN, RULE>), dim3(B), dim3(SP_NT), SP_SMEM, st, a);
     return FO1_OK;
 }
 
@@ -431,6 +479,14 @@ static int check_seen(const char* who, const void* seen, long long ld_words, int
     FO1_CHECK_ARG(!seen || (ld_words % 4 == 0 && ld_words >= ((long long)V + 31) / 32), "%s: ld_words=%lld (a multiple of 4, >= ceil(n_vocab / 32) = %d)", who,
                   ld_words, (V + 31) / 32);
     FO1_CHECK_ARG(!seen || ((uintptr_t)seen & 3) == 0, "%s: seen must be 4-byte aligned", who);
+    return FO1_OK;
+}
+
+static int check_masks(const char* who, const void* masks, int mask_rows, long long mask_ld_words, int V) {
+    FO1_CHECK_ARG(!masks || (mask_ld_words % 4 == 0 && mask_ld_words >= ((long long)V + 31) / 32),
+                  "%s: mask_ld_words=%lld (a multiple of 4, >= ceil(n_vocab / 32) = %d)", who, mask_ld_words, (V + 31) / 32);
+    FO1_CHECK_ARG(!masks || mask_rows > 0, "%s: mask_rows=%d with a mask table (>= 1)", who, mask_rows);
+    FO1_CHECK_ARG(!masks || ((uintptr_t)masks & 3) == 0, "%s: masks must be 4-byte aligned", who);
     return FO1_OK;
 }
 
@@ -506,6 +562,45 @@ int fo1_decode_head_accept(const void* logits, long long ld_logits, int n_vocab,
     a.state = (int*)state; a.plan = (int*)plan; a.ids_out = (int*)ids_out; a.ids_ld = ids_ld; a.stop_ids = (const int*)stop_ids; a.n_stop = n_stop;
     a.done = (int*)done; a.seen = seen; a.ld_words = ld_words;
     return launch_sample<true, true>(a, B, (hipStream_t)stream);
+}
+
+// fo1_sample_rows_seen_bf16 with the rows' token rules honoured (the head of this file; include/fo1.h).  rules == NULL or masks == NULL: no row
+// has a rule, and the call is fo1_sample_rows_seen_bf16's.
+int fo1_sample_rows_ruled_bf16(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params, const int32_t* counter,
+                               int counter_stride, const float* u, int32_t* out, void* workspace, size_t workspace_bytes, const uint32_t* seen,
+                               long long ld_words, const uint32_t* masks, int mask_rows, long long mask_ld_words, const fo1_token_rule_t* rules,
+                               void* stream) {
+    using namespace fo1;
+    if (int rc = check_sample("sample_rows_ruled", logits, ld_logits, n_vocab, B, params, workspace, workspace_bytes)) return rc;
+    if (int rc = check_seen("sample_rows_ruled", seen, ld_words, n_vocab)) return rc;
+    if (int rc = check_masks("sample_rows_ruled", masks, mask_rows, mask_ld_words, n_vocab)) return rc;
+    FO1_CHECK_ARG(out != nullptr, "sample_rows_ruled: NULL out");
+    SampleArgs a{};
+    a.logits = (const uint16_t*)logits; a.ld = ld_logits; a.V = n_vocab; a.params = params; a.counter = (const int*)counter;
+    a.counter_stride = counter_stride; a.u = u; a.out = (int*)out; a.seen = const_cast<uint32_t*>(seen); a.ld_words = ld_words;
+    if (!masks || !rules) return launch_sample<false, true>(a, B, (hipStream_t)stream);
+    a.masks = masks; a.mask_rows = mask_rows; a.mask_ld_words = mask_ld_words; a.rules = rules;
+    return launch_sample<false, true, true>(a, B, (hipStream_t)stream);
+}
+
+// fo1_decode_head_accept with the rows' token rules honoured (counter = state[b][4]).  rules == NULL or masks == NULL: fo1_decode_head_accept.
+// The step reads the mask table and the rules, it never writes them.
+int fo1_decode_head_ruled_accept(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params, int32_t* state,
+                                 int32_t* plan, int32_t* ids_out, int ids_ld, const int32_t* stop_ids, int n_stop, int32_t* done, void* workspace,
+                                 size_t workspace_bytes, uint32_t* seen, long long ld_words, const uint32_t* masks, int mask_rows,
+                                 long long mask_ld_words, const fo1_token_rule_t* rules, void* stream) {
+    using namespace fo1;
+    if (int rc = check_sample("decode_head_ruled_accept", logits, ld_logits, n_vocab, B, params, workspace, workspace_bytes)) return rc;
+    if (int rc = check_seen("decode_head_ruled_accept", seen, ld_words, n_vocab)) return rc;
+    if (int rc = check_masks("decode_head_ruled_accept", masks, mask_rows, mask_ld_words, n_vocab)) return rc;
+    FO1_CHECK_ARG(state && plan && ids_out && done && ids_ld > 0 && n_stop >= -1 && (n_stop == 0 || stop_ids), "decode_head_ruled_accept: bad arguments");
+    SampleArgs a{};
+    a.logits = (const uint16_t*)logits; a.ld = ld_logits; a.V = n_vocab; a.params = params;
+    a.state = (int*)state; a.plan = (int*)plan; a.ids_out = (int*)ids_out; a.ids_ld = ids_ld; a.stop_ids = (const int*)stop_ids; a.n_stop = n_stop;
+    a.done = (int*)done; a.seen = seen; a.ld_words = ld_words;
+    if (!masks || !rules) return launch_sample<true, true>(a, B, (hipStream_t)stream);
+    a.masks = masks; a.mask_rows = mask_rows; a.mask_ld_words = mask_ld_words; a.rules = rules;
+    return launch_sample<true, true, true>(a, B, (hipStream_t)stream);
 }
 
 // Sets bit ids[i] of row rows[i] of the seen bitmap for i < n (device int32 each; duplicates are fine).  Ids outside [0, n_vocab) and negative

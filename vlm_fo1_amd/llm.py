@@ -14,6 +14,7 @@ import math
 from dataclasses import dataclass
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import ops
@@ -694,7 +695,16 @@ def sampling_table(sampling, B: int):
     sequence, and per sequence "plain" (None: greedy, no penalty), "sampled" (a draw, no penalty) or "general" (greedy flag or a penalty).
     sampling: None; one dict for the submission (temperature, top_p, top_k, seed — optional when greedy=True — plus greedy,
     repetition_penalty; sequence b draws on stream streams[b], or stream + b, default b); or a list with one such dict (its own `stream`,
-    default b) or None per sequence."""
+    default b) or None per sequence.  A dict with a token-rule key (RULE_KEYS: ban, ban_first, allow, ban_until — token_rule) is "general"
+    too: dict(greedy=True, ban=[...]) is a constrained greedy sequence."""
+    per = _per_sequence(sampling, B)
+    rows = [ops.sampling_row(sp, b) for b, sp in enumerate(per)]
+    kinds = ["plain" if sp is None else ("general" if (r[5] or ops.penalty_on(r[6]) or has_rule(sp)) else "sampled") for sp, r in zip(per, rows)]
+    return rows, kinds
+
+
+def _per_sequence(sampling, B: int) -> list:
+    """sampling_table's argument -> one dict or None per sequence."""
     if sampling is None:
         per = [None] * B
     elif isinstance(sampling, dict):
@@ -706,9 +716,149 @@ def sampling_table(sampling, B: int):
         per = list(sampling)
         if len(per) != B:
             raise ValueError(f"sampling: {len(per)} entries for {B} sequences")
-    rows = [ops.sampling_row(sp, b) for b, sp in enumerate(per)]
-    kinds = ["plain" if sp is None else ("general" if (r[5] or ops.penalty_on(r[6])) else "sampled") for sp, r in zip(per, rows)]
-    return rows, kinds
+    return per
+
+
+RULE_KEYS = ("ban", "ban_first", "allow", "ban_until")      # the token-rule keys of a sequence's sampling dict (token_rule)
+
+
+def has_rule(sp: Optional[dict]) -> bool:
+    return sp is not None and any(sp.get(k) is not None for k in RULE_KEYS)
+
+
+class TokenRule(NamedTuple):
+    """A sequence's normalised token rule (include/fo1.h, fo1_token_rule_t): up to three banned sets as bitmaps in the seen bitmap's layout
+    (bytes of ops.seen_words(V) words; None = empty) — `always` at every pick, `early` while fewer than `until` tokens have been generated,
+    `first` at the first token."""
+    always: Optional[bytes]
+    early: Optional[bytes]
+    until: int
+    first: Optional[bytes]
+
+    def bitmaps(self) -> list:
+        return [m for m in (self.always, self.early, self.first) if m is not None]
+
+
+def _token_ids(ids, V: int, what: str) -> List[int]:
+    if isinstance(ids, (str, bytes)) or not hasattr(ids, "__iter__"):
+        raise ValueError(f"{what}: a list of token ids (got {ids!r})")
+    out = []
+    for t in ids:
+        if isinstance(t, (bool, float)) or not hasattr(t, "__index__"):
+            raise ValueError(f"{what}: token ids are integers (got {t!r})")
+        t = int(t)
+        if not 0 <= t < V:
+            raise ValueError(f"{what}: token id {t} outside [0, {V})")
+        out.append(t)
+    return out
+
+
+def token_rule(spec: Optional[dict], V: int, eos_ids: Sequence[int] = ()) -> Optional[TokenRule]:
+    """The token-rule keys of a sequence's sampling dict -> its TokenRule, or None for a dict without one:
+      ban=ids           never picked;
+      allow=ids         only these may be picked: everything else is banned, unioned with `ban`;
+      ban_first=ids     not picked as the first generated token;
+      ban_until=(n, ids)  not picked among the first n generated tokens (HF's min_new_tokens with ids = the EOS ids; a bare n takes eos_ids).
+    ValueError: an id that is not an integer or lies outside [0, V), an empty allow, n < 0, or a phase of the sequence (first token, tokens
+    before n, tokens from n on) whose union bans all V tokens."""
+    if not has_rule(spec):
+        return None
+    V = int(V)
+
+    def bits(ids):
+        m = np.zeros(V, dtype=bool)
+        m[ids] = True
+        return m
+
+    always = bits(_token_ids(spec.get("ban") or (), V, "ban"))
+    if spec.get("allow") is not None:
+        allow = _token_ids(spec["allow"], V, "allow")
+        if not allow:
+            raise ValueError("allow: an empty allow-list leaves no token to pick")
+        always |= ~bits(allow)
+    first = bits(_token_ids(spec.get("ban_first") or (), V, "ban_first"))
+    early, until = np.zeros(V, dtype=bool), 0
+    if spec.get("ban_until") is not None:
+        bu = spec["ban_until"]
+        n, ids = (bu, eos_ids) if not hasattr(bu, "__len__") else (bu if len(bu) == 2 else (None, None))
+        if isinstance(n, (bool, float)) or not hasattr(n, "__index__"):
+            raise ValueError(f"ban_until: (n, ids) with an integer n (got {bu!r})")
+        if int(n) < 0:
+            raise ValueError(f"ban_until: n = {int(n)} < 0")
+        until = int(n)
+        if until > 0:
+            early = bits(_token_ids(ids, V, "ban_until"))
+    for what, m in (("at every token", always), ("before ban_until's n tokens", always | early), ("at the first token", always | early | first)):
+        if m.all():
+            raise ValueError(f"token rule: every one of the {V} tokens is banned {what}")
+
+    def pack(m):
+        if not m.any():
+            return None
+        out = np.zeros(ops.seen_words(V) * 4, dtype=np.uint8)
+        pk = np.packbits(m, bitorder="little")
+        out[:pk.size] = pk
+        return out.tobytes()
+
+    e = pack(early)
+    return TokenRule(pack(always), e, until if e is not None else 0, pack(first))
+
+
+def sampling_rules(sampling, B: int, V: int, eos_ids: Sequence[int] = ()) -> List[Optional[TokenRule]]:
+    """sampling_table's argument -> the TokenRule (or None) of every sequence."""
+    return [token_rule(sp, V, eos_ids) for sp in _per_sequence(sampling, B)]
+
+
+class TokenMasks:
+    """Device side of the token rules of a decoder's rows: the mask table int32 [rows, seen_words(V)] (a set bit = token banned) and a host map
+    from a bitmap's bytes to its row with a user count.  Equal sets share a row; a row with users is never rewritten (a captured step reads
+    the table, it never writes it).  Allocated by the first constrained sequence, as the seen bitmap is by the first penalised one."""
+
+    def __init__(self, rows: int, n_vocab: int, dev):
+        with torch.inference_mode(False):
+            self.table = torch.zeros(rows, ops.seen_words(n_vocab), dtype=torch.int32, device=dev)
+        self.rows = rows
+        self._row: Dict[bytes, int] = {}
+        self.users = [0] * rows
+        self._keep: list = []
+
+    def room(self, bitmaps: Sequence[bytes]) -> bool:
+        """Is there a row for every one of these bitmaps (its own, or one without users)?"""
+        new = {m for m in bitmaps if m not in self._row}
+        taken = {self._row[m] for m in bitmaps if m in self._row}
+        return len(new) <= sum(1 for r in range(self.rows) if self.users[r] == 0 and r not in taken)
+
+    def acquire(self, bitmap: bytes) -> int:
+        """The row holding `bitmap`, one user more; a new bitmap is uploaded (current stream) into a row without users."""
+        if len(bitmap) != self.table.shape[1] * 4:
+            raise ValueError(f"TokenMasks: a bitmap has {self.table.shape[1] * 4} bytes (got {len(bitmap)})")
+        row = self._row.get(bitmap)
+        if row is None:
+            held = set(self._row.values())
+            free = [r for r in range(self.rows) if self.users[r] == 0 and r not in held] or [r for r in range(self.rows) if self.users[r] == 0]
+            if not free:
+                raise RuntimeError(f"TokenMasks: {self.rows} different token masks are live; wait for sequences to finish")
+            row = free[0]
+            for k in [k for k, v in self._row.items() if v == row]:
+                del self._row[k]
+            host = torch.frombuffer(bytearray(bitmap), dtype=torch.int32).view(1, -1)
+            self.table[row:row + 1].copy_(host, non_blocking=True)
+            self._keep.append(host)
+            if len(self._keep) > 2 * self.rows:
+                del self._keep[:len(self._keep) - 2 * self.rows]
+            self._row[bitmap] = row
+        self.users[row] += 1
+        return row
+
+    def release(self, row: int) -> None:
+        if row >= 0:
+            assert self.users[row] > 0
+            self.users[row] -= 1
+
+    def rule_row(self, rule: TokenRule):
+        """Acquires the rows of a sequence's rule -> (its fo1_token_rule_t row, the rows to release when it leaves)."""
+        a, e, f = (-1 if m is None else self.acquire(m) for m in (rule.always, rule.early, rule.first))
+        return (a, e, rule.until, f), [r for r in (a, e, f) if r >= 0]
 
 
 def new_seen(rows: int, n_vocab: int, dev) -> torch.Tensor:
@@ -822,6 +972,10 @@ class BatchDecoder:
         self.general = False       # ... in the general head: some row has the greedy flag or a repetition penalty
         self.seen = None           # seen bitmap [MAX_BATCH, ld_words], allocated by the first start() with a penalty
         self.lpb = None            # log-probability records (LogprobBuffers), allocated by the first start() that asks for them
+        self.masks = None          # token rules: the mask table (TokenMasks) and the per-row rule table, allocated by the first start() with a rule
+        self.rules = None
+        self.ruled = False         # some row of the current start() has a rule: the general head runs in its ruled form
+        self._mask_rows: List[int] = []      # mask rows the current start() holds
         self.lp_want: List[int] = []       # per sequence of the current start(): -1 = no record, else its top-n
         self.n_stop = 0
         self.dk = self.dvt = None
@@ -857,6 +1011,8 @@ class BatchDecoder:
         0 .. B - 1, the sequence's index in its request list.  A dict with greedy=True or a repetition_penalty, or a list with one dict or
         None per sequence (sampling_table), ends every step in the general head (fo1_decode_head_accept); a penalty needs prompt_ids, the
         ids each request passed: they and the first tokens seed the sequence's seen set (the caller picked the first tokens with it).
+        A dict's token-rule keys (ban, allow, ban_first, ban_until: token_rule) restrict that sequence's picks on the device; the rows of the
+        mask table they take are held until the next start().
         logprobs (logprob_wants): None, one int or a list with None / int per sequence = the top-n of the log-probability record kept for that
         sequence (logprobs()); orthogonal to `sampling`: the record launch follows whichever head the step ends in.  first_logprobs: the first
         tokens' records, ops.logprob_rows on the prefill's logits with the largest requested n (FO1Engine._first_logprobs)."""
@@ -890,11 +1046,13 @@ class BatchDecoder:
         self.stop.copy_(stop, non_blocking=True)
         self._keep = [reloc, state, stop]                 # sources of the async uploads stay alive
         srows, kinds = sampling_table(sampling, B)
+        trules = sampling_rules(sampling, B, llm.cfg.vocab_size)
         self.sampled = any(k != "plain" for k in kinds)
         self.general = self.sampled and any(k != "sampled" for k in kinds)
         penalised = any(ops.penalty_on(r[6]) for r in srows)
         if penalised and (prompt_ids is None or len(prompt_ids) != B):
             raise ValueError("BatchDecoder: a repetition penalty needs prompt_ids, one list per sequence")
+        self._start_rules(trules)
         if self.sampled:
             sp = ops.sample_params(srows)
             self.sparams[:B].copy_(sp, non_blocking=True)
@@ -916,6 +1074,31 @@ class BatchDecoder:
                 rt = torch.arange(B, dtype=torch.int32)
                 self._keep.append(rt)
                 ops.seen_mark(self.seen, llm.cfg.vocab_size, rt.to(first.device, non_blocking=True), first)
+
+    def _start_rules(self, trules):
+        """The previous run's mask rows go back; this run's rules take theirs (3 rows per sequence at most: there is always room)."""
+        if self.masks is not None:
+            for r in self._mask_rows:
+                self.masks.release(r)
+        self._mask_rows = []
+        self.ruled = any(t is not None for t in trules)
+        if not self.ruled:
+            return
+        if self.masks is None:
+            self.masks = TokenMasks(3 * self.MAX_BATCH, self.llm.cfg.vocab_size, self.llm.dev)
+            with torch.inference_mode(False):
+                self.rules = ops.token_rules([None] * self.MAX_BATCH, self.llm.dev)
+        table = []
+        for t in trules:
+            row, held = (None, []) if t is None else self.masks.rule_row(t)
+            table.append(row)
+            self._mask_rows += held
+        rt = ops.token_rules(table)
+        self.rules[:len(table)].copy_(rt, non_blocking=True)
+        self._keep.append(rt)
+
+    def _rule_args(self) -> dict:
+        return dict(masks=self.masks.table, rules=self.rules[:self.B]) if self.ruled else {}
 
     KV_BUCKET = 2048
 
@@ -953,7 +1136,8 @@ class BatchDecoder:
                 x = ops.gemv_batch(a, w["wdown"], residual=x)
             logits = ops.gemv_batch(x, llm.lm_head, norm_weight=llm.norm, norm_eps=c.rms_norm_eps)
             if self.general:
-                ops.decode_head_accept(logits, self.sparams[:B], st, self.plan[:B], self.ids[:B], self.stop[:self.n_stop], self.done, seen=self.seen)
+                ops.decode_head_accept(logits, self.sparams[:B], st, self.plan[:B], self.ids[:B], self.stop[:self.n_stop], self.done, seen=self.seen,
+                                       **self._rule_args())
             elif self.sampled:
                 ops.decode_sample_accept(logits, self.sparams[:B], st, self.plan[:B], self.ids[:B], self.stop[:self.n_stop], self.done)
             else:
@@ -981,6 +1165,8 @@ class BatchDecoder:
         if self.general:     # (one more form; the bitmap's identity is baked into its graph, and the warm-up step sets bits in it)
             seen = () if self.seen is None else (self.seen,)
             key += ("general", self.seen.data_ptr() if seen else 0)
+            if self.ruled:   # (the ruled form reads the mask and rule tables and writes neither: identity in the key, nothing more to roll back)
+                key += ("ruled", self.masks.table.data_ptr(), self.rules.data_ptr())
         if self.recording:   # (and one more: the record launch bakes the buffers' identity in, and the warm-up step writes them)
             key += ("logprobs", self.lpb.lp.data_ptr())
             seen += self.lpb.written()
@@ -1070,6 +1256,7 @@ class DecodePool:
     IDS_CAP = 4096
     MAX_STOP = 16
     MAX_SETS = 32            # distinct stop-id sets live in the pool at once
+    MAX_MASKS = 64           # distinct token masks (rows of the mask table) live in the pool at once
     KV_BUCKET = 256          # the attention launch geometry follows the longest live context rounded up to this many keys
 
     def __init__(self, llm: QwenLLM, slots: int = 128, slot_rows: int = 1024):
@@ -1092,6 +1279,11 @@ class DecodePool:
         self.seen = None                               # seen bitmap [P, ld_words], allocated when the first penalised sequence joins
         self.kind = ["plain"] * P                      # what each slot's sparams row holds: "plain", "sampled" or "general"
         self.n_general = 0                             # live slots that are not plain: > 0 ends the step in the general head
+        self.masks = None                              # token rules: the mask table (TokenMasks) and the per-slot rule table, allocated when
+        self.rules = None                              # the first constrained sequence joins
+        self.ruled_dev = [False] * P                   # does the slot's rule row on the device hold a rule (tracked as `kind` is)
+        self.slot_masks: List[List[int]] = [[] for _ in range(P)]      # mask rows a live slot holds
+        self.n_ruled = 0                               # live slots with a rule: > 0 runs the general head in its ruled form
         self.lpb = None                                # log-probability records (LogprobBuffers), allocated when the first requesting sequence joins
         self.lp_want = [-1] * P                        # a live slot's request: -1 = no record, else its top-n
         self.lp_dev = [-1] * P                         # what each slot's `want` word on the device holds (tracked as `kind` is)
@@ -1151,7 +1343,9 @@ class DecodePool:
         list with one dict or None per sequence = that sequence's row of the per-slot parameter table — temperature / top-k / top-p draws
         on Philox(tokens generated so far, stream; seed), greedy=True, repetition_penalty.  A penalty needs prompt_ids (the ids each request
         passed): the slot's seen-bitmap row is cleared and marked with them and with the first token, which the caller picked with the
-        prompt's set.  While any live slot is not plain the step ends in the general head (step()).
+        prompt's set.  While any live slot is not plain the step ends in the general head (step()).  A dict's token-rule keys (ban, allow,
+        ban_first, ban_until: token_rule) restrict that sequence's picks on the device: equal banned sets share a row of the mask table, at
+        most MAX_MASKS distinct ones are live at once (can_take), and the rows are released when the sequence is harvested.
         logprobs / first_logprobs: as BatchDecoder.start takes them; while any live slot asks for a record the record launch follows the head
         (step()), and harvest(records=True) hands the finished slots' records out.  A pool no requesting sequence ever joined holds no
         record buffer and issues exactly the launches and copies it always has."""
@@ -1160,9 +1354,12 @@ class DecodePool:
         if any(w >= 0 for w in wants) and first_logprobs is None:
             raise ValueError("DecodePool: logprobs needs first_logprobs, the first tokens' records")
         srows, kinds = sampling_table(sampling, B)
+        trules = sampling_rules(sampling, B, self.llm.cfg.vocab_size)
         penalised = [ops.penalty_on(r[6]) for r in srows]
         if any(penalised) and (prompt_ids is None or len(prompt_ids) != B):
             raise ValueError("DecodePool: a repetition penalty needs prompt_ids, one list per sequence")
+        if not self._mask_room(trules):
+            raise RuntimeError(f"DecodePool: {self.MAX_MASKS} different token masks are live; wait for sequences to finish")
         set_row = self._stop_set_row(tuple(stop_id_list(stop_ids, self.MAX_STOP, "DecodePool")))
         max_new = token_budget(max_new_tokens, self.IDS_CAP, "DecodePool")
         if B > len(self.free):
@@ -1174,6 +1371,7 @@ class DecodePool:
         try:
             self._join_slots(slots, kcache, vtcache, seqs, deltas, first_tokens, max_new, set_row)
             self._join_sampling(slots, srows, kinds, penalised, first_tokens, prompt_ids)
+            self._join_rules(slots, trules)
             self._join_logprobs(slots, wants, first_logprobs)
         except BaseException:
             # nothing of this submission is live: its slots go back (their device state may be half written — the next occupant's
@@ -1186,6 +1384,8 @@ class DecodePool:
             except BaseException:
                 pass
             self.free += slots
+            for s in slots:
+                self._release_masks(s)
             raise
         for k, s in enumerate(slots):
             # a tag identifies ONE occupancy of a slot: harvest() compares it by identity against an older snapshot, so the default must
@@ -1196,6 +1396,7 @@ class DecodePool:
             self.slot_set[s] = set_row
             self._set_users[set_row] += 1
             self.n_general += kinds[k] != "plain"
+            self.n_ruled += trules[k] is not None
             self.lp_want[s] = wants[k]
             self.n_logprob += wants[k] >= 0
         return slots
@@ -1211,6 +1412,38 @@ class DecodePool:
         self._keep += self.lpb.set_rows([slots[k] for k in write], [wants[k] for k in write], first_logprobs, write)
         for k in write:
             self.lp_dev[slots[k]] = wants[k]
+
+    def _mask_room(self, trules) -> bool:
+        maps = [m for t in trules if t is not None for m in t.bitmaps()]
+        if not maps:
+            return True
+        return self.masks.room(maps) if self.masks is not None else len(set(maps)) <= self.MAX_MASKS
+
+    def _join_rules(self, slots, trules):
+        """The rule rows of a submission's slots.  Nothing is enqueued for a sequence without a rule whose slot holds none: a slot a
+        constrained sequence has left gets -1 back when an unconstrained one reuses it."""
+        write = [k for k, s in enumerate(slots) if trules[k] is not None or self.ruled_dev[s]]
+        if not write:
+            return
+        if self.masks is None:      # (graphs captured before are unreachable for a ruled step: its key holds the tables' identity)
+            self.masks = TokenMasks(self.MAX_MASKS, self.llm.cfg.vocab_size, self.llm.dev)
+            with torch.inference_mode(False):
+                self.rules = ops.token_rules([None] * self.P, self.llm.dev)
+        table = []
+        for k in write:
+            row, held = (None, []) if trules[k] is None else self.masks.rule_row(trules[k])
+            table.append(row)
+            self.slot_masks[slots[k]] += held
+        rt = ops.token_rules(table)
+        self._keep.append(rt)
+        for j, k in enumerate(write):
+            self.rules[slots[k]:slots[k] + 1].copy_(rt[j:j + 1], non_blocking=True)
+            self.ruled_dev[slots[k]] = trules[k] is not None
+
+    def _release_masks(self, slot: int) -> None:
+        for r in self.slot_masks[slot]:
+            self.masks.release(r)
+        self.slot_masks[slot] = []
 
     def _join_sampling(self, slots, srows, kinds, penalised, first_tokens, prompt_ids):
         """The parameter rows and seen sets of a submission's slots.  Nothing is enqueued for a plain sequence whose slot still holds the
@@ -1234,10 +1467,18 @@ class DecodePool:
                 self._keep += ops.mark_prompts(self.seen, V, [slots[k] for k in pen], [prompt_ids[k] for k in pen])
                 ops.seen_mark(self.seen, V, rt.to(first.device, non_blocking=True), first)
 
-    def can_take(self, stop_ids: Sequence[int]) -> bool:
-        """Is there a table row for this stop-id set (its own, or one no live slot uses)?"""
+    def can_take(self, stop_ids: Sequence[int], sampling=None, B: int = 0) -> bool:
+        """Is there a table row for this stop-id set (its own, or one no live slot uses) — and, for a submission of B sequences with
+        `sampling`, a mask-table row for every banned set of its token rules?  (A malformed rule answers True: join() raises it.)"""
         key = tuple(sorted(set(int(t) for t in stop_ids)))
-        return key in self._sets or any(u == 0 for u in self._set_users)
+        if not (key in self._sets or any(u == 0 for u in self._set_users)):
+            return False
+        if sampling is None:
+            return True
+        try:      # (a submission that finds no room in a table nobody uses never will: join() raises that too)
+            return self._mask_room(sampling_rules(sampling, B, self.llm.cfg.vocab_size)) or self.masks is None or not any(self.masks.users)
+        except ValueError:
+            return True
 
     def _stop_set_row(self, stop_ids: tuple) -> int:
         row = self._sets.get(stop_ids)
@@ -1321,6 +1562,8 @@ class DecodePool:
         key = self.graph_key(bucket)
         if self.n_general > 0:
             key += ("general", self.seen.data_ptr() if self.seen is not None else 0)
+            if self.n_ruled > 0:      # (the ruled form reads the mask and rule tables and never writes them: nothing joins the rollback)
+                key += ("ruled", self.masks.table.data_ptr(), self.rules.data_ptr())
         if self.n_logprob > 0:
             key += ("logprobs", self.lpb.lp.data_ptr())
         return key
@@ -1366,7 +1609,8 @@ class DecodePool:
                     x = ops.gemm(a, w["wdown"], residual=x)
                 logits = ops.gemm(ops.rmsnorm(x, llm.norm, c.rms_norm_eps), llm.lm_head)
             if general:      # plain slots ride as greedy rows without penalty; empty and finished slots return early, as in the greedy head
-                ops.decode_head_accept(logits, self.sparams, st, self.plan, self.ids, self.stop, self.done, seen=self.seen, per_sequence_sets=True)
+                rule = dict(masks=self.masks.table, rules=self.rules) if self.n_ruled > 0 else {}
+                ops.decode_head_accept(logits, self.sparams, st, self.plan, self.ids, self.stop, self.done, seen=self.seen, per_sequence_sets=True, **rule)
             else:
                 ops.decode_argmax_accept(logits, None, st, self.plan, self.ids, self.stop, self.done, per_sequence_sets=True)
             if record:       # after the head, whichever it was; rows whose `want` is off, finished and empty slots return at once
@@ -1449,6 +1693,8 @@ class DecodePool:
                 self.free.append(s)
                 self._set_users[self.slot_set[s]] -= 1
                 self.n_general -= self.kind[s] != "plain"
+                self.n_ruled -= bool(self.slot_masks[s])
+                self._release_masks(s)
         return out
 
     def drain(self, use_graph: bool = True, poll: int = 8, records: bool = False) -> List[tuple]:

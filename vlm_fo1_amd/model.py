@@ -530,10 +530,12 @@ class FO1Engine:
     def _first_tokens(self, per: list, requests: Sequence[dict]) -> torch.Tensor:
         """The first token of every sequence of the pass that just ran, from the prefill's logits: its greedy picks when every request is
         plain; else one launch of the device sampler with counter 0 — the general head (greedy rows, penalties against the prompts' seen
-        sets, marked into a scratch bitmap first) unless every row is a plain draw."""
-        from .llm import new_seen, sampling_table
+        sets, marked into a scratch bitmap first) unless every row is a plain draw.  A request's token rule (llm.token_rule) goes to the ruled
+        form of that head through a scratch mask table: counter 0, so its first-token and early bans apply."""
+        from .llm import TokenMasks, new_seen, sampling_rules, sampling_table
         n = len(requests)
         rows, kinds = sampling_table(per, n)
+        trules = sampling_rules(per, n, self.cfg.llm.vocab_size)
         if all(k == "plain" for k in kinds):
             return self._last_next_tokens[:n]
         with ops.workspace_scope(self._ws_owner):
@@ -546,7 +548,20 @@ class FO1Engine:
                     self._seen_scratch = new_seen(max(n, self.PREFILL_MAX), self.cfg.llm.vocab_size, self.dev)
                 seen = self._seen_scratch
                 self._seen_keep = ops.mark_prompts(seen, self.cfg.llm.vocab_size, list(range(n)), [r["ids"] for r in requests])
-            return ops.sample_rows(self._last_logits[:n], table, seen=seen, general=True)
+            rule = {}
+            if any(t is not None for t in trules):
+                tm = getattr(self, "_mask_scratch", None)
+                if tm is None or tm.rows < 3 * n:
+                    tm = self._mask_scratch = TokenMasks(3 * max(n, self.PREFILL_MAX), self.cfg.llm.vocab_size, self.dev)
+                held, table_r = [], []
+                for t in trules:
+                    row, rs = (None, []) if t is None else tm.rule_row(t)
+                    table_r.append(row)
+                    held += rs
+                rule = dict(masks=tm.table, rules=ops.token_rules(table_r, self.dev))
+                for r in held:      # (the launch below is ordered before the next pass's uploads: same stream)
+                    tm.release(r)
+            return ops.sample_rows(self._last_logits[:n], table, seen=seen, general=True, **rule)
 
     @staticmethod
     def _logprob_part(logprobs, a: int, b: int):

@@ -1031,6 +1031,24 @@ def _seen_operand(seen: Optional[torch.Tensor], B: int, V: int):
     return seen.data_ptr(), seen.shape[1]
 
 
+NO_RULE = (-1, -1, 0, -1)      # fo1_token_rule_t of a row without a rule
+
+
+def token_rules(rows: Sequence, device=None) -> torch.Tensor:
+    """The fo1_token_rule_t table (int32 [B, 4]) from rows of (always_row, early_row, early_until, first_row) — indices into a mask table, -1
+    = none (include/fo1.h) — or None for a row without a rule.  On `device` when given, else a host tensor."""
+    tab = torch.tensor([list(NO_RULE) if r is None else [int(x) for x in r] for r in rows], dtype=torch.int32).view(-1, 4)
+    return tab if device is None else tab.to(device)
+
+
+def _rule_operands(masks: Optional[torch.Tensor], rules: Optional[torch.Tensor], B: int, V: int):
+    assert masks is not None and rules is not None, "a ruled head takes the mask table and the rule table together"
+    assert masks.dtype == torch.int32 and masks.is_cuda and masks.dim() == 2 and masks.is_contiguous() and masks.shape[0] >= 1
+    assert masks.shape[1] % 4 == 0 and masks.shape[1] * 32 >= V
+    assert rules.dtype == torch.int32 and rules.is_cuda and rules.dim() == 2 and rules.shape[1] == 4 and rules.is_contiguous() and rules.shape[0] >= B
+    return masks.data_ptr(), masks.shape[0], masks.shape[1], rules.data_ptr()
+
+
 def _sample_operands(logits: torch.Tensor, params: torch.Tensor):
     _chk(logits, "logits")
     pl, ld, B, V = _rows(logits, "logits")
@@ -1043,11 +1061,12 @@ def _sample_operands(logits: torch.Tensor, params: torch.Tensor):
 
 def sample_rows(logits: torch.Tensor, params: torch.Tensor, counter: Optional[torch.Tensor] = None, counter_stride: int = 1,
                 u: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, seen: Optional[torch.Tensor] = None,
-                general: bool = False) -> torch.Tensor:
+                general: bool = False, masks: Optional[torch.Tensor] = None, rules: Optional[torch.Tensor] = None) -> torch.Tensor:
     """int32 [B]: one sampled id per row of logits [B, V] bf16 (fo1_sample_rows_bf16): temperature / top-k / top-p per row from `params`
     (sample_params), draw = Philox(counter, stream; seed) with counter = counter[b * counter_stride] (device int32; None = 0), or the explicit
     u [B] fp32.  seen (int32 [>= B, ld_words] bitmap) or general=True: the general head (fo1_sample_rows_seen_bf16), which also honours a
-    row's greedy flag and its repetition penalty; without a bitmap no row may have a penalty on."""
+    row's greedy flag and its repetition penalty; without a bitmap no row may have a penalty on.  masks (int32 [R, ld_words], a set bit = token
+    banned) and rules (token_rules, int32 [>= B, 4]): the ruled head (fo1_sample_rows_ruled_bf16), the general head behind each row's bans."""
     head, tail = _sample_operands(logits, params)
     B = head[3]
     if out is None:
@@ -1057,6 +1076,12 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, counter: Optional[to
         assert counter.dtype == torch.int32 and counter.is_cuda and counter.numel() > (B - 1) * counter_stride
     if u is not None:
         assert u.dtype == torch.float32 and u.is_cuda and u.is_contiguous() and u.numel() == B
+    if masks is not None or rules is not None:
+        ps, ldw = _seen_operand(seen, B, head[2])
+        rc = _L.load().fo1_sample_rows_ruled_bf16(*head, _ptr(counter), int(counter_stride), _ptr(u), out.data_ptr(), *tail[:2], ps, ldw,
+                                                  *_rule_operands(masks, rules, B, head[2]), tail[2])
+        _L.check(rc, "fo1_sample_rows_ruled_bf16")
+        return out
     if seen is not None or general:
         ps, ldw = _seen_operand(seen, B, head[2])
         rc = _L.load().fo1_sample_rows_seen_bf16(*head, _ptr(counter), int(counter_stride), _ptr(u), out.data_ptr(), *tail[:2], ps, ldw, tail[2])
@@ -1083,10 +1108,11 @@ def decode_sample_accept(logits: torch.Tensor, params: torch.Tensor, state: torc
 
 def decode_head_accept(logits: torch.Tensor, params: torch.Tensor, state: torch.Tensor, plan: torch.Tensor, ids_out: torch.Tensor,
                        stop_ids: Optional[torch.Tensor], done: torch.Tensor, seen: Optional[torch.Tensor] = None,
-                       per_sequence_sets: bool = False) -> None:
+                       per_sequence_sets: bool = False, masks: Optional[torch.Tensor] = None, rules: Optional[torch.Tensor] = None) -> None:
     """The general head of a decode step (fo1_decode_head_accept): decode_sample_accept with each row's greedy flag and repetition penalty
     honoured; the accepted token's bit is set in the row's `seen` bitmap (int32 [>= B, ld_words]; None only when no row has a penalty).
-    per_sequence_sets: as decode_argmax_accept."""
+    per_sequence_sets: as decode_argmax_accept.  masks / rules (as sample_rows takes them): the ruled head (fo1_decode_head_ruled_accept), which
+    reads both tables and writes neither."""
     B = state.shape[0]
     assert state.dtype == plan.dtype == ids_out.dtype == done.dtype == torch.int32 and ids_out.is_contiguous() and plan.is_contiguous()
     assert state.is_contiguous() and logits.shape[0] == B
@@ -1096,6 +1122,12 @@ def decode_head_accept(logits: torch.Tensor, params: torch.Tensor, state: torch.
         assert stop_ids is not None and stop_ids.dim() == 2 and stop_ids.shape[1] == 17 and stop_ids.is_contiguous() and stop_ids.dtype == torch.int32
         n_stop = -1
     ps, ldw = _seen_operand(seen, B, head[2])
+    if masks is not None or rules is not None:
+        rc = _L.load().fo1_decode_head_ruled_accept(*head, state.data_ptr(), plan.data_ptr(), ids_out.data_ptr(), ids_out.shape[1],
+                                                    stop_ids.data_ptr() if n_stop else None, n_stop, done.data_ptr(), *tail[:2], ps, ldw,
+                                                    *_rule_operands(masks, rules, B, head[2]), tail[2])
+        _L.check(rc, "fo1_decode_head_ruled_accept")
+        return
     rc = _L.load().fo1_decode_head_accept(*head, state.data_ptr(), plan.data_ptr(), ids_out.data_ptr(), ids_out.shape[1],
                                           stop_ids.data_ptr() if n_stop else None, n_stop, done.data_ptr(), *tail[:2], ps, ldw, tail[2])
     _L.check(rc, "fo1_decode_head_accept")

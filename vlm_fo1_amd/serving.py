@@ -141,8 +141,8 @@ class PoolService:
             h, kc, vt, seqs, deltas, first, max_new, stop_ids, ev, sampling, prompt_ids, logprobs, first_lp = waiting[0]
             if len(seqs) > len(pool.free):
                 return
-            if not pool.can_take(stop_ids):
-                return                                   # every row of the stop-set table is in use by live sequences (32 different sets)
+            if not pool.can_take(stop_ids, sampling, len(seqs)):
+                return                                   # every row of the stop-set table (32 sets) or of the token-mask table (64 masks) is in use by live sequences
             if pool.live and not pool.fits(seqs, max_new):
                 return                                   # longer slots than the pool has: its caches can only grow while it is empty
             waiting.pop(0)
