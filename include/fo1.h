@@ -562,6 +562,40 @@ int fo1_decode_head_ruled_accept(const void* logits, long long ld_logits, int n_
                                  int32_t* done, void* workspace, size_t workspace_bytes, uint32_t* seen, long long ld_words,
                                  const uint32_t* masks, int mask_rows, long long mask_ld_words, const fo1_token_rule_t* rules /* device [B] */,
                                  void* stream);
+/* Token guides: the banned set of a pick as a function of a per-row automaton state that the head advances itself.  A
+ * guide is a deterministic automaton over token classes: cls[t] in [0, C) the class of token t, next[s * C + c] the state after a token of class
+ * c in state s, negative = class c is not allowed in s.  The banned set of state s, { t : next[s * C + cls[t]] < 0 }, is a row of the mask table
+ * above, named by state_row[row_off + s] (-1 or any index outside the table: nothing banned).  A row b with a guide (cls_row inside
+ * [0, cls_rows)) picks in state s = gstate[b]: masks[state_row[row_off + s]] takes always_row's place in the row's rule (the callers fold the
+ * sequence's own always-bans into every state's bitmap), early_row and first_row apply as above, and after the pick of token t the head stores
+ * gstate[b] = next[next_off + s * C + cls[cls_row][t]] unless that entry is negative (the "nothing left gives id 0" fall-back took a banned
+ * token: the state stays).  A row with cls_row < 0 has no guide: its rule applies as it stands and gstate[b] is not touched; neither is it for
+ * a finished row of the accept form.  Every index read from a table is checked against n_next / n_state_row / cls_rows before it is used: a
+ * corrupt table gives "no mask" or "state stays", never a read out of range.  ld_cls >= n_vocab.
+ *   fo1_sample_rows_guided_bf16    fo1_sample_rows_ruled_bf16 + guides: row b picks in state gstate[b], the state after the pick is written back
+ *   fo1_decode_head_guided_accept  fo1_decode_head_ruled_accept + guides: the step reads the guide tables and writes gstate, nothing else of them
+ * guides == NULL: the call is the _ruled entry's.  guides != NULL needs masks, rules and all five tables.  Still one launch whatever the data,
+ * no host read, capturable, B <= 256; the log-probability record below does not see the guide. */
+typedef struct fo1_token_guide {      /* 16 bytes; cls_row < 0: the row has no guide */
+    int32_t cls_row;      /* row of cls[cls_rows][ld_cls] (uint16): the token classes */
+    int32_t n_classes;    /* C */
+    int32_t next_off;     /* next[next_off + s * C + c] (int32): state after class c in state s, < 0 = not allowed */
+    int32_t row_off;      /* state_row[row_off + s] (int32): mask-table row holding state s's banned set, -1 = nothing banned */
+} fo1_token_guide_t;
+int fo1_sample_rows_guided_bf16(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params,
+                                const int32_t* counter /* NULL = 0 */, int counter_stride, const float* u /* device [B]; NULL = Philox */,
+                                int32_t* out /* [B] */, void* workspace, size_t workspace_bytes, const uint32_t* seen, long long ld_words,
+                                const uint32_t* masks, int mask_rows, long long mask_ld_words, const fo1_token_rule_t* rules /* device [B] */,
+                                void* stream, const uint16_t* cls, int cls_rows, long long ld_cls, const int32_t* next, long long n_next,
+                                const int32_t* state_row, long long n_state_row, const fo1_token_guide_t* guides /* device [B] */,
+                                int32_t* gstate /* device [B], read and written */);
+int fo1_decode_head_guided_accept(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params,
+                                  int32_t* state, int32_t* plan, int32_t* ids_out, int ids_ld, const int32_t* stop_ids, int n_stop,
+                                  int32_t* done, void* workspace, size_t workspace_bytes, uint32_t* seen, long long ld_words,
+                                  const uint32_t* masks, int mask_rows, long long mask_ld_words, const fo1_token_rule_t* rules /* device [B] */,
+                                  void* stream, const uint16_t* cls, int cls_rows, long long ld_cls, const int32_t* next, long long n_next,
+                                  const int32_t* state_row, long long n_state_row, const fo1_token_guide_t* guides /* device [B] */,
+                                  int32_t* gstate /* device [B], read and written */);
 /* Log-probabilities of generated tokens.  For a bf16 logits row l[0..V) with F = { i : l_i finite }:
  *   m = max_F l,  S = sum_{i in F} exp(l_i - m) (fp32, a fixed order),  lp_i = (l_i - m) - log S as fp32 for i in F,  lp_i = -inf otherwise
  * (the sampler's rule: a non-finite entry has weight 0); a row with empty F gives -inf everywhere.  This is the log-softmax of the RAW logits:

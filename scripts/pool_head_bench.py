@@ -9,17 +9,22 @@
   greedy_general   the general head with every sequence a greedy row (no draw, no penalty, no rule): what `banned` and `min_new` add to,
   banned     the ruled general head fo1_decode_head_ruled_accept, every sequence greedy with one shared mask row of 1000 banned ids,
   sampled_banned   the same row on every sequence of `sampled`,
-  min_new    every sequence greedy with an early_row (16 ids) that is live on every timed step.
+  min_new    every sequence greedy with an early_row (16 ids) that is live on every timed step,
+  guided     the guided general head fo1_decode_head_guided_accept, every sequence greedy with one shared two-state guide whose states both
+             ban `banned`'s 1000 ids (one live mask row) and which changes state with every token: what the guide adds to `banned`,
+  sampled_guided   the same guide on every sequence of `sampled`: what it adds to `sampled_banned`,
+  one_banned / one_guided   one such ruled / guided greedy sequence among 127 plain ones.
 The heads are timed alternately, `--rounds` times each in one process, so the spread of a figure is the spread between its rounds; the pool is
 drained and re-joined for every timing.  Prints one JSON object.
 
     python scripts/pool_head_bench.py [--slots 128] [--steps 64] [--rounds 5] [--heads greedy sampled penalised ...] [--root DIR]
 
 With `greedy` among the heads the output also holds each other head's increment over it (difference of the medians of this process), and
-for a ruled head its increment over the same head without a rule (banned, min_new: greedy_general; sampled_banned: sampled).
+for a ruled head its increment over the same head without a rule (banned, min_new: greedy_general; sampled_banned: sampled), for a guided
+head its increment over the ruled head with the same mask row (guided: banned; sampled_guided: sampled_banned; one_guided: one_banned).
 
 --root DIR imports the package from another checkout (e.g. the parent commit, for the greedy figure of both on one box; only `greedy`
-exists there)."""
+exists there; a head the other checkout lacks cannot be named)."""
 import argparse
 import json
 import os
@@ -35,7 +40,8 @@ def main():
     ap.add_argument("--slots", type=int, default=128)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=5)
-    HEADS = ["greedy", "sampled", "penalised", "greedy_lp0", "greedy_lp8", "greedy_general", "banned", "sampled_banned", "min_new"]
+    HEADS = ["greedy", "sampled", "penalised", "greedy_lp0", "greedy_lp8", "greedy_general", "banned", "sampled_banned", "min_new", "guided",
+             "sampled_guided", "one_banned", "one_guided"]
     ap.add_argument("--heads", nargs="+", default=HEADS[:3], choices=HEADS)
     ap.add_argument("--root", default=None, help="import vlm_fo1_amd from this checkout instead of the script's own")
     args = ap.parse_args()
@@ -68,12 +74,24 @@ def main():
     sampling.update(greedy_general=dict(greedy=True), banned=dict(greedy=True, ban=ban), sampled_banned=dict(sampling["sampled"], ban=ban),
                     min_new=dict(greedy=True, ban_until=(budget + 1, list(range(3, 19)))))
     unruled = dict(banned="greedy_general", min_new="greedy_general", sampled_banned="sampled")
+    unguided = dict(guided="banned", sampled_guided="sampled_banned", one_guided="one_banned")
+    lone = dict(one_banned="banned", one_guided="guided")      # heads whose first sequence alone carries the other head's dict
+    if any(h in unguided for h in args.heads):
+        import numpy as np
+        from vlm_fo1_amd.guide import TokenGuide
+        cls = np.zeros(V, np.uint16)
+        cls[ban] = 1
+        guide = TokenGuide(cls, np.array([[1, -1], [0, -1]], np.int32), 0, V)      # both states ban `ban`: one shared mask row, as `banned` has
+        sampling.update(guided=dict(greedy=True, guide=guide), sampled_guided=dict(sampling["sampled"], guide=guide))
+    sampling.update(one_banned=None, one_guided=None)
 
     def one(head):
         left, base = P, 0
         while left > 0:
             n = min(32, left)
             kw = {} if sampling[head] is None else dict(sampling=dict(sampling[head], stream=base), prompt_ids=prompts[:n])
+            if head in lone and base == 0:
+                kw = dict(sampling=[dict(sampling[lone[head]], stream=0)] + [None] * (n - 1), prompt_ids=prompts[:n])
             if head in top_n:
                 from vlm_fo1_amd import ops
                 kw.update(logprobs=top_n[head], first_logprobs=ops.logprob_rows(logits0[:n], first[:n].to(torch.int32).contiguous(), top_n[head]))
@@ -110,6 +128,9 @@ def main():
     ruled = {h: round(out["heads"][h]["median"] - out["heads"][u]["median"], 4) for h, u in unruled.items() if h in times and u in times}
     if ruled:
         out["increment_over_unruled_ms"] = ruled
+    guided = {h: round(out["heads"][h]["median"] - out["heads"][u]["median"], 4) for h, u in unguided.items() if h in times and u in times}
+    if guided:
+        out["increment_over_ruled_ms"] = guided
     print(json.dumps(out))
 
 

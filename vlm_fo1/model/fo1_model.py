@@ -309,15 +309,53 @@ class FO1ForCausalLM:
     @classmethod
     def _decode_plan(cls, kwargs: dict, generation_config: Optional[dict] = None, eos_ids=()) -> Optional[dict]:
         """_sampling_plan, _penalty_plan and _rule_plan as the one dict the engine takes per request: None = plain greedy; a sampled request's
-        dict gains repetition_penalty and the token-rule keys; a greedy request with a penalty or a rule is dict(greedy=True, ...)."""
+        dict gains repetition_penalty and the token-rule keys; a greedy request with a penalty or a rule is dict(greedy=True, ...).  guide (a
+        vlm_fo1_amd.guide.TokenGuide, or None = off; anything else is a ValueError) rides in the dict as the engine's `guide` key."""
         sampling, pen, rule = cls._sampling_plan(kwargs, generation_config), cls._penalty_plan(kwargs), cls._rule_plan(kwargs, eos_ids)
-        if pen is None and rule is None:
+        guide = cls._guide_plan(kwargs)
+        if pen is None and rule is None and guide is None:
             return sampling
         plan = dict(greedy=True) if sampling is None else dict(sampling)
         if pen is not None:
             plan["repetition_penalty"] = pen
         plan.update(rule or {})
+        if guide is not None:
+            plan["guide"] = guide
         return plan
+
+    @staticmethod
+    def _guide_plan(kwargs: dict):
+        guide = kwargs.get("guide")
+        if guide is None:
+            return None
+        from vlm_fo1_amd.guide import TokenGuide
+        if not isinstance(guide, TokenGuide):
+            raise ValueError(f"guide: a vlm_fo1_amd.guide.TokenGuide, as region_guide() builds one (got {type(guide).__name__})")
+        return guide
+
+    def region_guide(self, tokenizer, n_regions: int):
+        """The guide of the FO1 answer language `<ground>label</ground><objects><region3>...</objects>` for a request with n_regions boxes
+        (vlm_fo1_amd.guide.region_answer): the five structural ids and the <regionK> ids from tokenizer.convert_tokens_to_ids — every
+        <regionK> the tokenizer knows, K = 0, 1, ... —, the stop ids from config.eos_ids().  ValueError: a token that is not a single id of
+        the vocabulary, or fewer <regionK> tokens than n_regions."""
+        from vlm_fo1_amd.guide import region_answer
+        V = self.engine.cfg.llm.vocab_size
+        unk = getattr(tokenizer, "unk_token_id", None)
+
+        def one(tok):
+            t = tokenizer.convert_tokens_to_ids(tok)
+            if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < V or (unk is not None and t == unk):
+                return None
+            return t
+        struct = [one(t) for t in ("<ground>", "</ground>", "<objects>", "</objects>")]
+        if any(t is None for t in struct):
+            raise ValueError("region_guide: <ground>, </ground>, <objects> and </objects> must each be a single id of the vocabulary")
+        regions = []
+        while one(f"<region{len(regions)}>") is not None:
+            regions.append(one(f"<region{len(regions)}>"))
+        if int(n_regions) > len(regions):
+            raise ValueError(f"region_guide: the tokenizer has {len(regions)} <regionK> tokens, the request {int(n_regions)} boxes")
+        return region_answer(V, *struct, regions, int(n_regions), self.config.eos_ids())
 
     @staticmethod
     def _logprob_plan(kwargs: dict) -> Optional[int]:
@@ -357,7 +395,8 @@ class FO1ForCausalLM:
         def values(kw):      # what a packed batch without the pool must share
             sp = self._sampling_plan(dict(kw, seed=0), gen)
             rule = self._rule_plan(kw, eos)
-            return (None if sp is None else (sp["temperature"], sp["top_p"], sp["top_k"])), self._penalty_plan(kw), rule and tuple(sorted(rule.items()))
+            return ((None if sp is None else (sp["temperature"], sp["top_p"], sp["top_k"])), self._penalty_plan(kw), rule and tuple(sorted(rule.items())),
+                    self._guide_plan(kw))
         v0 = values(k0)
         mixed = False
         for kw in requests_kwargs[1:]:       # one budget and one stop rule per packed batch: refuse a mixed batch rather than apply the first's
@@ -371,7 +410,7 @@ class FO1ForCausalLM:
                     continue
                 if v != v0:      # without the pool one BatchDecoder group decodes the batch with one sampling
                     raise ValueError("generate_many: every request of a batch must share do_sample, temperature, top_p and top_k "
-                                     "(and repetition_penalty and the token-rule keywords) unless the decode pool is enabled")
+                                     "(and repetition_penalty, the token-rule keywords and the guide) unless the decode pool is enabled")
                 raise ValueError("generate_many: every request of a sampled batch must share seed (request i draws on stream i of the one seed)")
         sampling = [self._decode_plan(kw, gen, eos) for kw in requests_kwargs] if mixed else self._decode_plan(k0, gen, eos)
         reqs = [self._request(kw.get("inputs"), kw.get("images"), kw.get("images_aux"), kw.get("image_grid_thws"), kw.get("bbox_list"))
@@ -491,7 +530,8 @@ class FO1ForCausalLM:
     def generate(self, inputs=None, images=None, images_aux=None, image_grid_thws=None, bbox_list=None, do_sample=False,
                  temperature=0.0, max_new_tokens=512, streamer=None, top_p=1.0, use_cache=True, stopping_criteria=None,
                  pad_token_id=None, top_k=None, seed=None, repetition_penalty=None, _stream=0, output_logprobs=False, top_logprobs=0,
-                 suppress_tokens=None, begin_suppress_tokens=None, bad_words_ids=None, min_new_tokens=None, allowed_token_ids=None, **unused):
+                 suppress_tokens=None, begin_suppress_tokens=None, bad_words_ids=None, min_new_tokens=None, allowed_token_ids=None, guide=None,
+                 **unused):
         """Decoding of one prompt: greedy, or with do_sample=True temperature / top-k / top-p sampling on the device (_sampling_plan).
         Returns [1, L_in + new] like HF generate (the reference slices `output_ids[0, inputs.shape[1]:]`, inference.py:47-48).  Without a
         streamer and with id-set stop criteria the whole loop runs on the device (BatchDecoder, no per-token host read); otherwise tokens
@@ -508,7 +548,10 @@ class FO1ForCausalLM:
         suppress_tokens / bad_words_ids (single-token entries; a longer one is a NotImplementedError) / allowed_token_ids /
         begin_suppress_tokens / min_new_tokens: HF's processors of those names in front of the pick, on the device (_rule_plan; DESIGN.md
         section 14).  All default to off, whatever generation_config.json holds.  A constrained generation decodes as a penalised one does:
-        in the BatchDecoder, stepped one by one with a streamer or unexpressible stop criteria; max_new_tokens beyond IDS_CAP is a ValueError."""
+        in the BatchDecoder, stepped one by one with a streamer or unexpressible stop criteria; max_new_tokens beyond IDS_CAP is a ValueError.
+        guide: None (off) or a vlm_fo1_amd.guide.TokenGuide — region_guide(tokenizer, n_regions) for the FO1 answer language, guide.ban_sequences
+        for multi-token banned sequences: the banned set of every pick follows the guide's automaton state, which the head advances on the
+        device; decoded as a constrained generation is.  max_new_tokens may still cut an answer short inside a structure."""
         lpn = self._logprob_plan(dict(output_logprobs=output_logprobs, top_logprobs=top_logprobs))
         if lpn is not None and not self._fits_device_loop(max_new_tokens):
             from vlm_fo1_amd.llm import BatchDecoder
@@ -516,7 +559,8 @@ class FO1ForCausalLM:
         sampling = self._decode_plan(dict(do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k, seed=seed,
                                           repetition_penalty=repetition_penalty, suppress_tokens=suppress_tokens,
                                           begin_suppress_tokens=begin_suppress_tokens, bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens,
-                                          allowed_token_ids=allowed_token_ids), getattr(self.config, "_gen", None), self.config.eos_ids())
+                                          allowed_token_ids=allowed_token_ids, guide=guide), getattr(self.config, "_gen", None),
+                                     self.config.eos_ids())
         req = self._request(inputs, images, images_aux, image_grid_thws, bbox_list)
         dev = self.device
         stop = self._device_stop_ids(stopping_criteria) if streamer is None else None

@@ -35,6 +35,13 @@
 // a lane's 8 logits it also loads the matching byte of each active mask row, ORs them and replaces the banned entries by a NaN (no key) BEFORE
 // the penalty and the keying: a banned token is a non-finite entry to every pass — weight 0, never kept, never the greedy pick.  A row with
 // nothing left gives id 0, as a row without a finite entry does.  Behind a template parameter of its own, as the penalty is.
+//
+// The guided head (GUIDE instantiations: fo1_sample_rows_guided_bf16, fo1_decode_head_guided_accept) adds a per-row automaton state gstate[b]
+// and one fo1_token_guide_t per row.  For a guided row (cls_row inside the class table) the mask row state_row[row_off + gstate[b]] takes
+// `always_row`'s place among the three mask pointers, resolved once per workgroup as the rule is; every pass is the ruled head's.  After the
+// pick thread 0 loads cls[tok] and next[next_off + s * C + cls], issues the accept, and stores the new state (a negative entry keeps the old
+// one).  Every index read from a table is checked against the table's size first: a corrupt table gives a row without a mask or a state that
+// stays, never a read out of range.  A finished row and a row without a guide leave gstate alone.
 #include "decode_common.h"
 
 namespace fo1 {
@@ -69,6 +76,13 @@ __device__ __forceinline__ uint32_t sp_penalise(uint32_t b, float p) {
 struct SpRule {
     const uint8_t* m[3];
     bool live;
+};
+
+// what thread 0 of a guided row needs after the pick: the class row, the state's row of `next`, its entries inside the table (0: no advance)
+struct SpGuide {
+    const uint16_t* cls;
+    const int* next;
+    int cmax;
 };
 
 // sp_load8; RULE: banned tokens come back as a NaN (no key); PEN: seen tokens come back as their penalised logit, so every pass keys the same
@@ -155,6 +169,8 @@ struct SampleArgs {
     int* state; int* plan; int* ids_out; int ids_ld; const int* stop_ids; int n_stop; int* done;     // accept form
     uint32_t* seen; long long ld_words;         // general head: the seen bitmap [rows][ld_words] (NULL: no row has a penalty)
     const uint32_t* masks; int mask_rows; long long mask_ld_words; const fo1_token_rule_t* rules;      // ruled head: the mask table and the rows' rules
+    const uint16_t* cls; int cls_rows; long long ld_cls; const int* next; long long n_next;            // guided head: token classes, transitions,
+    const int* state_row; long long n_state_row; const fo1_token_guide_t* guides; int* gstate;         // state -> mask row, the rows' guides and states
 };
 
 // Key scan of the half whose counters sit in `hist` (keys key0 .. key0 + 32767), top key down.  carry_c / carry_m: tokens and mass of the
@@ -199,7 +215,7 @@ __device__ __forceinline__ void sp_key_scan(const uint32_t* hist, int key0, int 
     __syncthreads();
 }
 
-template <bool ACCEPT, bool PEN, bool RULE = false>
+template <bool ACCEPT, bool PEN, bool RULE = false, bool GUIDE = false>
 __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
     extern __shared__ __align__(16) unsigned char sp_smem[];
     uint32_t* hist = reinterpret_cast<uint32_t*>(sp_smem);
@@ -208,6 +224,7 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
     __shared__ float s_wm[SP_NW];
     __shared__ int s_kcut_k, s_range, s_kcut_p, s_tok;
     __shared__ float s_z1;
+    [[maybe_unused]] __shared__ SpGuide s_gd;      // GUIDE only (thread 0 writes and reads it)
 
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int V = a.V;
@@ -235,10 +252,30 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
         }
     }
     SpRule rule{{nullptr, nullptr, nullptr}, false};
+    if constexpr (GUIDE) {
+        if (tid == 0) s_gd.cmax = 0;
+    }
     if constexpr (RULE) {      // the mask rows live at this pick (uniform per row); an index outside the table: none
         const fo1_token_rule_t R = a.rules[b];
         const int c = ACCEPT ? st[4] : (a.counter ? a.counter[(long long)b * a.counter_stride] : 0);
-        const int rows3[3] = {R.always_row, c < R.early_until ? R.early_row : -1, c == 0 ? R.first_row : -1};
+        int row0 = R.always_row;
+        if constexpr (GUIDE) {      // a guided row: the mask row of its state instead (the host folded the sequence's own bans into it)
+            const fo1_token_guide_t G = a.guides[b];
+            if (G.cls_row >= 0 && G.cls_row < a.cls_rows && G.n_classes > 0 && G.next_off >= 0 && G.row_off >= 0) {
+                const int gs = a.gstate[b];
+                const long long ri = (long long)G.row_off + gs;
+                row0 = gs >= 0 && ri < a.n_state_row ? a.state_row[ri] : -1;
+                // what thread 0 needs after the pick waits in LDS, not in registers across the passes: the token's class row, the state's
+                // row of `next` and how many of its entries lie inside the table (0: the state stays)
+                const long long nb = (long long)G.next_off + (long long)gs * G.n_classes;
+                if (tid == 0 && gs >= 0 && nb < a.n_next) {
+                    s_gd.cls = a.cls + (long long)G.cls_row * a.ld_cls;
+                    s_gd.next = a.next + nb;
+                    s_gd.cmax = (int)min((long long)G.n_classes, a.n_next - nb);
+                }
+            }
+        }
+        const int rows3[3] = {row0, c < R.early_until ? R.early_row : -1, c == 0 ? R.first_row : -1};
         int any = -1;
 #pragma unroll
         for (int r = 0; r < 3; ++r)
@@ -441,6 +478,14 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
         tok = s_tok;
     }
     if (tid == 0) {
+        [[maybe_unused]] int ns = -1;
+        if constexpr (GUIDE) {      // the state after `tok`: both loads in front of the accept's stores (tok < V <= ld_cls: inside the class row)
+            const int cmax = s_gd.cmax;
+            if (cmax > 0) {
+                const int c = s_gd.cls[tok];
+                if (c < cmax) ns = s_gd.next[c];
+            }
+        }
         if (ACCEPT) {
             // the step that produced this token consumed row `pos`: the NEXT fed token goes one row further (as the greedy head does)
             st[0] += 1; st[1] += 1;
@@ -451,17 +496,21 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
         } else {
             a.out[b] = tok;
         }
+        if constexpr (GUIDE) {
+            if (ns >= 0) a.gstate[b] = ns;      // (a negative entry: the "nothing left gives id 0" fall-back took a banned token, the state stays)
+        }
     }
 }
 
 constexpr size_t SP_WORKSPACE = 256;      // the one-workgroup-per-row kernel keeps everything in LDS; the argument stays for a split form
 
-template <bool ACCEPT, bool PEN, bool RULE = false>
+template <bool ACCEPT, bool PEN, bool RULE = false, bool GUIDE = false>
 static int launch_sample(const SampleArgs& a, int B, hipStream_t st) {
-    FO1_DYNAMIC_LDS_ONCE(SP_SMEM, sample_rows_kernel<ACCEPT, PEN, RULE>);
-    FO1_LAUNCH(RULE ? (ACCEPT ? "head_ruled_accept" : "sample_rows_ruled")
-                    : PEN ? (ACCEPT ? "head_accept" : "sample_rows_seen") : (ACCEPT ? "sample_accept" : "sample_rows"),
-               (double)B * a.V * 2.0, (sample_rows_kernel<ACCEPT, PEN, RULE>), dim3(B), dim3(SP_NT), SP_SMEM, st, a);
+    FO1_DYNAMIC_LDS_ONCE(SP_SMEM, sample_rows_kernel<ACCEPT, PEN, RULE, GUIDE>);
+    FO1_LAUNCH(GUIDE ? (ACCEPT ? "head_guided_accept" : "sample_rows_guided")
+               : RULE ? (ACCEPT ? "head_ruled_accept" : "sample_rows_ruled")
+                      : PEN ? (ACCEPT ? "head_accept" : "sample_rows_seen") : (ACCEPT ? "sample_accept" : "sample_rows"),
+               (double)B * a.V * 2.0, (sample_rows_kernel<ACCEPT, PEN, RULE, GUIDE>), dim3(B), dim3(SP_NT), SP_SMEM, st, a);
     return FO1_OK;
 }
 
@@ -487,6 +536,16 @@ static int check_masks(const char* who, const void* masks, int mask_rows, long l
                   "%s: mask_ld_words=%lld (a multiple of 4, >= ceil(n_vocab / 32) = %d)", who, mask_ld_words, (V + 31) / 32);
     FO1_CHECK_ARG(!masks || mask_rows > 0, "%s: mask_rows=%d with a mask table (>= 1)", who, mask_rows);
     FO1_CHECK_ARG(!masks || ((uintptr_t)masks & 3) == 0, "%s: masks must be 4-byte aligned", who);
+    return FO1_OK;
+}
+
+static int check_guides(const char* who, const void* masks, const void* rules, const void* cls, int cls_rows, long long ld_cls, const void* next,
+                        long long n_next, const void* state_row, long long n_state_row, const void* gstate, int V) {
+    FO1_CHECK_ARG(masks && rules, "%s: guides need the mask table and the rule table", who);
+    FO1_CHECK_ARG(cls && next && state_row && gstate, "%s: guides with a NULL class, transition, state-row or state table", who);
+    FO1_CHECK_ARG(cls_rows > 0 && ld_cls >= V, "%s: cls_rows=%d ld_cls=%lld (>= 1 rows of >= n_vocab = %d classes)", who, cls_rows, ld_cls, V);
+    FO1_CHECK_ARG(n_next > 0 && n_state_row > 0, "%s: n_next=%lld n_state_row=%lld (>= 1 each)", who, n_next, n_state_row);
+    FO1_CHECK_ARG(((uintptr_t)cls & 1) == 0 && (((uintptr_t)next | (uintptr_t)state_row | (uintptr_t)gstate) & 3) == 0, "%s: misaligned guide table", who);
     return FO1_OK;
 }
 
@@ -601,6 +660,58 @@ int fo1_decode_head_ruled_accept(const void* logits, long long ld_logits, int n_
     if (!masks || !rules) return launch_sample<true, true>(a, B, (hipStream_t)stream);
     a.masks = masks; a.mask_rows = mask_rows; a.mask_ld_words = mask_ld_words; a.rules = rules;
     return launch_sample<true, true, true>(a, B, (hipStream_t)stream);
+}
+
+// fo1_sample_rows_ruled_bf16 with the rows' token guides honoured (the head of this file; include/fo1.h): row b picks in state gstate[b] and the
+// state after the pick is written back.  guides == NULL: fo1_sample_rows_ruled_bf16.
+int fo1_sample_rows_guided_bf16(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params, const int32_t* counter,
+                                int counter_stride, const float* u, int32_t* out, void* workspace, size_t workspace_bytes, const uint32_t* seen,
+                                long long ld_words, const uint32_t* masks, int mask_rows, long long mask_ld_words, const fo1_token_rule_t* rules,
+                                void* stream, const uint16_t* cls, int cls_rows, long long ld_cls, const int32_t* next, long long n_next,
+                                const int32_t* state_row, long long n_state_row, const fo1_token_guide_t* guides, int32_t* gstate) {
+    using namespace fo1;
+    if (!guides)
+        return fo1_sample_rows_ruled_bf16(logits, ld_logits, n_vocab, B, params, counter, counter_stride, u, out, workspace, workspace_bytes, seen, ld_words,
+                                          masks, mask_rows, mask_ld_words, rules, stream);
+    if (int rc = check_sample("sample_rows_guided", logits, ld_logits, n_vocab, B, params, workspace, workspace_bytes)) return rc;
+    if (int rc = check_seen("sample_rows_guided", seen, ld_words, n_vocab)) return rc;
+    if (int rc = check_masks("sample_rows_guided", masks, mask_rows, mask_ld_words, n_vocab)) return rc;
+    if (int rc = check_guides("sample_rows_guided", masks, rules, cls, cls_rows, ld_cls, next, n_next, state_row, n_state_row, gstate, n_vocab)) return rc;
+    FO1_CHECK_ARG(out != nullptr, "sample_rows_guided: NULL out");
+    SampleArgs a{};
+    a.logits = (const uint16_t*)logits; a.ld = ld_logits; a.V = n_vocab; a.params = params; a.counter = (const int*)counter;
+    a.counter_stride = counter_stride; a.u = u; a.out = (int*)out; a.seen = const_cast<uint32_t*>(seen); a.ld_words = ld_words;
+    a.masks = masks; a.mask_rows = mask_rows; a.mask_ld_words = mask_ld_words; a.rules = rules;
+    a.cls = cls; a.cls_rows = cls_rows; a.ld_cls = ld_cls; a.next = (const int*)next; a.n_next = n_next; a.state_row = (const int*)state_row;
+    a.n_state_row = n_state_row; a.guides = guides; a.gstate = (int*)gstate;
+    return launch_sample<false, true, true, true>(a, B, (hipStream_t)stream);
+}
+
+// fo1_decode_head_ruled_accept with the rows' token guides honoured: the step reads the guide tables and writes gstate, nothing else of them.
+// guides == NULL: fo1_decode_head_ruled_accept.
+int fo1_decode_head_guided_accept(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params, int32_t* state,
+                                  int32_t* plan, int32_t* ids_out, int ids_ld, const int32_t* stop_ids, int n_stop, int32_t* done, void* workspace,
+                                  size_t workspace_bytes, uint32_t* seen, long long ld_words, const uint32_t* masks, int mask_rows,
+                                  long long mask_ld_words, const fo1_token_rule_t* rules, void* stream, const uint16_t* cls, int cls_rows,
+                                  long long ld_cls, const int32_t* next, long long n_next, const int32_t* state_row, long long n_state_row,
+                                  const fo1_token_guide_t* guides, int32_t* gstate) {
+    using namespace fo1;
+    if (!guides)
+        return fo1_decode_head_ruled_accept(logits, ld_logits, n_vocab, B, params, state, plan, ids_out, ids_ld, stop_ids, n_stop, done, workspace,
+                                            workspace_bytes, seen, ld_words, masks, mask_rows, mask_ld_words, rules, stream);
+    if (int rc = check_sample("decode_head_guided_accept", logits, ld_logits, n_vocab, B, params, workspace, workspace_bytes)) return rc;
+    if (int rc = check_seen("decode_head_guided_accept", seen, ld_words, n_vocab)) return rc;
+    if (int rc = check_masks("decode_head_guided_accept", masks, mask_rows, mask_ld_words, n_vocab)) return rc;
+    if (int rc = check_guides("decode_head_guided_accept", masks, rules, cls, cls_rows, ld_cls, next, n_next, state_row, n_state_row, gstate, n_vocab)) return rc;
+    FO1_CHECK_ARG(state && plan && ids_out && done && ids_ld > 0 && n_stop >= -1 && (n_stop == 0 || stop_ids), "decode_head_guided_accept: bad arguments");
+    SampleArgs a{};
+    a.logits = (const uint16_t*)logits; a.ld = ld_logits; a.V = n_vocab; a.params = params;
+    a.state = (int*)state; a.plan = (int*)plan; a.ids_out = (int*)ids_out; a.ids_ld = ids_ld; a.stop_ids = (const int*)stop_ids; a.n_stop = n_stop;
+    a.done = (int*)done; a.seen = seen; a.ld_words = ld_words;
+    a.masks = masks; a.mask_rows = mask_rows; a.mask_ld_words = mask_ld_words; a.rules = rules;
+    a.cls = cls; a.cls_rows = cls_rows; a.ld_cls = ld_cls; a.next = (const int*)next; a.n_next = n_next; a.state_row = (const int*)state_row;
+    a.n_state_row = n_state_row; a.guides = guides; a.gstate = (int*)gstate;
+    return launch_sample<true, true, true, true>(a, B, (hipStream_t)stream);
 }
 
 // Sets bit ids[i] of row rows[i] of the seen bitmap for i < n (device int32 each; duplicates are fine).  Ids outside [0, n_vocab) and negative

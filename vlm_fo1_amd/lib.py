@@ -282,6 +282,13 @@ SIGNATURES = {
                                            c_longlong, c_void_p, c_int, c_longlong, c_void_p, c_void_p]),
     "fo1_decode_head_ruled_accept": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                              c_void_p, c_void_p, c_size_t, c_void_p, c_longlong, c_void_p, c_int, c_longlong, c_void_p, c_void_p]),
+    # the _ruled entries' lists + (cls, cls_rows, ld_cls, next, n_next, state_row, n_state_row, guides, gstate)
+    "fo1_sample_rows_guided_bf16": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
+                                            c_longlong, c_void_p, c_int, c_longlong, c_void_p, c_void_p,
+                                            c_void_p, c_int, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p]),
+    "fo1_decode_head_guided_accept": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                              c_void_p, c_void_p, c_size_t, c_void_p, c_longlong, c_void_p, c_int, c_longlong, c_void_p, c_void_p,
+                                              c_void_p, c_int, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p]),
     "fo1_logprob_rows_bf16": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
     "fo1_decode_logprob_record": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p]),

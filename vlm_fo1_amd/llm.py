@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .guide import TokenGuide
 
 IMAGE_TOKEN_INDEX = -200
 DEFAULT_REGION_INDEX = -300
@@ -696,10 +697,10 @@ def sampling_table(sampling, B: int):
     sampling: None; one dict for the submission (temperature, top_p, top_k, seed — optional when greedy=True — plus greedy,
     repetition_penalty; sequence b draws on stream streams[b], or stream + b, default b); or a list with one such dict (its own `stream`,
     default b) or None per sequence.  A dict with a token-rule key (RULE_KEYS: ban, ban_first, allow, ban_until — token_rule) is "general"
-    too: dict(greedy=True, ban=[...]) is a constrained greedy sequence."""
+    too: dict(greedy=True, ban=[...]) is a constrained greedy sequence; so is a dict with a guide (guide=TokenGuide: sampling_guides)."""
     per = _per_sequence(sampling, B)
     rows = [ops.sampling_row(sp, b) for b, sp in enumerate(per)]
-    kinds = ["plain" if sp is None else ("general" if (r[5] or ops.penalty_on(r[6]) or has_rule(sp)) else "sampled") for sp, r in zip(per, rows)]
+    kinds = ["plain" if sp is None else ("general" if (r[5] or ops.penalty_on(r[6]) or has_rule(sp) or has_guide(sp)) else "sampled") for sp, r in zip(per, rows)]
     return rows, kinds
 
 
@@ -724,6 +725,10 @@ RULE_KEYS = ("ban", "ban_first", "allow", "ban_until")      # the token-rule key
 
 def has_rule(sp: Optional[dict]) -> bool:
     return sp is not None and any(sp.get(k) is not None for k in RULE_KEYS)
+
+
+def has_guide(sp: Optional[dict]) -> bool:
+    return sp is not None and sp.get("guide") is not None
 
 
 class TokenRule(NamedTuple):
@@ -861,6 +866,270 @@ class TokenMasks:
         return (a, e, rule.until, f), [r for r in (a, e, f) if r >= 0]
 
 
+class GuidePlan(NamedTuple):
+    """What a guided sequence asks of the tables: its guide, the always-bans of its token rule (folded into every state's bitmap: the head
+    reads the state's mask row in always_row's place), the resulting bitmap of every state (None = nothing banned), the state its first token
+    is picked in, and — when the caller picked the first token on the device — the device int32 word holding the state after it."""
+    guide: TokenGuide
+    always: Optional[bytes]
+    bitmaps: tuple
+    s0: int
+    after_first: Optional[torch.Tensor]
+
+    @property
+    def key(self):
+        return (self.guide, self.always)
+
+
+def sampling_guides(sampling, B: int, V: int, trules: Sequence[Optional[TokenRule]], prompt_ids=None) -> List[Optional[GuidePlan]]:
+    """sampling_table's argument -> the GuidePlan (or None) of every sequence; trules: sampling_rules' result for the same argument.
+    A sequence's `guide` key holds a TokenGuide over V tokens; a guide built by ban_sequences starts in guide.run(prompt ids), so it needs
+    prompt_ids.  The optional key `guide_state` holds a device int32 tensor of one element, the state after the first token, when the caller
+    picked that token with the guided head (FO1Engine._first_tokens).  ValueError: not a TokenGuide, another vocabulary size, or a state the
+    sequence can reach in which the guide and its token rule together leave nothing to pick (a guide whose only exit is a stop id that
+    ban_until still bans is one such case)."""
+    out = []
+    for b, sp in enumerate(_per_sequence(sampling, B)):
+        if not has_guide(sp):
+            out.append(None)
+            continue
+        g = sp["guide"]
+        if not isinstance(g, TokenGuide):
+            raise ValueError(f"guide: a vlm_fo1_amd.guide.TokenGuide (got {type(g).__name__})")
+        if g.V != int(V):
+            raise ValueError(f"guide: built for {g.V} tokens, the model has {int(V)}")
+        if g.from_prompt:
+            if prompt_ids is None or len(prompt_ids) != B:
+                raise ValueError("guide: a guide that starts in the prompt's state needs prompt_ids, one list per sequence")
+            s0 = g.run(prompt_ids[b])
+        else:
+            s0 = g.start
+        t = trules[b]
+        always = t.always if t is not None else None
+        if t is None:
+            g.check_pickable(s0)
+        else:
+            g.check_pickable(s0, t.always, t.early, t.until, t.first)
+        out.append(GuidePlan(g, always, tuple(g.state_bitmaps(always)), s0, sp.get("guide_state")))
+    return out
+
+
+def unguided_rules(trules: Sequence[Optional[TokenRule]], gplans: Sequence[Optional[GuidePlan]]) -> List[Optional[TokenRule]]:
+    """The rules whose mask rows the sequences take themselves: a guided sequence's always-bans live in its guide's state bitmaps."""
+    out = []
+    for t, g in zip(trules, gplans):
+        if t is not None and g is not None:
+            t = t._replace(always=None)
+            if not t.bitmaps():
+                t = None
+        out.append(t)
+    return out
+
+
+class _Spans:
+    """First-fit spans of a flat table, keyed by content, with user counts: equal contents share a span, a span with users is never rewritten
+    or moved, one without users stays findable until its place is taken."""
+
+    def __init__(self, cap: int):
+        self.cap = cap
+        self.ent: Dict[object, list] = {}      # key -> [offset, length, users]
+
+    def _place(self, n: int, busy: list) -> int:
+        at = 0
+        for o, l in sorted(busy):
+            if o - at >= n:
+                return at
+            at = max(at, o + l)
+        return at if self.cap - at >= n else -1
+
+    def room(self, needs: Sequence[tuple]) -> bool:
+        """Is there a span for every (key, length) of `needs` (its own, or a place no live span covers)?"""
+        busy = [(o, l) for o, l, u in self.ent.values() if u > 0]
+        for key, n in dict(needs).items():
+            if key in self.ent:
+                if self.ent[key][2] == 0:
+                    busy.append(tuple(self.ent[key][:2]))
+                continue
+            at = self._place(n, busy)
+            if at < 0:
+                return False
+            busy.append((at, n))
+        return True
+
+    def acquire(self, key, n: int):
+        """-> (offset, new): the span holding `key`, one user more; new = the caller has to write its n entries."""
+        e = self.ent.get(key)
+        if e is not None:
+            e[2] += 1
+            return e[0], False
+        at = self._place(n, [(o, l) for o, l, u in self.ent.values() if u > 0])
+        if at < 0:
+            raise RuntimeError("no room in a token-guide table; wait for sequences to finish")
+        for k in [k for k, (o, l, u) in self.ent.items() if o < at + n and at < o + l]:      # (spans without users whose place is taken)
+            del self.ent[k]
+        self.ent[key] = [at, n, 1]
+        return at, True
+
+    def release(self, key, drop: bool = False) -> None:
+        e = self.ent[key]
+        assert e[2] > 0
+        e[2] -= 1
+        if drop and e[2] == 0:
+            del self.ent[key]
+
+
+class GuideTables:
+    """Device side of the token guides of a decoder's rows (include/fo1.h, fo1_token_guide_t): the class table cls int16 [CLS_ROWS, V] (the
+    uint16 classes), the transition table next int32 [N_NEXT] and the state-row table state_row int32 [N_STATE_ROW], which names the mask row
+    (of the decoder's TokenMasks) holding each state's banned set.  Content-keyed sharing with user counts: equal class maps share a row, equal
+    transition tables a span, equal (guide, always-bans) pairs everything — region_answer guides for different n_regions share their class
+    row — and states with equal banned sets share mask rows within and across guides, since the bitmaps are acquired through TokenMasks.
+    A row or span with users is never rewritten.  The step reads all three and writes none.  Allocated by the first guided sequence."""
+    CLS_ROWS = 64
+    N_NEXT = 1 << 14
+    N_STATE_ROW = 1 << 10
+
+    def __init__(self, n_vocab: int, dev, masks: Optional[TokenMasks]):
+        """dev = None: the bookkeeping alone, without device tables — what room() and new_bitmaps() answer from before anything is allocated."""
+        self.masks = masks
+        self.cls = self.next = self.state_row = None
+        if dev is not None:
+            with torch.inference_mode(False):
+                self.cls = torch.zeros(self.CLS_ROWS, int(n_vocab), dtype=torch.int16, device=dev)
+                self.next = torch.full((self.N_NEXT,), -1, dtype=torch.int32, device=dev)
+                self.state_row = torch.full((self.N_STATE_ROW,), -1, dtype=torch.int32, device=dev)
+        self._cls, self._next, self._sr = _Spans(self.CLS_ROWS), _Spans(self.N_NEXT), _Spans(self.N_STATE_ROW)
+        self.live: Dict[tuple, dict] = {}      # GuidePlan.key -> dict(users, row = the fo1_token_guide_t fields, mask_rows)
+        self._keep: list = []
+
+    @staticmethod
+    def _keys(plan: GuidePlan):
+        g = plan.guide
+        return g.cls.tobytes(), (g.C, g.next.tobytes()), plan.key
+
+    def new_bitmaps(self, plans: Sequence[Optional[GuidePlan]]) -> list:
+        """The state bitmaps the plans would acquire mask rows for (those of pairs that are not live yet)."""
+        return [m for p in {q.key: q for q in plans if q is not None}.values() if p.key not in self.live for m in p.bitmaps if m is not None]
+
+    def room(self, plans: Sequence[Optional[GuidePlan]]) -> bool:
+        """Is there a class row, a transition span and a state-row span for every plan?  (The mask rows: TokenMasks.room over new_bitmaps.)"""
+        new = [p for p in {q.key: q for q in plans if q is not None}.values() if p.key not in self.live]
+        ks = [self._keys(p) for p in new]
+        return (self._cls.room([(k[0], 1) for k in ks]) and self._next.room([(k[1], p.guide.S * p.guide.C) for k, p in zip(ks, new)])
+                and self._sr.room([(k[2], p.guide.S) for k, p in zip(ks, new)]))
+
+    def _upload(self, dst: torch.Tensor, host: torch.Tensor) -> None:
+        dst.copy_(host, non_blocking=True)
+        self._keep.append(host)
+        if len(self._keep) > 256:
+            del self._keep[:len(self._keep) - 256]
+
+    def acquire(self, plan: GuidePlan) -> tuple:
+        """One user more of the plan's tables -> its fo1_token_guide_t fields (cls_row, n_classes, next_off, row_off); a new (guide,
+        always-bans) pair uploads what is not there yet (current stream) and takes a mask row per distinct state bitmap."""
+        e = self.live.get(plan.key)
+        if e is None:
+            g = plan.guide
+            kc, kn, ks = self._keys(plan)
+            got = []
+            try:
+                crow, new = self._cls.acquire(kc, 1)
+                got.append((self._cls, kc))
+                if new:
+                    self._upload(self.cls[crow], torch.from_numpy(g.cls.view(np.int16).copy()))
+                noff, new = self._next.acquire(kn, g.S * g.C)
+                got.append((self._next, kn))
+                if new:
+                    self._upload(self.next[noff:noff + g.S * g.C], torch.from_numpy(g.next.reshape(-1).copy()))
+                roff, _ = self._sr.acquire(ks, g.S)
+                got.append((self._sr, ks))
+                rows = []
+                try:
+                    for m in plan.bitmaps:
+                        rows.append(-1 if m is None else self.masks.acquire(m))
+                except BaseException:
+                    for r in rows:
+                        self.masks.release(r)
+                    raise
+            except BaseException:
+                for sp, k in got:
+                    sp.release(k, drop=sp is self._sr)
+                raise
+            self._upload(self.state_row[roff:roff + g.S], torch.tensor(rows, dtype=torch.int32))
+            e = self.live[plan.key] = dict(users=0, row=(crow, g.C, noff, roff), mask_rows=rows, keys=(kc, kn, ks))
+        e["users"] += 1
+        return e["row"]
+
+    def release(self, key) -> None:
+        e = self.live[key]
+        assert e["users"] > 0
+        e["users"] -= 1
+        if e["users"] == 0:      # its mask rows may be rewritten from here on: the state-row span goes with them, class row and transitions stay findable
+            for r in e["mask_rows"]:
+                self.masks.release(r)
+            kc, kn, ks = e["keys"]
+            self._cls.release(kc)
+            self._next.release(kn)
+            self._sr.release(ks, drop=True)
+            del self.live[key]
+
+    def users(self) -> int:
+        return sum(e["users"] for e in self.live.values())
+
+    def operands(self, guides: torch.Tensor, gstate: torch.Tensor) -> "ops.GuideOperands":
+        return ops.GuideOperands(self.cls, self.next, self.state_row, guides, gstate)
+
+    def pointers(self) -> tuple:
+        return self.cls.data_ptr(), self.next.data_ptr(), self.state_row.data_ptr()
+
+
+class PassTables:
+    """The mask and guide rows one launch over a pass's rows needs, held together until the launch is enqueued (FO1Engine._first_tokens'
+    scratch tables): the rules' rows stay held while the guides acquire theirs — a released row may be rewritten by the next new bitmap, and
+    the rule table handed to the kernel would still name it.  rules / guides: the rows of ops.token_rules / ops.token_guides (guides: None
+    when no sequence has a guide).  release() gives everything back; an acquire that fails part-way gives back what it took and raises."""
+
+    def __init__(self, masks: "TokenMasks", gtab, trules: Sequence[Optional[TokenRule]], gplans: Sequence[Optional[GuidePlan]] = ()):
+        self.masks, self.gtab = masks, gtab
+        self._rows: List[int] = []
+        self._keys: list = []
+        self.rules, self.guides = [], None
+        try:
+            for t in trules:
+                row, held = (None, []) if t is None else masks.rule_row(t)
+                self.rules.append(row)
+                self._rows += held
+            if any(g is not None for g in gplans):
+                if not gtab.room(gplans):
+                    raise RuntimeError("the token guides of one pass do not fit the guide tables")
+                if not masks.room(gtab.new_bitmaps(gplans)):
+                    raise RuntimeError("the state bitmaps of one pass's token guides do not fit the mask table")
+                self.guides = []
+                for g in gplans:
+                    self.guides.append(None if g is None else gtab.acquire(g))
+                    if g is not None:
+                        self._keys.append(g.key)
+        except BaseException:
+            self.release()
+            raise
+
+    def release(self) -> None:
+        for k in self._keys:
+            self.gtab.release(k)
+        for r in self._rows:
+            self.masks.release(r)
+        self._keys, self._rows = [], []
+
+
+def guide_states_host(gplans: Sequence[Optional[GuidePlan]], first_tokens: torch.Tensor) -> List[int]:
+    """The state after the first token of every guided sequence whose plan brings no device word for it (one host read of the first tokens)."""
+    need = [k for k, p in enumerate(gplans) if p is not None and p.after_first is None]
+    if not need:
+        return [0] * len(gplans)
+    first = first_tokens.to(torch.int32).cpu().tolist()
+    return [p.guide.advance(p.s0, first[k]) if k in need else 0 for k, p in enumerate(gplans)]
+
+
 def new_seen(rows: int, n_vocab: int, dev) -> torch.Tensor:
     """A cleared seen bitmap int32 [rows, ld_words] (csrc/sample.hip: bit t & 31 of word t >> 5 of row b = token t occurs in sequence b)."""
     with torch.inference_mode(False):
@@ -976,6 +1245,11 @@ class BatchDecoder:
         self.rules = None
         self.ruled = False         # some row of the current start() has a rule: the general head runs in its ruled form
         self._mask_rows: List[int] = []      # mask rows the current start() holds
+        self.gtab = None           # token guides: the guide tables (GuideTables), the per-row guide table and the rows' automaton states,
+        self.guides = None         # allocated by the first start() with a guide
+        self.gstate = None
+        self.guided = False        # some row of the current start() has a guide: the general head runs in its guided form
+        self._guide_keys: list = []          # guide-table entries the current start() holds
         self.lp_want: List[int] = []       # per sequence of the current start(): -1 = no record, else its top-n
         self.n_stop = 0
         self.dk = self.dvt = None
@@ -1012,7 +1286,8 @@ class BatchDecoder:
         None per sequence (sampling_table), ends every step in the general head (fo1_decode_head_accept); a penalty needs prompt_ids, the
         ids each request passed: they and the first tokens seed the sequence's seen set (the caller picked the first tokens with it).
         A dict's token-rule keys (ban, allow, ban_first, ban_until: token_rule) restrict that sequence's picks on the device; the rows of the
-        mask table they take are held until the next start().
+        mask table they take are held until the next start().  A dict's guide (guide=TokenGuide: sampling_guides) makes the banned set a
+        function of the sequence's automaton state, which the head advances on the device; its table rows are held until the next start() too.
         logprobs (logprob_wants): None, one int or a list with None / int per sequence = the top-n of the log-probability record kept for that
         sequence (logprobs()); orthogonal to `sampling`: the record launch follows whichever head the step ends in.  first_logprobs: the first
         tokens' records, ops.logprob_rows on the prefill's logits with the largest requested n (FO1Engine._first_logprobs)."""
@@ -1047,12 +1322,13 @@ class BatchDecoder:
         self._keep = [reloc, state, stop]                 # sources of the async uploads stay alive
         srows, kinds = sampling_table(sampling, B)
         trules = sampling_rules(sampling, B, llm.cfg.vocab_size)
+        gplans = sampling_guides(sampling, B, llm.cfg.vocab_size, trules, prompt_ids)
         self.sampled = any(k != "plain" for k in kinds)
         self.general = self.sampled and any(k != "sampled" for k in kinds)
         penalised = any(ops.penalty_on(r[6]) for r in srows)
         if penalised and (prompt_ids is None or len(prompt_ids) != B):
             raise ValueError("BatchDecoder: a repetition penalty needs prompt_ids, one list per sequence")
-        self._start_rules(trules)
+        self._start_rules(unguided_rules(trules, gplans), gplans, first_tokens)
         if self.sampled:
             sp = ops.sample_params(srows)
             self.sparams[:B].copy_(sp, non_blocking=True)
@@ -1075,17 +1351,25 @@ class BatchDecoder:
                 self._keep.append(rt)
                 ops.seen_mark(self.seen, llm.cfg.vocab_size, rt.to(first.device, non_blocking=True), first)
 
-    def _start_rules(self, trules):
-        """The previous run's mask rows go back; this run's rules take theirs (3 rows per sequence at most: there is always room)."""
+    GUIDE_MASKS = 64         # mask rows kept for the guides' state bitmaps, beside the 3 per sequence of the rules
+
+    def _start_rules(self, trules, gplans=(), first_tokens=None):
+        """The previous run's mask and guide rows go back; this run's rules take theirs (3 rows per sequence at most: there is always room),
+        then its guides (RuntimeError when their state bitmaps or tables do not fit)."""
+        if self.gtab is not None:
+            for k in self._guide_keys:
+                self.gtab.release(k)
+        self._guide_keys = []
         if self.masks is not None:
             for r in self._mask_rows:
                 self.masks.release(r)
         self._mask_rows = []
-        self.ruled = any(t is not None for t in trules)
+        self.guided = any(g is not None for g in gplans)
+        self.ruled = self.guided or any(t is not None for t in trules)
         if not self.ruled:
             return
         if self.masks is None:
-            self.masks = TokenMasks(3 * self.MAX_BATCH, self.llm.cfg.vocab_size, self.llm.dev)
+            self.masks = TokenMasks(3 * self.MAX_BATCH + self.GUIDE_MASKS, self.llm.cfg.vocab_size, self.llm.dev)
             with torch.inference_mode(False):
                 self.rules = ops.token_rules([None] * self.MAX_BATCH, self.llm.dev)
         table = []
@@ -1096,9 +1380,37 @@ class BatchDecoder:
         rt = ops.token_rules(table)
         self.rules[:len(table)].copy_(rt, non_blocking=True)
         self._keep.append(rt)
+        if self.guided:
+            self._start_guides(gplans, first_tokens)
+
+    def _start_guides(self, gplans, first_tokens):
+        if self.gtab is None:
+            self.gtab = GuideTables(self.llm.cfg.vocab_size, self.llm.dev, self.masks)
+            with torch.inference_mode(False):
+                self.guides = ops.token_guides([None] * self.MAX_BATCH, self.llm.dev)
+                self.gstate = torch.zeros(self.MAX_BATCH, dtype=torch.int32, device=self.llm.dev)
+        if not (self.gtab.room(gplans) and self.masks.room(self.gtab.new_bitmaps(gplans))):
+            self.guided = self.ruled = False
+            raise RuntimeError("BatchDecoder: the token guides of this batch do not fit the guide tables or the mask table")
+        table = []
+        for g in gplans:
+            table.append(None if g is None else self.gtab.acquire(g))
+            if g is not None:
+                self._guide_keys.append(g.key)
+        gt = ops.token_guides(table)
+        gs = torch.tensor(guide_states_host(gplans, first_tokens), dtype=torch.int32)
+        self.guides[:len(table)].copy_(gt, non_blocking=True)
+        self.gstate[:len(table)].copy_(gs, non_blocking=True)
+        self._keep += [gt, gs]
+        for k, g in enumerate(gplans):
+            if g is not None and g.after_first is not None:      # the caller picked the first token with the guided head: its state word
+                self.gstate[k:k + 1].copy_(g.after_first.view(1), non_blocking=True)
 
     def _rule_args(self) -> dict:
-        return dict(masks=self.masks.table, rules=self.rules[:self.B]) if self.ruled else {}
+        if not self.ruled:
+            return {}
+        guide = dict(guide=self.gtab.operands(self.guides[:self.B], self.gstate[:self.B])) if self.guided else {}
+        return dict(masks=self.masks.table, rules=self.rules[:self.B], **guide)
 
     KV_BUCKET = 2048
 
@@ -1167,6 +1479,9 @@ class BatchDecoder:
             key += ("general", self.seen.data_ptr() if seen else 0)
             if self.ruled:   # (the ruled form reads the mask and rule tables and writes neither: identity in the key, nothing more to roll back)
                 key += ("ruled", self.masks.table.data_ptr(), self.rules.data_ptr())
+            if self.guided:  # (the guided form advances the rows' automaton states: they join the rollback, or the first replay would start
+                key += ("guided", *self.gtab.pointers(), self.guides.data_ptr(), self.gstate.data_ptr())      # from the warm-up step's states)
+                seen += (self.gstate,)
         if self.recording:   # (and one more: the record launch bakes the buffers' identity in, and the warm-up step writes them)
             key += ("logprobs", self.lpb.lp.data_ptr())
             seen += self.lpb.written()
@@ -1284,6 +1599,12 @@ class DecodePool:
         self.ruled_dev = [False] * P                   # does the slot's rule row on the device hold a rule (tracked as `kind` is)
         self.slot_masks: List[List[int]] = [[] for _ in range(P)]      # mask rows a live slot holds
         self.n_ruled = 0                               # live slots with a rule: > 0 runs the general head in its ruled form
+        self.gtab = None                               # token guides: the guide tables (GuideTables), the per-slot guide table and the slots'
+        self.guides = None                             # automaton states, allocated when the first guided sequence joins
+        self.gstate = None
+        self.guided_dev = [False] * P                  # does the slot's guide row on the device hold a guide (tracked as `kind` is)
+        self.slot_guide: list = [None] * P             # the guide-table entry a live slot holds
+        self.n_guided = 0                              # live slots with a guide: > 0 runs the general head in its guided form
         self.lpb = None                                # log-probability records (LogprobBuffers), allocated when the first requesting sequence joins
         self.lp_want = [-1] * P                        # a live slot's request: -1 = no record, else its top-n
         self.lp_dev = [-1] * P                         # what each slot's `want` word on the device holds (tracked as `kind` is)
@@ -1346,6 +1667,10 @@ class DecodePool:
         prompt's set.  While any live slot is not plain the step ends in the general head (step()).  A dict's token-rule keys (ban, allow,
         ban_first, ban_until: token_rule) restrict that sequence's picks on the device: equal banned sets share a row of the mask table, at
         most MAX_MASKS distinct ones are live at once (can_take), and the rows are released when the sequence is harvested.
+        A dict's guide (guide=TokenGuide: sampling_guides) makes the banned set a function of the sequence's automaton state, which the head
+        advances on the device: the slot's state word is set here to the state after the first token (the dict's guide_state word when the
+        caller picked that token with the guided head, else computed on the host from first_tokens — one host read), every state's bitmap
+        takes a mask row (equal ones are shared, within and across guides), and the rows are released when the sequence is harvested.
         logprobs / first_logprobs: as BatchDecoder.start takes them; while any live slot asks for a record the record launch follows the head
         (step()), and harvest(records=True) hands the finished slots' records out.  A pool no requesting sequence ever joined holds no
         record buffer and issues exactly the launches and copies it always has."""
@@ -1355,11 +1680,14 @@ class DecodePool:
             raise ValueError("DecodePool: logprobs needs first_logprobs, the first tokens' records")
         srows, kinds = sampling_table(sampling, B)
         trules = sampling_rules(sampling, B, self.llm.cfg.vocab_size)
+        gplans = sampling_guides(sampling, B, self.llm.cfg.vocab_size, trules, prompt_ids)
+        trules = unguided_rules(trules, gplans)
         penalised = [ops.penalty_on(r[6]) for r in srows]
         if any(penalised) and (prompt_ids is None or len(prompt_ids) != B):
             raise ValueError("DecodePool: a repetition penalty needs prompt_ids, one list per sequence")
-        if not self._mask_room(trules):
-            raise RuntimeError(f"DecodePool: {self.MAX_MASKS} different token masks are live; wait for sequences to finish")
+        full = self._table_without_room(trules, gplans)
+        if full is not None:
+            raise RuntimeError(f"DecodePool: {full}; wait for sequences to finish")
         set_row = self._stop_set_row(tuple(stop_id_list(stop_ids, self.MAX_STOP, "DecodePool")))
         max_new = token_budget(max_new_tokens, self.IDS_CAP, "DecodePool")
         if B > len(self.free):
@@ -1372,6 +1700,7 @@ class DecodePool:
             self._join_slots(slots, kcache, vtcache, seqs, deltas, first_tokens, max_new, set_row)
             self._join_sampling(slots, srows, kinds, penalised, first_tokens, prompt_ids)
             self._join_rules(slots, trules)
+            self._join_guides(slots, gplans, first_tokens)
             self._join_logprobs(slots, wants, first_logprobs)
         except BaseException:
             # nothing of this submission is live: its slots go back (their device state may be half written — the next occupant's
@@ -1386,6 +1715,7 @@ class DecodePool:
             self.free += slots
             for s in slots:
                 self._release_masks(s)
+                self._release_guide(s)
             raise
         for k, s in enumerate(slots):
             # a tag identifies ONE occupancy of a slot: harvest() compares it by identity against an older snapshot, so the default must
@@ -1397,6 +1727,7 @@ class DecodePool:
             self._set_users[set_row] += 1
             self.n_general += kinds[k] != "plain"
             self.n_ruled += trules[k] is not None
+            self.n_guided += gplans[k] is not None
             self.lp_want[s] = wants[k]
             self.n_logprob += wants[k] >= 0
         return slots
@@ -1413,11 +1744,60 @@ class DecodePool:
         for k in write:
             self.lp_dev[slots[k]] = wants[k]
 
-    def _mask_room(self, trules) -> bool:
+    def _table_without_room(self, trules, gplans=()) -> Optional[str]:
+        """None when there is a mask row for every banned set of the rules and every state bitmap of the guides and room in the guide tables;
+        else which table is full."""
         maps = [m for t in trules if t is not None for m in t.bitmaps()]
-        if not maps:
-            return True
-        return self.masks.room(maps) if self.masks is not None else len(set(maps)) <= self.MAX_MASKS
+        if any(g is not None for g in gplans):      # (nothing allocated yet: the same answers from the bookkeeping alone)
+            gtab = self.gtab if self.gtab is not None else GuideTables(self.llm.cfg.vocab_size, None, None)
+            if not gtab.room(gplans):
+                return "the token-guide tables (class rows, transitions, state rows) are full"
+            maps += gtab.new_bitmaps(gplans)
+        if not maps or (self.masks.room(maps) if self.masks is not None else len(set(maps)) <= self.MAX_MASKS):
+            return None
+        return f"{self.MAX_MASKS} different token masks are live"
+
+    def _mask_room(self, trules, gplans=()) -> bool:
+        return self._table_without_room(trules, gplans) is None
+
+    def _ensure_masks(self):
+        if self.masks is None:      # (graphs captured before are unreachable for a ruled step: its key holds the tables' identity)
+            self.masks = TokenMasks(self.MAX_MASKS, self.llm.cfg.vocab_size, self.llm.dev)
+            with torch.inference_mode(False):
+                self.rules = ops.token_rules([None] * self.P, self.llm.dev)
+
+    def _join_guides(self, slots, gplans, first_tokens):
+        """The guide rows and automaton states of a submission's slots.  Nothing is enqueued for a sequence without a guide whose slot holds
+        none: a slot a guided sequence has left gets cls_row = -1 back when an unguided one reuses it."""
+        write = [k for k, s in enumerate(slots) if gplans[k] is not None or self.guided_dev[s]]
+        if not write:
+            return
+        self._ensure_masks()
+        if self.gtab is None:
+            self.gtab = GuideTables(self.llm.cfg.vocab_size, self.llm.dev, self.masks)
+            with torch.inference_mode(False):
+                self.guides = ops.token_guides([None] * self.P, self.llm.dev)
+                self.gstate = torch.zeros(self.P, dtype=torch.int32, device=self.llm.dev)
+        table = []
+        for k in write:
+            table.append(None if gplans[k] is None else self.gtab.acquire(gplans[k]))
+            if gplans[k] is not None:
+                self.slot_guide[slots[k]] = gplans[k].key
+        gt = ops.token_guides(table)
+        gs = torch.tensor(guide_states_host(gplans, first_tokens), dtype=torch.int32)
+        self._keep += [gt, gs]
+        for j, k in enumerate(write):
+            s = slots[k]
+            self.guides[s:s + 1].copy_(gt[j:j + 1], non_blocking=True)
+            self.guided_dev[s] = gplans[k] is not None
+            if gplans[k] is not None:
+                src = gplans[k].after_first
+                self.gstate[s:s + 1].copy_(gs[k:k + 1] if src is None else src.view(1), non_blocking=True)
+
+    def _release_guide(self, slot: int) -> None:
+        if self.slot_guide[slot] is not None:
+            self.gtab.release(self.slot_guide[slot])
+            self.slot_guide[slot] = None
 
     def _join_rules(self, slots, trules):
         """The rule rows of a submission's slots.  Nothing is enqueued for a sequence without a rule whose slot holds none: a slot a
@@ -1425,10 +1805,7 @@ class DecodePool:
         write = [k for k, s in enumerate(slots) if trules[k] is not None or self.ruled_dev[s]]
         if not write:
             return
-        if self.masks is None:      # (graphs captured before are unreachable for a ruled step: its key holds the tables' identity)
-            self.masks = TokenMasks(self.MAX_MASKS, self.llm.cfg.vocab_size, self.llm.dev)
-            with torch.inference_mode(False):
-                self.rules = ops.token_rules([None] * self.P, self.llm.dev)
+        self._ensure_masks()
         table = []
         for k in write:
             row, held = (None, []) if trules[k] is None else self.masks.rule_row(trules[k])
@@ -1476,7 +1853,14 @@ class DecodePool:
         if sampling is None:
             return True
         try:      # (a submission that finds no room in a table nobody uses never will: join() raises that too)
-            return self._mask_room(sampling_rules(sampling, B, self.llm.cfg.vocab_size)) or self.masks is None or not any(self.masks.users)
+            trules = sampling_rules(sampling, B, self.llm.cfg.vocab_size)
+            gplans = []      # (the tables a guide takes do not depend on the state it starts in: no prompt ids needed here)
+            for sp, t in zip(_per_sequence(sampling, B), trules):
+                g, always = (sp.get("guide") if sp is not None else None), (t.always if t is not None else None)
+                if g is not None and not isinstance(g, TokenGuide):
+                    raise ValueError("guide: not a TokenGuide")
+                gplans.append(None if g is None else GuidePlan(g, always, tuple(g.state_bitmaps(always)), g.start, None))
+            return self._mask_room(unguided_rules(trules, gplans), gplans) or self.masks is None or not any(self.masks.users)
         except ValueError:
             return True
 
@@ -1564,6 +1948,8 @@ class DecodePool:
             key += ("general", self.seen.data_ptr() if self.seen is not None else 0)
             if self.n_ruled > 0:      # (the ruled form reads the mask and rule tables and never writes them: nothing joins the rollback)
                 key += ("ruled", self.masks.table.data_ptr(), self.rules.data_ptr())
+            if self.n_guided > 0:     # (the guided form advances the slots' automaton states: gstate joins the rollback in step())
+                key += ("guided", self.masks.table.data_ptr(), self.rules.data_ptr(), *self.gtab.pointers(), self.guides.data_ptr(), self.gstate.data_ptr())
         if self.n_logprob > 0:
             key += ("logprobs", self.lpb.lp.data_ptr())
         return key
@@ -1609,7 +1995,9 @@ class DecodePool:
                     x = ops.gemm(a, w["wdown"], residual=x)
                 logits = ops.gemm(ops.rmsnorm(x, llm.norm, c.rms_norm_eps), llm.lm_head)
             if general:      # plain slots ride as greedy rows without penalty; empty and finished slots return early, as in the greedy head
-                rule = dict(masks=self.masks.table, rules=self.rules) if self.n_ruled > 0 else {}
+                rule = dict(masks=self.masks.table, rules=self.rules) if self.n_ruled > 0 or self.n_guided > 0 else {}
+                if self.n_guided > 0:
+                    rule["guide"] = self.gtab.operands(self.guides, self.gstate)
                 ops.decode_head_accept(logits, self.sparams, st, self.plan, self.ids, self.stop, self.done, seen=self.seen, per_sequence_sets=True, **rule)
             else:
                 ops.decode_argmax_accept(logits, None, st, self.plan, self.ids, self.stop, self.done, per_sequence_sets=True)
@@ -1636,6 +2024,8 @@ class DecodePool:
             roll = (self.state, self.plan, self.ids, self.done)
             if general and self.seen is not None:
                 roll += (self.seen,)
+            if general and self.n_guided > 0:      # or the first replay would start from the warm-up step's states, not the ones join() set
+                roll += (self.gstate,)
             if record:
                 roll += self.lpb.written()
             ent = self._graphs.get(key)
@@ -1695,6 +2085,8 @@ class DecodePool:
                 self.n_general -= self.kind[s] != "plain"
                 self.n_ruled -= bool(self.slot_masks[s])
                 self._release_masks(s)
+                self.n_guided -= self.slot_guide[s] is not None
+                self._release_guide(s)
         return out
 
     def drain(self, use_graph: bool = True, poll: int = 8, records: bool = False) -> List[tuple]:

@@ -367,6 +367,7 @@ class FO1Engine:
                         next_tokens=toks, region_ranges=ranges, row0=bp.row0, _keep=keep)
 
     PREFILL_MAX = 32       # requests per packed prefill pass of generate_batch
+    GUIDE_MASKS = 64       # scratch mask rows for the state bitmaps of a pass's token guides (the first tokens' pick)
     PREFILL_ROWS = 65536   # ... and ViT patch rows per pass: 32 COCO-sized images are 50k rows; a group of the datasets' largest images (32 x 10 800
                            # patches: CountBench / Pixmo through evaluation/eval_countbench.py) would otherwise be ONE pass whose SimpleFPN scratch
                            # alone is 44 GB (round 5: the driver-level CountBench run hit it)
@@ -531,11 +532,17 @@ class FO1Engine:
         """The first token of every sequence of the pass that just ran, from the prefill's logits: its greedy picks when every request is
         plain; else one launch of the device sampler with counter 0 — the general head (greedy rows, penalties against the prompts' seen
         sets, marked into a scratch bitmap first) unless every row is a plain draw.  A request's token rule (llm.token_rule) goes to the ruled
-        form of that head through a scratch mask table: counter 0, so its first-token and early bans apply."""
-        from .llm import TokenMasks, new_seen, sampling_rules, sampling_table
+        form of that head through a scratch mask table: counter 0, so its first-token and early bans apply.  A request's guide
+        (llm.sampling_guides) goes to the guided form through scratch guide tables: the pick is made in the guide's start state (the prompt's
+        state for a ban_sequences guide), and the device word holding the state after it is put into the request's dict as `guide_state`, which
+        BatchDecoder.start / DecodePool.join copy into their own state array — no host read."""
+        from .llm import GuideTables, PassTables, TokenMasks, new_seen, sampling_guides, sampling_rules, sampling_table, unguided_rules
         n = len(requests)
         rows, kinds = sampling_table(per, n)
         trules = sampling_rules(per, n, self.cfg.llm.vocab_size)
+        gplans = sampling_guides(per, n, self.cfg.llm.vocab_size, trules, [r["ids"] for r in requests])
+        trules = unguided_rules(trules, gplans)
+        guided = any(g is not None for g in gplans)
         if all(k == "plain" for k in kinds):
             return self._last_next_tokens[:n]
         with ops.workspace_scope(self._ws_owner):
@@ -549,19 +556,30 @@ class FO1Engine:
                 seen = self._seen_scratch
                 self._seen_keep = ops.mark_prompts(seen, self.cfg.llm.vocab_size, list(range(n)), [r["ids"] for r in requests])
             rule = {}
-            if any(t is not None for t in trules):
+            if guided or any(t is not None for t in trules):
                 tm = getattr(self, "_mask_scratch", None)
-                if tm is None or tm.rows < 3 * n:
-                    tm = self._mask_scratch = TokenMasks(3 * max(n, self.PREFILL_MAX), self.cfg.llm.vocab_size, self.dev)
-                held, table_r = [], []
-                for t in trules:
-                    row, rs = (None, []) if t is None else tm.rule_row(t)
-                    table_r.append(row)
-                    held += rs
-                rule = dict(masks=tm.table, rules=ops.token_rules(table_r, self.dev))
-                for r in held:      # (the launch below is ordered before the next pass's uploads: same stream)
-                    tm.release(r)
-            return ops.sample_rows(self._last_logits[:n], table, seen=seen, general=True, **rule)
+                if tm is None or tm.rows < 3 * n + self.GUIDE_MASKS:
+                    tm = self._mask_scratch = TokenMasks(3 * max(n, self.PREFILL_MAX) + self.GUIDE_MASKS, self.cfg.llm.vocab_size, self.dev)
+                    self._guide_scratch = None
+                gt = getattr(self, "_guide_scratch", None)
+                if guided and gt is None:
+                    gt = self._guide_scratch = GuideTables(self.cfg.llm.vocab_size, self.dev, tm)
+                # every row of the pass, the rules' and the guides', is held until the launch is enqueued (the next pass's uploads are
+                # ordered behind it: same stream): a row given back earlier could be rewritten by a later acquire of this same pass
+                held = PassTables(tm, gt, trules, gplans)
+                try:
+                    rule = dict(masks=tm.table, rules=ops.token_rules(held.rules, self.dev))
+                    if guided:
+                        gstate = torch.tensor([0 if g is None else g.s0 for g in gplans], dtype=torch.int32).to(self.dev)
+                        rule["guide"] = gt.operands(ops.token_guides(held.guides, self.dev), gstate)
+                    out = ops.sample_rows(self._last_logits[:n], table, seen=seen, general=True, **rule)
+                finally:
+                    held.release()
+                for k, g in enumerate(gplans):      # (the state words stay with the requests)
+                    if g is not None:
+                        per[k]["guide_state"] = gstate[k:k + 1]
+                return out
+            return ops.sample_rows(self._last_logits[:n], table, seen=seen, general=True)
 
     @staticmethod
     def _logprob_part(logprobs, a: int, b: int):

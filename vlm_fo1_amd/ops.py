@@ -9,7 +9,7 @@ import math
 import itertools
 import os
 import threading
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import ctypes
 
@@ -1049,6 +1049,38 @@ def _rule_operands(masks: Optional[torch.Tensor], rules: Optional[torch.Tensor],
     return masks.data_ptr(), masks.shape[0], masks.shape[1], rules.data_ptr()
 
 
+NO_GUIDE = (-1, 0, 0, 0)       # fo1_token_guide_t of a row without a guide
+
+
+def token_guides(rows: Sequence, device=None) -> torch.Tensor:
+    """The fo1_token_guide_t table (int32 [B, 4]) from rows of (cls_row, n_classes, next_off, row_off) — a row of the class table, the number of
+    classes, the guide's offsets into the `next` and `state_row` tables (include/fo1.h) — or None for a row without a guide.  On `device` when
+    given, else a host tensor."""
+    tab = torch.tensor([list(NO_GUIDE) if r is None else [int(x) for x in r] for r in rows], dtype=torch.int32).view(-1, 4)
+    return tab if device is None else tab.to(device)
+
+
+class GuideOperands(NamedTuple):
+    """What a guided head takes besides masks and rules (include/fo1.h): cls int16 [rows, ld_cls >= V] holding the uint16 token classes, next
+    int32 [n_next], state_row int32 [n_state_row] (mask-table row of every state, -1 = nothing banned), guides (token_guides, int32 [>= B, 4])
+    and gstate int32 [>= B], the rows' automaton states — the one table the head writes."""
+    cls: torch.Tensor
+    next: torch.Tensor
+    state_row: torch.Tensor
+    guides: torch.Tensor
+    gstate: torch.Tensor
+
+
+def _guide_operands(g: GuideOperands, B: int, V: int):
+    assert g.cls.dtype == torch.int16 and g.cls.is_cuda and g.cls.dim() == 2 and g.cls.is_contiguous() and g.cls.shape[0] >= 1 and g.cls.shape[1] >= V
+    for t in (g.next, g.state_row, g.gstate):
+        assert t.dtype == torch.int32 and t.is_cuda and t.dim() == 1 and t.is_contiguous() and t.numel() >= 1
+    assert g.guides.dtype == torch.int32 and g.guides.is_cuda and g.guides.dim() == 2 and g.guides.shape[1] == 4 and g.guides.is_contiguous()
+    assert g.guides.shape[0] >= B and g.gstate.numel() >= B
+    return (g.cls.data_ptr(), g.cls.shape[0], g.cls.shape[1], g.next.data_ptr(), g.next.numel(), g.state_row.data_ptr(), g.state_row.numel(),
+            g.guides.data_ptr(), g.gstate.data_ptr())
+
+
 def _sample_operands(logits: torch.Tensor, params: torch.Tensor):
     _chk(logits, "logits")
     pl, ld, B, V = _rows(logits, "logits")
@@ -1061,12 +1093,15 @@ def _sample_operands(logits: torch.Tensor, params: torch.Tensor):
 
 def sample_rows(logits: torch.Tensor, params: torch.Tensor, counter: Optional[torch.Tensor] = None, counter_stride: int = 1,
                 u: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, seen: Optional[torch.Tensor] = None,
-                general: bool = False, masks: Optional[torch.Tensor] = None, rules: Optional[torch.Tensor] = None) -> torch.Tensor:
+                general: bool = False, masks: Optional[torch.Tensor] = None, rules: Optional[torch.Tensor] = None,
+                guide: Optional[GuideOperands] = None) -> torch.Tensor:
     """int32 [B]: one sampled id per row of logits [B, V] bf16 (fo1_sample_rows_bf16): temperature / top-k / top-p per row from `params`
     (sample_params), draw = Philox(counter, stream; seed) with counter = counter[b * counter_stride] (device int32; None = 0), or the explicit
     u [B] fp32.  seen (int32 [>= B, ld_words] bitmap) or general=True: the general head (fo1_sample_rows_seen_bf16), which also honours a
     row's greedy flag and its repetition penalty; without a bitmap no row may have a penalty on.  masks (int32 [R, ld_words], a set bit = token
-    banned) and rules (token_rules, int32 [>= B, 4]): the ruled head (fo1_sample_rows_ruled_bf16), the general head behind each row's bans."""
+    banned) and rules (token_rules, int32 [>= B, 4]): the ruled head (fo1_sample_rows_ruled_bf16), the general head behind each row's bans.
+    guide (GuideOperands, with masks and rules): the guided head (fo1_sample_rows_guided_bf16) — a guided row b picks in state guide.gstate[b]
+    and the state after the pick is written back."""
     head, tail = _sample_operands(logits, params)
     B = head[3]
     if out is None:
@@ -1076,6 +1111,12 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, counter: Optional[to
         assert counter.dtype == torch.int32 and counter.is_cuda and counter.numel() > (B - 1) * counter_stride
     if u is not None:
         assert u.dtype == torch.float32 and u.is_cuda and u.is_contiguous() and u.numel() == B
+    if guide is not None:
+        ps, ldw = _seen_operand(seen, B, head[2])
+        rc = _L.load().fo1_sample_rows_guided_bf16(*head, _ptr(counter), int(counter_stride), _ptr(u), out.data_ptr(), *tail[:2], ps, ldw,
+                                                   *_rule_operands(masks, rules, B, head[2]), tail[2], *_guide_operands(guide, B, head[2]))
+        _L.check(rc, "fo1_sample_rows_guided_bf16")
+        return out
     if masks is not None or rules is not None:
         ps, ldw = _seen_operand(seen, B, head[2])
         rc = _L.load().fo1_sample_rows_ruled_bf16(*head, _ptr(counter), int(counter_stride), _ptr(u), out.data_ptr(), *tail[:2], ps, ldw,
@@ -1108,11 +1149,13 @@ def decode_sample_accept(logits: torch.Tensor, params: torch.Tensor, state: torc
 
 def decode_head_accept(logits: torch.Tensor, params: torch.Tensor, state: torch.Tensor, plan: torch.Tensor, ids_out: torch.Tensor,
                        stop_ids: Optional[torch.Tensor], done: torch.Tensor, seen: Optional[torch.Tensor] = None,
-                       per_sequence_sets: bool = False, masks: Optional[torch.Tensor] = None, rules: Optional[torch.Tensor] = None) -> None:
+                       per_sequence_sets: bool = False, masks: Optional[torch.Tensor] = None, rules: Optional[torch.Tensor] = None,
+                       guide: Optional[GuideOperands] = None) -> None:
     """The general head of a decode step (fo1_decode_head_accept): decode_sample_accept with each row's greedy flag and repetition penalty
     honoured; the accepted token's bit is set in the row's `seen` bitmap (int32 [>= B, ld_words]; None only when no row has a penalty).
     per_sequence_sets: as decode_argmax_accept.  masks / rules (as sample_rows takes them): the ruled head (fo1_decode_head_ruled_accept), which
-    reads both tables and writes neither."""
+    reads both tables and writes neither.  guide (GuideOperands, with masks and rules): the guided head (fo1_decode_head_guided_accept), which
+    also advances guide.gstate, the only guide table it writes."""
     B = state.shape[0]
     assert state.dtype == plan.dtype == ids_out.dtype == done.dtype == torch.int32 and ids_out.is_contiguous() and plan.is_contiguous()
     assert state.is_contiguous() and logits.shape[0] == B
@@ -1122,6 +1165,12 @@ def decode_head_accept(logits: torch.Tensor, params: torch.Tensor, state: torch.
         assert stop_ids is not None and stop_ids.dim() == 2 and stop_ids.shape[1] == 17 and stop_ids.is_contiguous() and stop_ids.dtype == torch.int32
         n_stop = -1
     ps, ldw = _seen_operand(seen, B, head[2])
+    if guide is not None:
+        rc = _L.load().fo1_decode_head_guided_accept(*head, state.data_ptr(), plan.data_ptr(), ids_out.data_ptr(), ids_out.shape[1],
+                                                     stop_ids.data_ptr() if n_stop else None, n_stop, done.data_ptr(), *tail[:2], ps, ldw,
+                                                     *_rule_operands(masks, rules, B, head[2]), tail[2], *_guide_operands(guide, B, head[2]))
+        _L.check(rc, "fo1_decode_head_guided_accept")
+        return
     if masks is not None or rules is not None:
         rc = _L.load().fo1_decode_head_ruled_accept(*head, state.data_ptr(), plan.data_ptr(), ids_out.data_ptr(), ids_out.shape[1],
                                                     stop_ids.data_ptr() if n_stop else None, n_stop, done.data_ptr(), *tail[:2], ps, ldw,
