@@ -596,6 +596,38 @@ int fo1_decode_head_guided_accept(const void* logits, long long ld_logits, int n
                                   void* stream, const uint16_t* cls, int cls_rows, long long ld_cls, const int32_t* next, long long n_next,
                                   const int32_t* state_row, long long n_state_row, const fo1_token_guide_t* guides /* device [B] */,
                                   int32_t* gstate /* device [B], read and written */);
+/* Budget-aware guides: a guided row may close its structure before its token budget runs out.  With c tokens generated
+ * and an effective budget N, r = N - c - 1 tokens may still follow this pick.  A guided row b whose closes[b].depth > 0 picks, while
+ * 0 <= r < depth, behind the mask row close_row[close_off + s * depth + r] instead of state_row[row_off + s] (s = gstate[b]); for r >= depth, for
+ * r < 0, for depth <= 0 and for a row without a guide everything is the _guided entry's.  The callers fill close_row so that the row of (s, r)
+ * holds { t : next[s][cls[t]] < 0 or more than r tokens lead from next[s][cls[t]] to an accepting state }.  An index close_off + s * depth + r
+ * outside [0, n_close_row) (a negative close_off included) falls back to the state's plain row; a mask-row index outside the mask table means
+ * "no mask", as everywhere.  Nothing is read out of range.  The advance of gstate, early_row and first_row are the _guided entry's.
+ *   fo1_sample_rows_closing_bf16     fo1_sample_rows_guided_bf16 + closing: r = budget[b] - c - 1, c = counter[b * counter_stride] (NULL = 0)
+ *   fo1_decode_head_closing_accept   fo1_decode_head_guided_accept + closing: r = min(state[b][5], ids_ld) - state[b][4] - 1
+ * closes == NULL: the call is the _guided entry's.  closes != NULL needs guides, close_row (and budget, in the rows form).  The step reads the
+ * new tables and writes none of them.  Still one launch whatever the data, no host read, capturable, B <= 256. */
+typedef struct fo1_guide_close {      /* 16 bytes; depth <= 0: the row has no closing rule */
+    int32_t close_off;    /* close_row[close_off + s * depth + r] (int32): mask-table row of state s with r < depth tokens left */
+    int32_t depth;        /* D: the closing rule bans nothing more from D tokens left on */
+    int32_t reserved[2];
+} fo1_guide_close_t;
+int fo1_sample_rows_closing_bf16(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params,
+                                 const int32_t* counter /* NULL = 0 */, int counter_stride, const float* u /* device [B]; NULL = Philox */,
+                                 int32_t* out /* [B] */, void* workspace, size_t workspace_bytes, const uint32_t* seen, long long ld_words,
+                                 const uint32_t* masks, int mask_rows, long long mask_ld_words, const fo1_token_rule_t* rules /* device [B] */,
+                                 void* stream, const uint16_t* cls, int cls_rows, long long ld_cls, const int32_t* next, long long n_next,
+                                 const int32_t* state_row, long long n_state_row, const fo1_token_guide_t* guides /* device [B] */,
+                                 int32_t* gstate /* device [B], read and written */, const int32_t* close_row, long long n_close_row,
+                                 const fo1_guide_close_t* closes /* device [B] */, const int32_t* budget /* device [B] */);
+int fo1_decode_head_closing_accept(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params,
+                                   int32_t* state, int32_t* plan, int32_t* ids_out, int ids_ld, const int32_t* stop_ids, int n_stop,
+                                   int32_t* done, void* workspace, size_t workspace_bytes, uint32_t* seen, long long ld_words,
+                                   const uint32_t* masks, int mask_rows, long long mask_ld_words, const fo1_token_rule_t* rules /* device [B] */,
+                                   void* stream, const uint16_t* cls, int cls_rows, long long ld_cls, const int32_t* next, long long n_next,
+                                   const int32_t* state_row, long long n_state_row, const fo1_token_guide_t* guides /* device [B] */,
+                                   int32_t* gstate /* device [B], read and written */, const int32_t* close_row, long long n_close_row,
+                                   const fo1_guide_close_t* closes /* device [B] */);
 /* Log-probabilities of generated tokens.  For a bf16 logits row l[0..V) with F = { i : l_i finite }:
  *   m = max_F l,  S = sum_{i in F} exp(l_i - m) (fp32, a fixed order),  lp_i = (l_i - m) - log S as fp32 for i in F,  lp_i = -inf otherwise
  * (the sampler's rule: a non-finite entry has weight 0); a row with empty F gives -inf everywhere.  This is the log-softmax of the RAW logits:

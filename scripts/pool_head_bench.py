@@ -13,7 +13,13 @@
   guided     the guided general head fo1_decode_head_guided_accept, every sequence greedy with one shared two-state guide whose states both
              ban `banned`'s 1000 ids (one live mask row) and which changes state with every token: what the guide adds to `banned`,
   sampled_guided   the same guide on every sequence of `sampled`: what it adds to `sampled_banned`,
-  one_banned / one_guided   one such ruled / guided greedy sequence among 127 plain ones.
+  one_banned / one_guided   one such ruled / guided greedy sequence among 127 plain ones,
+  closing    the closing form of the guided head, fo1_decode_head_closing_accept: every sequence greedy with one shared two-state guide over
+             three classes (banned ids, even ids, odd ids: an even id changes the state, an odd one keeps it) whose state 0 is accepting, so
+             D = 1 and the budget's last pick alone reads a closing row — every timed step pays the closing form's two table reads and
+             resolves to the state's plain row, the steady state of a closing sequence,
+  guided_open   the same guide without accepting states through fo1_decode_head_guided_accept: what `closing` adds to,
+  sampled_closing / sampled_guided_open   the two on every sequence of `sampled`.
 The heads are timed alternately, `--rounds` times each in one process, so the spread of a figure is the spread between its rounds; the pool is
 drained and re-joined for every timing.  Prints one JSON object.
 
@@ -21,7 +27,8 @@ drained and re-joined for every timing.  Prints one JSON object.
 
 With `greedy` among the heads the output also holds each other head's increment over it (difference of the medians of this process), and
 for a ruled head its increment over the same head without a rule (banned, min_new: greedy_general; sampled_banned: sampled), for a guided
-head its increment over the ruled head with the same mask row (guided: banned; sampled_guided: sampled_banned; one_guided: one_banned).
+head its increment over the ruled head with the same mask row (guided: banned; sampled_guided: sampled_banned; one_guided: one_banned), for
+a closing head its increment over the guided head with the same guide (closing: guided_open; sampled_closing: sampled_guided_open).
 
 --root DIR imports the package from another checkout (e.g. the parent commit, for the greedy figure of both on one box; only `greedy`
 exists there; a head the other checkout lacks cannot be named)."""
@@ -41,7 +48,7 @@ def main():
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=5)
     HEADS = ["greedy", "sampled", "penalised", "greedy_lp0", "greedy_lp8", "greedy_general", "banned", "sampled_banned", "min_new", "guided",
-             "sampled_guided", "one_banned", "one_guided"]
+             "sampled_guided", "one_banned", "one_guided", "closing", "guided_open", "sampled_closing", "sampled_guided_open"]
     ap.add_argument("--heads", nargs="+", default=HEADS[:3], choices=HEADS)
     ap.add_argument("--root", default=None, help="import vlm_fo1_amd from this checkout instead of the script's own")
     args = ap.parse_args()
@@ -84,6 +91,17 @@ def main():
         guide = TokenGuide(cls, np.array([[1, -1], [0, -1]], np.int32), 0, V)      # both states ban `ban`: one shared mask row, as `banned` has
         sampling.update(guided=dict(greedy=True, guide=guide), sampled_guided=dict(sampling["sampled"], guide=guide))
     sampling.update(one_banned=None, one_guided=None)
+    unclosed = dict(closing="guided_open", sampled_closing="sampled_guided_open")
+    if any(h in unclosed or h in unclosed.values() for h in args.heads):
+        import numpy as np
+        from vlm_fo1_amd.guide import TokenGuide
+        cls = (np.arange(V) % 2 * 2).astype(np.uint16)      # class 0: even ids, class 2: odd ids, class 1: `ban`
+        cls[ban] = 1
+        nx = np.array([[1, -1, 0], [0, -1, 1]], np.int32)
+        for name, accept in (("closing", [0]), ("guided_open", None)):
+            g3 = TokenGuide(cls, nx, 0, V, accept=accept)
+            sampling[name] = dict(greedy=True, guide=g3)
+            sampling["sampled_" + name] = dict(sampling["sampled"], guide=g3)
 
     def one(head):
         left, base = P, 0
@@ -131,6 +149,9 @@ def main():
     guided = {h: round(out["heads"][h]["median"] - out["heads"][u]["median"], 4) for h, u in unguided.items() if h in times and u in times}
     if guided:
         out["increment_over_ruled_ms"] = guided
+    closing = {h: round(out["heads"][h]["median"] - out["heads"][u]["median"], 4) for h, u in unclosed.items() if h in times and u in times}
+    if closing:
+        out["increment_over_guided_ms"] = closing
     print(json.dumps(out))
 
 

@@ -333,11 +333,13 @@ class FO1ForCausalLM:
             raise ValueError(f"guide: a vlm_fo1_amd.guide.TokenGuide, as region_guide() builds one (got {type(guide).__name__})")
         return guide
 
-    def region_guide(self, tokenizer, n_regions: int):
+    def region_guide(self, tokenizer, n_regions: int, close: bool = False):
         """The guide of the FO1 answer language `<ground>label</ground><objects><region3>...</objects>` for a request with n_regions boxes
         (vlm_fo1_amd.guide.region_answer): the five structural ids and the <regionK> ids from tokenizer.convert_tokens_to_ids — every
         <regionK> the tokenizer knows, K = 0, 1, ... —, the stop ids from config.eos_ids().  ValueError: a token that is not a single id of
-        the vocabulary, or fewer <regionK> tokens than n_regions."""
+        the vocabulary, or fewer <regionK> tokens than n_regions.
+        close=True: the answer also closes its structure before max_new_tokens runs out — generate(guide=, max_new_tokens=k) ends outside
+        `<ground>` / `<objects>` for every k; the budget is generate()'s max_new_tokens, no further keyword."""
         from vlm_fo1_amd.guide import region_answer
         V = self.engine.cfg.llm.vocab_size
         unk = getattr(tokenizer, "unk_token_id", None)
@@ -355,7 +357,7 @@ class FO1ForCausalLM:
             regions.append(one(f"<region{len(regions)}>"))
         if int(n_regions) > len(regions):
             raise ValueError(f"region_guide: the tokenizer has {len(regions)} <regionK> tokens, the request {int(n_regions)} boxes")
-        return region_answer(V, *struct, regions, int(n_regions), self.config.eos_ids())
+        return region_answer(V, *struct, regions, int(n_regions), self.config.eos_ids(), close=bool(close))
 
     @staticmethod
     def _logprob_plan(kwargs: dict) -> Optional[int]:
@@ -501,7 +503,7 @@ class FO1ForCausalLM:
         eng.prefill_batch([req], use_graph=self.use_graph)
         hp = eng._last_batch
         per = [dict(sampling, stream=stream)]      # (a greedy request with a repetition penalty takes this loop too: dict(greedy=True, ...))
-        tok = eng._first_tokens(per, [req])
+        tok = eng._first_tokens(per, [req], n_max)      # (a closing guide's budget: the one dec.start() gets)
         dec = eng._decoder()
         lpa = {} if logprobs is None else dict(logprobs=logprobs, first_logprobs=eng._first_logprobs(logprobs, tok, 1))
         dec.start(hp["seqs"], hp["delta"], tok, n_max, (), sampling=per, prompt_ids=[req["ids"]], **lpa)
@@ -551,7 +553,8 @@ class FO1ForCausalLM:
         in the BatchDecoder, stepped one by one with a streamer or unexpressible stop criteria; max_new_tokens beyond IDS_CAP is a ValueError.
         guide: None (off) or a vlm_fo1_amd.guide.TokenGuide — region_guide(tokenizer, n_regions) for the FO1 answer language, guide.ban_sequences
         for multi-token banned sequences: the banned set of every pick follows the guide's automaton state, which the head advances on the
-        device; decoded as a constrained generation is.  max_new_tokens may still cut an answer short inside a structure."""
+        device; decoded as a constrained generation is.  max_new_tokens may still cut an answer short inside a structure unless the guide has
+        accepting states (region_guide(..., close=True)): then the head closes the structure before the budget runs out."""
         lpn = self._logprob_plan(dict(output_logprobs=output_logprobs, top_logprobs=top_logprobs))
         if lpn is not None and not self._fits_device_loop(max_new_tokens):
             from vlm_fo1_amd.llm import BatchDecoder

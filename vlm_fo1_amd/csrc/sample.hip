@@ -42,6 +42,11 @@
 // pick thread 0 loads cls[tok] and next[next_off + s * C + cls], issues the accept, and stores the new state (a negative entry keeps the old
 // one).  Every index read from a table is checked against the table's size first: a corrupt table gives a row without a mask or a state that
 // stays, never a read out of range.  A finished row and a row without a guide leave gstate alone.
+//
+// The closing head (CLOSE instantiations: fo1_sample_rows_closing_bf16, fo1_decode_head_closing_accept) reads one fo1_guide_close_t per row.
+// With r = budget - c - 1 tokens still to follow this pick, a guided row with 0 <= r < depth takes close_row[close_off + s * depth + r] as its
+// state's mask row instead of state_row[row_off + s]: two more scalar table reads where the guide is resolved, nothing else.  An index outside
+// close_row keeps the plain row.
 #include "decode_common.h"
 
 namespace fo1 {
@@ -171,6 +176,7 @@ struct SampleArgs {
     const uint32_t* masks; int mask_rows; long long mask_ld_words; const fo1_token_rule_t* rules;      // ruled head: the mask table and the rows' rules
     const uint16_t* cls; int cls_rows; long long ld_cls; const int* next; long long n_next;            // guided head: token classes, transitions,
     const int* state_row; long long n_state_row; const fo1_token_guide_t* guides; int* gstate;         // state -> mask row, the rows' guides and states
+    const int* close_row; long long n_close_row; const fo1_guide_close_t* closes; const int* budget;   // closing head: (state, tokens left) -> mask row, the rows' closing rules, rows form: their budgets
 };
 
 // Key scan of the half whose counters sit in `hist` (keys key0 .. key0 + 32767), top key down.  carry_c / carry_m: tokens and mass of the
@@ -215,7 +221,7 @@ __device__ __forceinline__ void sp_key_scan(const uint32_t* hist, int key0, int 
     __syncthreads();
 }
 
-template <bool ACCEPT, bool PEN, bool RULE = false, bool GUIDE = false>
+template <bool ACCEPT, bool PEN, bool RULE = false, bool GUIDE = false, bool CLOSE = false>
 __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
     extern __shared__ __align__(16) unsigned char sp_smem[];
     uint32_t* hist = reinterpret_cast<uint32_t*>(sp_smem);
@@ -265,6 +271,14 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
                 const int gs = a.gstate[b];
                 const long long ri = (long long)G.row_off + gs;
                 row0 = gs >= 0 && ri < a.n_state_row ? a.state_row[ri] : -1;
+                if constexpr (CLOSE) {      // fewer than `depth` tokens may follow this pick: the row of (state, tokens left) instead
+                    const fo1_guide_close_t K = a.closes[b];
+                    const int left = (ACCEPT ? min(st[5], a.ids_ld) : a.budget[b]) - c - 1;
+                    if (K.depth > 0 && K.close_off >= 0 && gs >= 0 && left >= 0 && left < K.depth) {
+                        const long long ci = (long long)K.close_off + (long long)gs * K.depth + left;
+                        if (ci < a.n_close_row) row0 = a.close_row[ci];
+                    }
+                }
                 // what thread 0 needs after the pick waits in LDS, not in registers across the passes: the token's class row, the state's
                 // row of `next` and how many of its entries lie inside the table (0: the state stays)
                 const long long nb = (long long)G.next_off + (long long)gs * G.n_classes;
@@ -504,13 +518,14 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
 
 constexpr size_t SP_WORKSPACE = 256;      // the one-workgroup-per-row kernel keeps everything in LDS; the argument stays for a split form
 
-template <bool ACCEPT, bool PEN, bool RULE = false, bool GUIDE = false>
+template <bool ACCEPT, bool PEN, bool RULE = false, bool GUIDE = false, bool CLOSE = false>
 static int launch_sample(const SampleArgs& a, int B, hipStream_t st) {
-    FO1_DYNAMIC_LDS_ONCE(SP_SMEM, sample_rows_kernel<ACCEPT, PEN, RULE, GUIDE>);
-    FO1_LAUNCH(GUIDE ? (ACCEPT ? "head_guided_accept" : "sample_rows_guided")
+    FO1_DYNAMIC_LDS_ONCE(SP_SMEM, sample_rows_kernel<ACCEPT, PEN, RULE, GUIDE, CLOSE>);
+    FO1_LAUNCH(CLOSE ? (ACCEPT ? "head_closing_accept" : "sample_rows_closing")
+               : GUIDE ? (ACCEPT ? "head_guided_accept" : "sample_rows_guided")
                : RULE ? (ACCEPT ? "head_ruled_accept" : "sample_rows_ruled")
                       : PEN ? (ACCEPT ? "head_accept" : "sample_rows_seen") : (ACCEPT ? "sample_accept" : "sample_rows"),
-               (double)B * a.V * 2.0, (sample_rows_kernel<ACCEPT, PEN, RULE, GUIDE>), dim3(B), dim3(SP_NT), SP_SMEM, st, a);
+               (double)B * a.V * 2.0, (sample_rows_kernel<ACCEPT, PEN, RULE, GUIDE, CLOSE>), dim3(B), dim3(SP_NT), SP_SMEM, st, a);
     return FO1_OK;
 }
 
@@ -546,6 +561,12 @@ static int check_guides(const char* who, const void* masks, const void* rules, c
     FO1_CHECK_ARG(cls_rows > 0 && ld_cls >= V, "%s: cls_rows=%d ld_cls=%lld (>= 1 rows of >= n_vocab = %d classes)", who, cls_rows, ld_cls, V);
     FO1_CHECK_ARG(n_next > 0 && n_state_row > 0, "%s: n_next=%lld n_state_row=%lld (>= 1 each)", who, n_next, n_state_row);
     FO1_CHECK_ARG(((uintptr_t)cls & 1) == 0 && (((uintptr_t)next | (uintptr_t)state_row | (uintptr_t)gstate) & 3) == 0, "%s: misaligned guide table", who);
+    return FO1_OK;
+}
+
+static int check_closes(const char* who, const void* close_row, long long n_close_row, const void* closes) {
+    FO1_CHECK_ARG(close_row && n_close_row > 0, "%s: closing rules with close_row=%p n_close_row=%lld (a table of >= 1 entries)", who, close_row, n_close_row);
+    FO1_CHECK_ARG((((uintptr_t)close_row | (uintptr_t)closes) & 3) == 0, "%s: misaligned closing table", who);
     return FO1_OK;
 }
 
@@ -712,6 +733,69 @@ int fo1_decode_head_guided_accept(const void* logits, long long ld_logits, int n
     a.cls = cls; a.cls_rows = cls_rows; a.ld_cls = ld_cls; a.next = (const int*)next; a.n_next = n_next; a.state_row = (const int*)state_row;
     a.n_state_row = n_state_row; a.guides = guides; a.gstate = (int*)gstate;
     return launch_sample<true, true, true, true>(a, B, (hipStream_t)stream);
+}
+
+// fo1_sample_rows_guided_bf16 with the rows' closing rules honoured (the head of this file; include/fo1.h): a guided row b with fewer than
+// closes[b].depth tokens left of budget[b] picks behind the mask row of (state, tokens left).  closes == NULL: fo1_sample_rows_guided_bf16.
+int fo1_sample_rows_closing_bf16(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params, const int32_t* counter,
+                                 int counter_stride, const float* u, int32_t* out, void* workspace, size_t workspace_bytes, const uint32_t* seen,
+                                 long long ld_words, const uint32_t* masks, int mask_rows, long long mask_ld_words, const fo1_token_rule_t* rules,
+                                 void* stream, const uint16_t* cls, int cls_rows, long long ld_cls, const int32_t* next, long long n_next,
+                                 const int32_t* state_row, long long n_state_row, const fo1_token_guide_t* guides, int32_t* gstate,
+                                 const int32_t* close_row, long long n_close_row, const fo1_guide_close_t* closes, const int32_t* budget) {
+    using namespace fo1;
+    if (!closes)
+        return fo1_sample_rows_guided_bf16(logits, ld_logits, n_vocab, B, params, counter, counter_stride, u, out, workspace, workspace_bytes, seen, ld_words,
+                                           masks, mask_rows, mask_ld_words, rules, stream, cls, cls_rows, ld_cls, next, n_next, state_row, n_state_row,
+                                           guides, gstate);
+    FO1_CHECK_ARG(guides != nullptr, "sample_rows_closing: closing rules need the rows' guides");
+    if (int rc = check_sample("sample_rows_closing", logits, ld_logits, n_vocab, B, params, workspace, workspace_bytes)) return rc;
+    if (int rc = check_seen("sample_rows_closing", seen, ld_words, n_vocab)) return rc;
+    if (int rc = check_masks("sample_rows_closing", masks, mask_rows, mask_ld_words, n_vocab)) return rc;
+    if (int rc = check_guides("sample_rows_closing", masks, rules, cls, cls_rows, ld_cls, next, n_next, state_row, n_state_row, gstate, n_vocab)) return rc;
+    if (int rc = check_closes("sample_rows_closing", close_row, n_close_row, closes)) return rc;
+    FO1_CHECK_ARG(out != nullptr, "sample_rows_closing: NULL out");
+    FO1_CHECK_ARG(budget && ((uintptr_t)budget & 3) == 0, "sample_rows_closing: closing rules need the rows' budgets (device int32 [B])");
+    SampleArgs a{};
+    a.logits = (const uint16_t*)logits; a.ld = ld_logits; a.V = n_vocab; a.params = params; a.counter = (const int*)counter;
+    a.counter_stride = counter_stride; a.u = u; a.out = (int*)out; a.seen = const_cast<uint32_t*>(seen); a.ld_words = ld_words;
+    a.masks = masks; a.mask_rows = mask_rows; a.mask_ld_words = mask_ld_words; a.rules = rules;
+    a.cls = cls; a.cls_rows = cls_rows; a.ld_cls = ld_cls; a.next = (const int*)next; a.n_next = n_next; a.state_row = (const int*)state_row;
+    a.n_state_row = n_state_row; a.guides = guides; a.gstate = (int*)gstate;
+    a.close_row = (const int*)close_row; a.n_close_row = n_close_row; a.closes = closes; a.budget = (const int*)budget;
+    return launch_sample<false, true, true, true, true>(a, B, (hipStream_t)stream);
+}
+
+// fo1_decode_head_guided_accept with the rows' closing rules honoured: tokens left = min(state[b][5], ids_ld) - state[b][4] - 1.  The step
+// reads close_row and closes, it never writes them.  closes == NULL: fo1_decode_head_guided_accept.
+int fo1_decode_head_closing_accept(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params, int32_t* state,
+                                   int32_t* plan, int32_t* ids_out, int ids_ld, const int32_t* stop_ids, int n_stop, int32_t* done, void* workspace,
+                                   size_t workspace_bytes, uint32_t* seen, long long ld_words, const uint32_t* masks, int mask_rows,
+                                   long long mask_ld_words, const fo1_token_rule_t* rules, void* stream, const uint16_t* cls, int cls_rows,
+                                   long long ld_cls, const int32_t* next, long long n_next, const int32_t* state_row, long long n_state_row,
+                                   const fo1_token_guide_t* guides, int32_t* gstate, const int32_t* close_row, long long n_close_row,
+                                   const fo1_guide_close_t* closes) {
+    using namespace fo1;
+    if (!closes)
+        return fo1_decode_head_guided_accept(logits, ld_logits, n_vocab, B, params, state, plan, ids_out, ids_ld, stop_ids, n_stop, done, workspace,
+                                             workspace_bytes, seen, ld_words, masks, mask_rows, mask_ld_words, rules, stream, cls, cls_rows, ld_cls, next,
+                                             n_next, state_row, n_state_row, guides, gstate);
+    FO1_CHECK_ARG(guides != nullptr, "decode_head_closing_accept: closing rules need the rows' guides");
+    if (int rc = check_sample("decode_head_closing_accept", logits, ld_logits, n_vocab, B, params, workspace, workspace_bytes)) return rc;
+    if (int rc = check_seen("decode_head_closing_accept", seen, ld_words, n_vocab)) return rc;
+    if (int rc = check_masks("decode_head_closing_accept", masks, mask_rows, mask_ld_words, n_vocab)) return rc;
+    if (int rc = check_guides("decode_head_closing_accept", masks, rules, cls, cls_rows, ld_cls, next, n_next, state_row, n_state_row, gstate, n_vocab)) return rc;
+    if (int rc = check_closes("decode_head_closing_accept", close_row, n_close_row, closes)) return rc;
+    FO1_CHECK_ARG(state && plan && ids_out && done && ids_ld > 0 && n_stop >= -1 && (n_stop == 0 || stop_ids), "decode_head_closing_accept: bad arguments");
+    SampleArgs a{};
+    a.logits = (const uint16_t*)logits; a.ld = ld_logits; a.V = n_vocab; a.params = params;
+    a.state = (int*)state; a.plan = (int*)plan; a.ids_out = (int*)ids_out; a.ids_ld = ids_ld; a.stop_ids = (const int*)stop_ids; a.n_stop = n_stop;
+    a.done = (int*)done; a.seen = seen; a.ld_words = ld_words;
+    a.masks = masks; a.mask_rows = mask_rows; a.mask_ld_words = mask_ld_words; a.rules = rules;
+    a.cls = cls; a.cls_rows = cls_rows; a.ld_cls = ld_cls; a.next = (const int*)next; a.n_next = n_next; a.state_row = (const int*)state_row;
+    a.n_state_row = n_state_row; a.guides = guides; a.gstate = (int*)gstate;
+    a.close_row = (const int*)close_row; a.n_close_row = n_close_row; a.closes = closes;
+    return launch_sample<true, true, true, true, true>(a, B, (hipStream_t)stream);
 }
 
 // Sets bit ids[i] of row rows[i] of the seen bitmap for i < n (device int32 each; duplicates are fine).  Ids outside [0, n_vocab) and negative

@@ -13,6 +13,7 @@ from typing import Iterable, List, Optional, Sequence
 import numpy as np
 
 OUT, LABEL0, LABEL, OPEN, OBJ0, OBJ = range(6)      # the states of region_answer
+INF = int(np.iinfo(np.int32).max)                   # distances(): no path to an accepting state
 
 
 def _words(V: int) -> int:
@@ -42,10 +43,14 @@ class TokenGuide:
     for a class that next bans; a guide with a walk table starts a sequence in run(prompt ids) instead of `start` (ban_sequences), and any of
     its states may be the first one.
     ValueError: shapes that do not match, a class outside [0, C), an entry of next >= S, a start state outside [0, S), or a state the guide can
-    reach whose banned set is all V tokens."""
-    __slots__ = ("V", "S", "C", "start", "cls", "next", "walk", "_key", "_hash", "_banned")
+    reach whose banned set is all V tokens.
+    accept (optional, an iterable of states): the ACCEPTING states — an answer is closed when its guide is in one of them.  A guide with
+    accepting states closes before the sequence's token budget runs out (closing_bitmaps; DESIGN.md section 14, "budget-aware guides");
+    None is a guide without the rule, with the key, the hash and the tables it has without the keyword.  ValueError: a state outside
+    [0, S), or no state at all."""
+    __slots__ = ("V", "S", "C", "start", "cls", "next", "walk", "accept", "_key", "_hash", "_banned")
 
-    def __init__(self, cls, next, start: int, V: int, walk=None):
+    def __init__(self, cls, next, start: int, V: int, walk=None, accept=None):
         V = int(V)
         c = np.asarray(cls)
         n = np.asarray(next)
@@ -76,7 +81,19 @@ class TokenGuide:
                 raise ValueError(f"TokenGuide: walk has shape {w.shape} or an entry outside [0, {S})")
             w.setflags(write=False)
             self.walk = w
+        self.accept = None
+        if accept is not None:
+            acc = []
+            for a in accept:
+                if isinstance(a, (bool, float)) or not hasattr(a, "__index__") or not 0 <= int(a) < S:
+                    raise ValueError(f"TokenGuide: accepting state {a!r} outside [0, {S})")
+                acc.append(int(a))
+            if not acc:
+                raise ValueError("TokenGuide: accept names no state (None = a guide without accepting states)")
+            self.accept = tuple(sorted(set(acc)))
         self._key = (V, S, C, self.start, self.cls.tobytes(), self.next.tobytes(), None if self.walk is None else self.walk.tobytes())
+        if self.accept is not None:
+            self._key += (self.accept,)
         self._hash = hash(self._key)
         self._banned: dict = {}
         for s in self.reachable():
@@ -90,7 +107,7 @@ class TokenGuide:
         return self._hash
 
     def __repr__(self):
-        return f"TokenGuide(V={self.V}, S={self.S}, C={self.C}, start={self.start})"
+        return f"TokenGuide(V={self.V}, S={self.S}, C={self.C}, start={self.start}{'' if self.accept is None else f', accept={list(self.accept)}'})"
 
     @property
     def from_prompt(self) -> bool:
@@ -165,35 +182,125 @@ class TokenGuide:
             self._banned[("fold", always)] = out
         return list(out)
 
+    def distances(self, always: Optional[bytes] = None) -> np.ndarray:
+        """int64 [S]: the smallest number of tokens that lead from each state to an accepting one, over the classes that have a token the
+        sequence's always-bans leave; 0 for an accepting state, INF for a state without a path (every state of a guide without accepting
+        states)."""
+        out = self._banned.get(("dist", always))
+        if out is None:
+            out = np.full(self.S, INF, dtype=np.int64)
+            if self.accept is not None:
+                ok = np.zeros(self.C, dtype=bool)
+                ok[self.cls[~unpack_bits(always, self.V)]] = True
+                out[list(self.accept)] = 0
+                d, grew = 0, True
+                while grew:      # breadth first from the accepting states, backwards: level d + 1 = a state with an edge into level d
+                    near = out <= d
+                    step = ((self.next >= 0) & ok[None, :] & near[np.maximum(self.next, 0)]).any(axis=1) & ~near
+                    out[step] = d + 1
+                    grew = bool(step.any())
+                    d += 1
+            out.setflags(write=False)
+            self._banned[("dist", always)] = out
+        return out
+
+    def depth(self, always: Optional[bytes] = None) -> int:
+        """D: the largest finite distance among the states the guide can reach — from D tokens left on, the closing rule bans nothing a
+        sequence that check_pickable passed could take (0 for a guide without accepting states)."""
+        d = self.distances(always)[self.reachable()]
+        d = d[d < INF]
+        return int(d.max()) if d.size else 0
+
+    def closing_mask(self, s: int, r: int, always: Optional[bytes] = None) -> np.ndarray:
+        """bool [V]: the banned set of state s at a pick that r tokens may still follow — { t : next[s][cls[t]] < 0 or
+        dist[next[s][cls[t]]] > r }, with the sequence's always-bans folded in."""
+        n = self.next[int(s)][self.cls]
+        return (n < 0) | (self.distances(always)[np.maximum(n, 0)] > int(r)) | unpack_bits(always, self.V)
+
+    def closing_bitmaps(self, always: Optional[bytes] = None):
+        """-> (D, rows): rows[s][r], 0 <= r < D, is closing_mask(s, r, always) as a bitmap in the seen bitmap's layout (None = nothing
+        banned); for r >= D the head reads the state's plain row (state_bitmaps), which holds the same set for every state that leads to no
+        state without a path — check_pickable refuses a sequence that could enter one.  rows is None for a guide without accepting states
+        and when D == 0."""
+        if self.accept is None:
+            return 0, None
+        out = self._banned.get(("close", always))
+        if out is None:
+            D = self.depth(always)
+            rows = None
+            if D > 0:
+                rows = []
+                for s in range(self.S):
+                    ms = [self.closing_mask(s, r, always) for r in range(D)]
+                    rows.append(tuple(pack_bits(m) if m.any() else None for m in ms))
+                rows = tuple(rows)
+            out = self._banned[("close", always)] = (D, rows)
+        return out
+
     def check_pickable(self, s0: int, always: Optional[bytes] = None, early: Optional[bytes] = None, until: int = 0,
-                       first: Optional[bytes] = None, c0: int = 0) -> None:
+                       first: Optional[bytes] = None, c0: int = 0, budget: Optional[int] = None) -> None:
         """ValueError when the sequence can reach a pick with nothing left: it starts in state s0 with c0 tokens generated; the pick after c
-        tokens bans the state's set, `always`, `early` while c < until and `first` while c == 0 (llm.TokenRule)."""
+        tokens bans the state's set, `always`, `early` while c < until and `first` while c == 0 (llm.TokenRule).
+        budget (N, for a guide with accepting states; None = no closing rule): the pick after c tokens, which r = N - c - 1 tokens may
+        follow, also bans every token whose next state is more than r tokens from an accepting one (closing_mask), and a start further than
+        N - c0 tokens from one is a ValueError, and so is a token the sequence may take into a state without a path to one.  The walk runs over (state, min(c, cap), min(r, D)): c and r are exact while c < cap or
+        r < D, and the picks between (c >= cap and r >= D, all alike) are one node per state, left for r = D - 1 from every state they
+        reach."""
         V = self.V
         a, e, f = (unpack_bits(m, V) for m in (always, early, first))
         until = int(until) if early is not None else 0
+        s0, c0 = int(s0), int(c0)
+        N = D = None
+        if budget is not None and self.accept is not None:
+            N, D = int(budget), self.depth(always)
+            dist = self.distances(always)
+            if dist[s0] > max(N - c0, 0):
+                far = "no path" if dist[s0] >= INF else f"{int(dist[s0])} tokens"
+                raise ValueError(f"token guide: state {s0} after {c0} generated tokens is {far} from an accepting state, the budget of {N} "
+                                 f"tokens leaves {max(N - c0, 0)}")
+            if N - c0 <= 0:
+                return
 
         def avail(ban):      # bool [C]: the class has a token outside `ban`
             p = np.zeros(self.C, dtype=bool)
             p[self.cls[~ban]] = True
             return p
 
-        phases = {}
         cap = max(until, 1)      # counts from `cap` on are alike
-        seen, todo = set(), [(int(s0), min(int(c0), cap))]
+        MID = -1                 # the node of every count c >= cap with (under a budget) r >= D
+
+        def node(c):
+            return c if c < cap or (N is not None and N - 1 - c < D) else MID
+
+        phases = {}
+        seen, todo = set(), [(s0, node(c0))]
         while todo:
             s, c = todo.pop()
             if (s, c) in seen:
                 continue
             seen.add((s, c))
-            ph = (c == 0, c < until)
+            ph = (c == 0, c != MID and c < until)
             if ph not in phases:
                 phases[ph] = avail(a | (f if ph[0] else False) | (e if ph[1] else False))
             ok = (self.next[s] >= 0) & phases[ph]
+            r = None if N is None or c == MID else N - 1 - c
+            if r is not None and r < D:
+                ok &= dist[np.maximum(self.next[s], 0)] <= r
+            elif N is not None and (dist[self.next[s][ok]] >= INF).any():      # (from D tokens left on the head reads the state's plain row)
+                raise ValueError(f"token guide: in state {s} the guide and the sequence's token rule allow a token into state "
+                                 f"{int(self.next[s][ok][dist[self.next[s][ok]] >= INF][0])}, from which no path leads to an accepting state")
             if not ok.any():
-                raise ValueError(f"token guide: in state {s} after {c}{'+' if c == cap else ''} generated tokens the guide and the sequence's "
-                                 f"token rule together ban all {V} tokens")
-            todo += [(int(n), min(c + 1, cap)) for n in self.next[s][ok]]
+                at = f"{cap}+" if c == MID else f"{c}"
+                left = "" if N is None else f" with {f'{D}+' if r is None else r} tokens left of a budget of {N}"
+                raise ValueError(f"token guide: in state {s} after {at} generated tokens{left} the guide{'' if N is None else ', its closing rule'} "
+                                 f"and the sequence's token rule together ban all {V} tokens")
+            if c == MID:
+                nxt = [MID] if N is None or N - D - cap >= 2 else []
+                if N is not None and D >= 1:
+                    nxt.append(N - D)
+            else:
+                nxt = [node(c + 1)] if N is None or c + 1 <= N - 1 else []
+            todo += [(int(n), k) for n in self.next[s][ok] for k in nxt]
 
 
 def _ids(ids, V: int, what: str) -> List[int]:
@@ -206,7 +313,7 @@ def _ids(ids, V: int, what: str) -> List[int]:
 
 
 def region_answer(V: int, ground: int, ground_end: int, objects: int, objects_end: int, region_ids: Sequence[int], n_regions: int,
-                  stop_ids: Sequence[int]) -> TokenGuide:
+                  stop_ids: Sequence[int], close: bool = False) -> TokenGuide:
     """The FO1 answer language `<ground>label</ground><objects><region3><region7></objects>` with region indices below n_regions;
     region_ids[k] is the id of `<regionk>`.  States (OUT is the start):
       OUT     anything but </ground>, <objects>, </objects> and region_ids[n_regions:]; stop ids allowed; <ground> -> LABEL0
@@ -215,7 +322,8 @@ def region_answer(V: int, ground: int, ground_end: int, objects: int, objects_en
       OPEN    only <objects> -> OBJ0
       OBJ0    only region_ids[:n_regions] -> OBJ
       OBJ     region_ids[:n_regions]; </objects> -> OUT
-    Every region id has a class of its own, so guides that differ in n_regions only share their class map."""
+    Every region id has a class of its own, so guides that differ in n_regions only share their class map.
+    close=True: OUT is the accepting state — the answer closes its structure before the sequence's token budget runs out."""
     V = int(V)
     regions = _ids(region_ids, V, "region_answer: region_ids")
     struct = _ids([ground, ground_end, objects, objects_end], V, "region_answer: a structural id")
@@ -249,7 +357,7 @@ def region_answer(V: int, ground: int, ground_end: int, objects: int, objects_en
     nx[OBJ, OE] = OUT
     if len(named) >= V:
         raise ValueError("region_answer: the vocabulary has no plain token left for a label")
-    return TokenGuide(cls, nx, OUT, V)
+    return TokenGuide(cls, nx, OUT, V, accept=(OUT,) if close else None)
 
 
 def ban_sequences(words: Sequence[Sequence[int]], V: int) -> TokenGuide:

@@ -289,6 +289,15 @@ SIGNATURES = {
     "fo1_decode_head_guided_accept": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                               c_void_p, c_void_p, c_size_t, c_void_p, c_longlong, c_void_p, c_int, c_longlong, c_void_p, c_void_p,
                                               c_void_p, c_int, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p]),
+    # the _guided entries' lists + (close_row, n_close_row, closes) and, in the rows form, budget
+    "fo1_sample_rows_closing_bf16": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
+                                             c_longlong, c_void_p, c_int, c_longlong, c_void_p, c_void_p,
+                                             c_void_p, c_int, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p,
+                                             c_void_p, c_longlong, c_void_p, c_void_p]),
+    "fo1_decode_head_closing_accept": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                               c_void_p, c_void_p, c_size_t, c_void_p, c_longlong, c_void_p, c_int, c_longlong, c_void_p, c_void_p,
+                                               c_void_p, c_int, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p,
+                                               c_void_p, c_longlong, c_void_p]),
     "fo1_logprob_rows_bf16": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
     "fo1_decode_logprob_record": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p]),

@@ -869,25 +869,45 @@ class TokenMasks:
 class GuidePlan(NamedTuple):
     """What a guided sequence asks of the tables: its guide, the always-bans of its token rule (folded into every state's bitmap: the head
     reads the state's mask row in always_row's place), the resulting bitmap of every state (None = nothing banned), the state its first token
-    is picked in, and — when the caller picked the first token on the device — the device int32 word holding the state after it."""
+    is picked in, and — when the caller picked the first token on the device — the device int32 word holding the state after it.
+    A guide with accepting states adds its closing rule (guide.closing_bitmaps): depth = D > 0 and closing = the S * D bitmaps of (state s,
+    r < D tokens left), entry s * D + r.  A (state, tokens left) pair no checked sequence can be in — more than r + 1 tokens from an accepting
+    state, every token banned — holds the state's plain bitmap instead, so it costs no mask row of its own."""
     guide: TokenGuide
     always: Optional[bytes]
     bitmaps: tuple
     s0: int
     after_first: Optional[torch.Tensor]
+    depth: int = 0
+    closing: Optional[tuple] = None
 
     @property
     def key(self):
         return (self.guide, self.always)
 
 
-def sampling_guides(sampling, B: int, V: int, trules: Sequence[Optional[TokenRule]], prompt_ids=None) -> List[Optional[GuidePlan]]:
+def guide_plan(g: TokenGuide, always: Optional[bytes], s0: int, after_first=None) -> GuidePlan:
+    """The GuidePlan of a sequence with guide g and always-bans `always` that picks its first token in state s0."""
+    plain = tuple(g.state_bitmaps(always))
+    D, rows = g.closing_bitmaps(always)
+    if rows is None:
+        return GuidePlan(g, always, plain, s0, after_first)
+    dist = g.distances(always)
+    closing = tuple(plain[s] if dist[s] > r + 1 else rows[s][r] for s in range(g.S) for r in range(D))
+    return GuidePlan(g, always, plain, s0, after_first, D, closing)
+
+
+def sampling_guides(sampling, B: int, V: int, trules: Sequence[Optional[TokenRule]], prompt_ids=None,
+                    budget: Optional[int] = None) -> List[Optional[GuidePlan]]:
     """sampling_table's argument -> the GuidePlan (or None) of every sequence; trules: sampling_rules' result for the same argument.
     A sequence's `guide` key holds a TokenGuide over V tokens; a guide built by ban_sequences starts in guide.run(prompt ids), so it needs
     prompt_ids.  The optional key `guide_state` holds a device int32 tensor of one element, the state after the first token, when the caller
     picked that token with the guided head (FO1Engine._first_tokens).  ValueError: not a TokenGuide, another vocabulary size, or a state the
     sequence can reach in which the guide and its token rule together leave nothing to pick (a guide whose only exit is a stop id that
-    ban_until still bans is one such case)."""
+    ban_until still bans is one such case).
+    budget: the sequences' effective token budget N (max_new_tokens, capped by the ids the decoder keeps).  A guide with accepting states
+    closes under it (guide.closing_bitmaps); a start state more than N tokens from an accepting one, or a pick at which the guide, its
+    closing rule and the token rule leave nothing, is a ValueError.  Without a budget such a guide is a ValueError too."""
     out = []
     for b, sp in enumerate(_per_sequence(sampling, B)):
         if not has_guide(sp):
@@ -906,11 +926,13 @@ def sampling_guides(sampling, B: int, V: int, trules: Sequence[Optional[TokenRul
             s0 = g.start
         t = trules[b]
         always = t.always if t is not None else None
+        if g.accept is not None and budget is None:
+            raise ValueError("guide: a guide with accepting states needs the sequence's token budget")
         if t is None:
-            g.check_pickable(s0)
+            g.check_pickable(s0, budget=budget)
         else:
-            g.check_pickable(s0, t.always, t.early, t.until, t.first)
-        out.append(GuidePlan(g, always, tuple(g.state_bitmaps(always)), s0, sp.get("guide_state")))
+            g.check_pickable(s0, t.always, t.early, t.until, t.first, budget=budget)
+        out.append(guide_plan(g, always, s0, sp.get("guide_state")))
     return out
 
 
@@ -984,21 +1006,26 @@ class GuideTables:
     (of the decoder's TokenMasks) holding each state's banned set.  Content-keyed sharing with user counts: equal class maps share a row, equal
     transition tables a span, equal (guide, always-bans) pairs everything — region_answer guides for different n_regions share their class
     row — and states with equal banned sets share mask rows within and across guides, since the bitmaps are acquired through TokenMasks.
-    A row or span with users is never rewritten.  The step reads all three and writes none.  Allocated by the first guided sequence."""
+    A row or span with users is never rewritten.  The step reads all three and writes none.  Allocated by the first guided sequence.
+    A fourth table, close_row int32 [N_CLOSE_ROW], names the mask row of every (state, tokens left) of a plan with a closing rule (S * D
+    entries, include/fo1.h fo1_guide_close_t); a (guide, always-bans) pair shares its span, and its bitmaps go through TokenMasks too."""
     CLS_ROWS = 64
     N_NEXT = 1 << 14
     N_STATE_ROW = 1 << 10
+    N_CLOSE_ROW = 1 << 12
 
     def __init__(self, n_vocab: int, dev, masks: Optional[TokenMasks]):
         """dev = None: the bookkeeping alone, without device tables — what room() and new_bitmaps() answer from before anything is allocated."""
         self.masks = masks
-        self.cls = self.next = self.state_row = None
+        self.cls = self.next = self.state_row = self.close_row = None
         if dev is not None:
             with torch.inference_mode(False):
                 self.cls = torch.zeros(self.CLS_ROWS, int(n_vocab), dtype=torch.int16, device=dev)
                 self.next = torch.full((self.N_NEXT,), -1, dtype=torch.int32, device=dev)
                 self.state_row = torch.full((self.N_STATE_ROW,), -1, dtype=torch.int32, device=dev)
+                self.close_row = torch.full((self.N_CLOSE_ROW,), -1, dtype=torch.int32, device=dev)
         self._cls, self._next, self._sr = _Spans(self.CLS_ROWS), _Spans(self.N_NEXT), _Spans(self.N_STATE_ROW)
+        self._cr = _Spans(self.N_CLOSE_ROW)
         self.live: Dict[tuple, dict] = {}      # GuidePlan.key -> dict(users, row = the fo1_token_guide_t fields, mask_rows)
         self._keep: list = []
 
@@ -1009,14 +1036,17 @@ class GuideTables:
 
     def new_bitmaps(self, plans: Sequence[Optional[GuidePlan]]) -> list:
         """The state bitmaps the plans would acquire mask rows for (those of pairs that are not live yet)."""
-        return [m for p in {q.key: q for q in plans if q is not None}.values() if p.key not in self.live for m in p.bitmaps if m is not None]
+        return [m for p in {q.key: q for q in plans if q is not None}.values() if p.key not in self.live
+                for m in p.bitmaps + (p.closing or ()) if m is not None]
 
     def room(self, plans: Sequence[Optional[GuidePlan]]) -> bool:
-        """Is there a class row, a transition span and a state-row span for every plan?  (The mask rows: TokenMasks.room over new_bitmaps.)"""
+        """Is there a class row, a transition span, a state-row span and (for a closing rule) a close-row span for every plan?  (The mask
+        rows: TokenMasks.room over new_bitmaps.)"""
         new = [p for p in {q.key: q for q in plans if q is not None}.values() if p.key not in self.live]
         ks = [self._keys(p) for p in new]
         return (self._cls.room([(k[0], 1) for k in ks]) and self._next.room([(k[1], p.guide.S * p.guide.C) for k, p in zip(ks, new)])
-                and self._sr.room([(k[2], p.guide.S) for k, p in zip(ks, new)]))
+                and self._sr.room([(k[2], p.guide.S) for k, p in zip(ks, new)])
+                and self._cr.room([(k[2], p.guide.S * p.depth) for k, p in zip(ks, new) if p.depth > 0]))
 
     def _upload(self, dst: torch.Tensor, host: torch.Tensor) -> None:
         dst.copy_(host, non_blocking=True)
@@ -1043,9 +1073,13 @@ class GuideTables:
                     self._upload(self.next[noff:noff + g.S * g.C], torch.from_numpy(g.next.reshape(-1).copy()))
                 roff, _ = self._sr.acquire(ks, g.S)
                 got.append((self._sr, ks))
+                coff = 0
+                if plan.depth > 0:
+                    coff, _ = self._cr.acquire(ks, g.S * plan.depth)
+                    got.append((self._cr, ks))
                 rows = []
                 try:
-                    for m in plan.bitmaps:
+                    for m in plan.bitmaps + (plan.closing or ()):
                         rows.append(-1 if m is None else self.masks.acquire(m))
                 except BaseException:
                     for r in rows:
@@ -1053,10 +1087,13 @@ class GuideTables:
                     raise
             except BaseException:
                 for sp, k in got:
-                    sp.release(k, drop=sp is self._sr)
+                    sp.release(k, drop=sp is self._sr or sp is self._cr)
                 raise
-            self._upload(self.state_row[roff:roff + g.S], torch.tensor(rows, dtype=torch.int32))
-            e = self.live[plan.key] = dict(users=0, row=(crow, g.C, noff, roff), mask_rows=rows, keys=(kc, kn, ks))
+            self._upload(self.state_row[roff:roff + g.S], torch.tensor(rows[:g.S], dtype=torch.int32))
+            if plan.depth > 0:
+                self._upload(self.close_row[coff:coff + g.S * plan.depth], torch.tensor(rows[g.S:], dtype=torch.int32))
+            e = self.live[plan.key] = dict(users=0, row=(crow, g.C, noff, roff), mask_rows=rows, keys=(kc, kn, ks),
+                                           close=(coff, plan.depth) if plan.depth > 0 else None)
         e["users"] += 1
         return e["row"]
 
@@ -1071,13 +1108,23 @@ class GuideTables:
             self._cls.release(kc)
             self._next.release(kn)
             self._sr.release(ks, drop=True)
+            if e["close"] is not None:
+                self._cr.release(ks, drop=True)
             del self.live[key]
 
     def users(self) -> int:
         return sum(e["users"] for e in self.live.values())
 
-    def operands(self, guides: torch.Tensor, gstate: torch.Tensor) -> "ops.GuideOperands":
-        return ops.GuideOperands(self.cls, self.next, self.state_row, guides, gstate)
+    def close_of(self, key) -> Optional[tuple]:
+        """(close_off, depth) of a live plan: its fo1_guide_close_t fields; None without a closing rule."""
+        return self.live[key]["close"]
+
+    def operands(self, guides: torch.Tensor, gstate: torch.Tensor, closes: Optional[torch.Tensor] = None,
+                 budget: Optional[torch.Tensor] = None) -> "ops.GuideOperands":
+        """closes (ops.guide_closes): the closing form, with the rows' budgets in the rows form."""
+        if closes is None:
+            return ops.GuideOperands(self.cls, self.next, self.state_row, guides, gstate)
+        return ops.GuideOperands(self.cls, self.next, self.state_row, guides, gstate, self.close_row, closes, budget)
 
     def pointers(self) -> tuple:
         return self.cls.data_ptr(), self.next.data_ptr(), self.state_row.data_ptr()
@@ -1093,7 +1140,7 @@ class PassTables:
         self.masks, self.gtab = masks, gtab
         self._rows: List[int] = []
         self._keys: list = []
-        self.rules, self.guides = [], None
+        self.rules, self.guides, self.closes = [], None, None      # closes: the rows of ops.guide_closes, None when no guide closes
         try:
             for t in trules:
                 row, held = (None, []) if t is None else masks.rule_row(t)
@@ -1109,6 +1156,8 @@ class PassTables:
                     self.guides.append(None if g is None else gtab.acquire(g))
                     if g is not None:
                         self._keys.append(g.key)
+                if any(g is not None and g.depth > 0 for g in gplans):
+                    self.closes = [None if g is None else gtab.close_of(g.key) for g in gplans]
         except BaseException:
             self.release()
             raise
@@ -1250,6 +1299,8 @@ class BatchDecoder:
         self.gstate = None
         self.guided = False        # some row of the current start() has a guide: the general head runs in its guided form
         self._guide_keys: list = []          # guide-table entries the current start() holds
+        self.closes = None         # budget-aware guides: the per-row fo1_guide_close_t table, allocated by the first start() with a closing guide
+        self.closing = False       # some row of the current start() has a closing rule: the guided head runs in its closing form
         self.lp_want: List[int] = []       # per sequence of the current start(): -1 = no record, else its top-n
         self.n_stop = 0
         self.dk = self.dvt = None
@@ -1288,6 +1339,8 @@ class BatchDecoder:
         A dict's token-rule keys (ban, allow, ban_first, ban_until: token_rule) restrict that sequence's picks on the device; the rows of the
         mask table they take are held until the next start().  A dict's guide (guide=TokenGuide: sampling_guides) makes the banned set a
         function of the sequence's automaton state, which the head advances on the device; its table rows are held until the next start() too.
+        A guide with accepting states closes before max_new_tokens runs out (guide.closing_bitmaps): the head reads the tokens left from the
+        row's decode state; a start state further from an accepting one than the budget is a ValueError.
         logprobs (logprob_wants): None, one int or a list with None / int per sequence = the top-n of the log-probability record kept for that
         sequence (logprobs()); orthogonal to `sampling`: the record launch follows whichever head the step ends in.  first_logprobs: the first
         tokens' records, ops.logprob_rows on the prefill's logits with the largest requested n (FO1Engine._first_logprobs)."""
@@ -1322,7 +1375,7 @@ class BatchDecoder:
         self._keep = [reloc, state, stop]                 # sources of the async uploads stay alive
         srows, kinds = sampling_table(sampling, B)
         trules = sampling_rules(sampling, B, llm.cfg.vocab_size)
-        gplans = sampling_guides(sampling, B, llm.cfg.vocab_size, trules, prompt_ids)
+        gplans = sampling_guides(sampling, B, llm.cfg.vocab_size, trules, prompt_ids, budget=max_new)
         self.sampled = any(k != "plain" for k in kinds)
         self.general = self.sampled and any(k != "sampled" for k in kinds)
         penalised = any(ops.penalty_on(r[6]) for r in srows)
@@ -1365,6 +1418,7 @@ class BatchDecoder:
                 self.masks.release(r)
         self._mask_rows = []
         self.guided = any(g is not None for g in gplans)
+        self.closing = False
         self.ruled = self.guided or any(t is not None for t in trules)
         if not self.ruled:
             return
@@ -1405,11 +1459,21 @@ class BatchDecoder:
         for k, g in enumerate(gplans):
             if g is not None and g.after_first is not None:      # the caller picked the first token with the guided head: its state word
                 self.gstate[k:k + 1].copy_(g.after_first.view(1), non_blocking=True)
+        if any(g is not None and g.depth > 0 for g in gplans):      # every row's entry is written: a row without the rule gets depth 0
+            if self.closes is None:
+                with torch.inference_mode(False):
+                    self.closes = ops.guide_closes([None] * self.MAX_BATCH, self.llm.dev)
+            ct = ops.guide_closes([None if g is None else self.gtab.close_of(g.key) for g in gplans])
+            self.closes[:len(table)].copy_(ct, non_blocking=True)
+            self._keep.append(ct)
+            self.closing = True
 
     def _rule_args(self) -> dict:
         if not self.ruled:
             return {}
-        guide = dict(guide=self.gtab.operands(self.guides[:self.B], self.gstate[:self.B])) if self.guided else {}
+        guide = {}
+        if self.guided:
+            guide = dict(guide=self.gtab.operands(self.guides[:self.B], self.gstate[:self.B], self.closes[:self.B] if self.closing else None))
         return dict(masks=self.masks.table, rules=self.rules[:self.B], **guide)
 
     KV_BUCKET = 2048
@@ -1482,6 +1546,8 @@ class BatchDecoder:
             if self.guided:  # (the guided form advances the rows' automaton states: they join the rollback, or the first replay would start
                 key += ("guided", *self.gtab.pointers(), self.guides.data_ptr(), self.gstate.data_ptr())      # from the warm-up step's states)
                 seen += (self.gstate,)
+            if self.closing:  # (the closing form reads two more tables and writes neither: nothing more to roll back)
+                key += ("closing", self.gtab.close_row.data_ptr(), self.closes.data_ptr())
         if self.recording:   # (and one more: the record launch bakes the buffers' identity in, and the warm-up step writes them)
             key += ("logprobs", self.lpb.lp.data_ptr())
             seen += self.lpb.written()
@@ -1605,6 +1671,10 @@ class DecodePool:
         self.guided_dev = [False] * P                  # does the slot's guide row on the device hold a guide (tracked as `kind` is)
         self.slot_guide: list = [None] * P             # the guide-table entry a live slot holds
         self.n_guided = 0                              # live slots with a guide: > 0 runs the general head in its guided form
+        self.closes = None                             # budget-aware guides: the per-slot fo1_guide_close_t table, allocated when the first
+        self.close_dev = [False] * P                   # closing sequence joins; does the slot's row on the device hold depth > 0 (as `kind`)
+        self.slot_close = [False] * P                  # a live slot's guide has a closing rule
+        self.n_closing = 0                             # live slots with a closing rule: > 0 runs the guided head in its closing form
         self.lpb = None                                # log-probability records (LogprobBuffers), allocated when the first requesting sequence joins
         self.lp_want = [-1] * P                        # a live slot's request: -1 = no record, else its top-n
         self.lp_dev = [-1] * P                         # what each slot's `want` word on the device holds (tracked as `kind` is)
@@ -1671,6 +1741,9 @@ class DecodePool:
         advances on the device: the slot's state word is set here to the state after the first token (the dict's guide_state word when the
         caller picked that token with the guided head, else computed on the host from first_tokens — one host read), every state's bitmap
         takes a mask row (equal ones are shared, within and across guides), and the rows are released when the sequence is harvested.
+        A guide with accepting states closes before max_new_tokens runs out (guide.closing_bitmaps): its (state, tokens left) bitmaps take
+        mask rows too, the head reads the tokens left from the slot's decode state, and a start state further from an accepting one than
+        the budget is a ValueError.  While no such sequence is live the step is the guided (or ruled, or general, or greedy) one.
         logprobs / first_logprobs: as BatchDecoder.start takes them; while any live slot asks for a record the record launch follows the head
         (step()), and harvest(records=True) hands the finished slots' records out.  A pool no requesting sequence ever joined holds no
         record buffer and issues exactly the launches and copies it always has."""
@@ -1680,7 +1753,8 @@ class DecodePool:
             raise ValueError("DecodePool: logprobs needs first_logprobs, the first tokens' records")
         srows, kinds = sampling_table(sampling, B)
         trules = sampling_rules(sampling, B, self.llm.cfg.vocab_size)
-        gplans = sampling_guides(sampling, B, self.llm.cfg.vocab_size, trules, prompt_ids)
+        max_new = token_budget(max_new_tokens, self.IDS_CAP, "DecodePool")
+        gplans = sampling_guides(sampling, B, self.llm.cfg.vocab_size, trules, prompt_ids, budget=max_new)
         trules = unguided_rules(trules, gplans)
         penalised = [ops.penalty_on(r[6]) for r in srows]
         if any(penalised) and (prompt_ids is None or len(prompt_ids) != B):
@@ -1689,7 +1763,6 @@ class DecodePool:
         if full is not None:
             raise RuntimeError(f"DecodePool: {full}; wait for sequences to finish")
         set_row = self._stop_set_row(tuple(stop_id_list(stop_ids, self.MAX_STOP, "DecodePool")))
-        max_new = token_budget(max_new_tokens, self.IDS_CAP, "DecodePool")
         if B > len(self.free):
             raise RuntimeError(f"DecodePool: {B} sequences, {len(self.free)} free slots")
         if not self.fits(seqs, max_new):
@@ -1728,6 +1801,8 @@ class DecodePool:
             self.n_general += kinds[k] != "plain"
             self.n_ruled += trules[k] is not None
             self.n_guided += gplans[k] is not None
+            self.slot_close[s] = gplans[k] is not None and gplans[k].depth > 0
+            self.n_closing += self.slot_close[s]
             self.lp_want[s] = wants[k]
             self.n_logprob += wants[k] >= 0
         return slots
@@ -1751,7 +1826,7 @@ class DecodePool:
         if any(g is not None for g in gplans):      # (nothing allocated yet: the same answers from the bookkeeping alone)
             gtab = self.gtab if self.gtab is not None else GuideTables(self.llm.cfg.vocab_size, None, None)
             if not gtab.room(gplans):
-                return "the token-guide tables (class rows, transitions, state rows) are full"
+                return "the token-guide tables (class rows, transitions, state rows, closing rows) are full"
             maps += gtab.new_bitmaps(gplans)
         if not maps or (self.masks.room(maps) if self.masks is not None else len(set(maps)) <= self.MAX_MASKS):
             return None
@@ -1793,6 +1868,23 @@ class DecodePool:
             if gplans[k] is not None:
                 src = gplans[k].after_first
                 self.gstate[s:s + 1].copy_(gs[k:k + 1] if src is None else src.view(1), non_blocking=True)
+        self._join_closes(slots, gplans)
+
+    def _join_closes(self, slots, gplans):
+        """The closing rows of a submission's slots.  Nothing is enqueued for a sequence without a closing rule whose slot holds none: a slot
+        a closing sequence has left gets depth = 0 back when a sequence without the rule reuses it."""
+        closing = [g is not None and g.depth > 0 for g in gplans]
+        write = [k for k, s in enumerate(slots) if closing[k] or self.close_dev[s]]
+        if not write:
+            return
+        if self.closes is None:      # (graphs captured before are unreachable for a closing step: its key holds the table's identity)
+            with torch.inference_mode(False):
+                self.closes = ops.guide_closes([None] * self.P, self.llm.dev)
+        ct = ops.guide_closes([self.gtab.close_of(gplans[k].key) if closing[k] else None for k in write])
+        self._keep.append(ct)
+        for j, k in enumerate(write):
+            self.closes[slots[k]:slots[k] + 1].copy_(ct[j:j + 1], non_blocking=True)
+            self.close_dev[slots[k]] = closing[k]
 
     def _release_guide(self, slot: int) -> None:
         if self.slot_guide[slot] is not None:
@@ -1859,7 +1951,7 @@ class DecodePool:
                 g, always = (sp.get("guide") if sp is not None else None), (t.always if t is not None else None)
                 if g is not None and not isinstance(g, TokenGuide):
                     raise ValueError("guide: not a TokenGuide")
-                gplans.append(None if g is None else GuidePlan(g, always, tuple(g.state_bitmaps(always)), g.start, None))
+                gplans.append(None if g is None else guide_plan(g, always, g.start))
             return self._mask_room(unguided_rules(trules, gplans), gplans) or self.masks is None or not any(self.masks.users)
         except ValueError:
             return True
@@ -1950,6 +2042,8 @@ class DecodePool:
                 key += ("ruled", self.masks.table.data_ptr(), self.rules.data_ptr())
             if self.n_guided > 0:     # (the guided form advances the slots' automaton states: gstate joins the rollback in step())
                 key += ("guided", self.masks.table.data_ptr(), self.rules.data_ptr(), *self.gtab.pointers(), self.guides.data_ptr(), self.gstate.data_ptr())
+            if self.n_closing > 0:    # (the closing form reads two more tables and writes neither: nothing more joins the rollback)
+                key += ("closing", self.gtab.close_row.data_ptr(), self.closes.data_ptr())
         if self.n_logprob > 0:
             key += ("logprobs", self.lpb.lp.data_ptr())
         return key
@@ -1997,7 +2091,7 @@ class DecodePool:
             if general:      # plain slots ride as greedy rows without penalty; empty and finished slots return early, as in the greedy head
                 rule = dict(masks=self.masks.table, rules=self.rules) if self.n_ruled > 0 or self.n_guided > 0 else {}
                 if self.n_guided > 0:
-                    rule["guide"] = self.gtab.operands(self.guides, self.gstate)
+                    rule["guide"] = self.gtab.operands(self.guides, self.gstate, self.closes if self.n_closing > 0 else None)
                 ops.decode_head_accept(logits, self.sparams, st, self.plan, self.ids, self.stop, self.done, seen=self.seen, per_sequence_sets=True, **rule)
             else:
                 ops.decode_argmax_accept(logits, None, st, self.plan, self.ids, self.stop, self.done, per_sequence_sets=True)
@@ -2087,6 +2181,8 @@ class DecodePool:
                 self._release_masks(s)
                 self.n_guided -= self.slot_guide[s] is not None
                 self._release_guide(s)
+                self.n_closing -= self.slot_close[s]
+                self.slot_close[s] = False
         return out
 
     def drain(self, use_graph: bool = True, poll: int = 8, records: bool = False) -> List[tuple]:

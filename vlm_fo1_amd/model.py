@@ -528,19 +528,23 @@ class FO1Engine:
             raise ValueError(f"sampling: {len(per)} entries for {n} requests")
         return [None if sp is None else dict(sp, stream=sp.get("stream", base + i)) for i, sp in enumerate(per)]
 
-    def _first_tokens(self, per: list, requests: Sequence[dict]) -> torch.Tensor:
+    def _first_tokens(self, per: list, requests: Sequence[dict], max_new_tokens: Optional[int] = None) -> torch.Tensor:
         """The first token of every sequence of the pass that just ran, from the prefill's logits: its greedy picks when every request is
         plain; else one launch of the device sampler with counter 0 — the general head (greedy rows, penalties against the prompts' seen
         sets, marked into a scratch bitmap first) unless every row is a plain draw.  A request's token rule (llm.token_rule) goes to the ruled
         form of that head through a scratch mask table: counter 0, so its first-token and early bans apply.  A request's guide
         (llm.sampling_guides) goes to the guided form through scratch guide tables: the pick is made in the guide's start state (the prompt's
         state for a ban_sequences guide), and the device word holding the state after it is put into the request's dict as `guide_state`, which
-        BatchDecoder.start / DecodePool.join copy into their own state array — no host read."""
-        from .llm import GuideTables, PassTables, TokenMasks, new_seen, sampling_guides, sampling_rules, sampling_table, unguided_rules
+        BatchDecoder.start / DecodePool.join copy into their own state array — no host read.  A guide with accepting states
+        (guide.closing_bitmaps) goes to the closing form with budget = max_new_tokens for every row: the first pick already closes under it
+        (max_new_tokens = 1 leaves only a token after which the answer is closed); such a guide without max_new_tokens is a ValueError."""
+        from .llm import (BatchDecoder, GuideTables, PassTables, TokenMasks, new_seen, sampling_guides, sampling_rules, sampling_table,
+                          unguided_rules)
         n = len(requests)
         rows, kinds = sampling_table(per, n)
         trules = sampling_rules(per, n, self.cfg.llm.vocab_size)
-        gplans = sampling_guides(per, n, self.cfg.llm.vocab_size, trules, [r["ids"] for r in requests])
+        budget = None if max_new_tokens is None else min(max(1, int(max_new_tokens)), BatchDecoder.IDS_CAP)      # (as the decoders count it)
+        gplans = sampling_guides(per, n, self.cfg.llm.vocab_size, trules, [r["ids"] for r in requests], budget=budget)
         trules = unguided_rules(trules, gplans)
         guided = any(g is not None for g in gplans)
         if all(k == "plain" for k in kinds):
@@ -571,7 +575,11 @@ class FO1Engine:
                     rule = dict(masks=tm.table, rules=ops.token_rules(held.rules, self.dev))
                     if guided:
                         gstate = torch.tensor([0 if g is None else g.s0 for g in gplans], dtype=torch.int32).to(self.dev)
-                        rule["guide"] = gt.operands(ops.token_guides(held.guides, self.dev), gstate)
+                        close = {}
+                        if held.closes is not None:
+                            close = dict(closes=ops.guide_closes(held.closes, self.dev),
+                                         budget=torch.full((n,), budget, dtype=torch.int32).to(self.dev))
+                        rule["guide"] = gt.operands(ops.token_guides(held.guides, self.dev), gstate, **close)
                     out = ops.sample_rows(self._last_logits[:n], table, seen=seen, general=True, **rule)
                 finally:
                     held.release()
@@ -628,7 +636,7 @@ class FO1Engine:
             hp = self._last_batch
             n = len(grp)
             per = self._per_request(sampling if sampling is None or isinstance(sampling, dict) else list(sampling)[base:base + n], n, base)
-            first = self._first_tokens(per, grp)
+            first = self._first_tokens(per, grp, max_new_tokens)
             lpp = self._logprob_part(logprobs, base, base + n)
             first_lp = self._first_logprobs(lpp, first, n)
             plain = all(sp is None for sp in per)
@@ -720,7 +728,7 @@ class FO1Engine:
         logprob_wants(logprobs, len(requests))      # (a bad request fails before the prefill)
         self.prefill_batch(requests, use_graph=use_graph)
         hp = self._last_batch
-        first = self._first_tokens(per, requests)
+        first = self._first_tokens(per, requests, max_new_tokens)
         first_lp = self._first_logprobs(logprobs, first, len(requests))
         lpa = {} if first_lp is None else dict(logprobs=logprobs, first_logprobs=first_lp)
         if all(sp is None for sp in per):

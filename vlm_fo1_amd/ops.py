@@ -1060,15 +1060,31 @@ def token_guides(rows: Sequence, device=None) -> torch.Tensor:
     return tab if device is None else tab.to(device)
 
 
+NO_CLOSE = (0, 0, 0, 0)        # fo1_guide_close_t of a row without a closing rule (depth 0)
+
+
+def guide_closes(rows: Sequence, device=None) -> torch.Tensor:
+    """The fo1_guide_close_t table (int32 [B, 4]) from rows of (close_off, depth) — the guide's offset into the `close_row` table and its depth D
+    (include/fo1.h) — or None for a row without a closing rule.  On `device` when given, else a host tensor."""
+    tab = torch.tensor([list(NO_CLOSE) if r is None else [int(r[0]), int(r[1]), 0, 0] for r in rows], dtype=torch.int32).view(-1, 4)
+    return tab if device is None else tab.to(device)
+
+
 class GuideOperands(NamedTuple):
     """What a guided head takes besides masks and rules (include/fo1.h): cls int16 [rows, ld_cls >= V] holding the uint16 token classes, next
     int32 [n_next], state_row int32 [n_state_row] (mask-table row of every state, -1 = nothing banned), guides (token_guides, int32 [>= B, 4])
-    and gstate int32 [>= B], the rows' automaton states — the one table the head writes."""
+    and gstate int32 [>= B], the rows' automaton states — the one table the head writes.
+    closes (guide_closes, int32 [>= B, 4]) with close_row int32 [n_close_row] (mask-table row of every (state, tokens left)): the closing
+    head (fo1_sample_rows_closing_bf16 / fo1_decode_head_closing_accept); budget int32 [>= B]: the rows' token budgets, which the rows form
+    needs (the accept form reads them from the decode state)."""
     cls: torch.Tensor
     next: torch.Tensor
     state_row: torch.Tensor
     guides: torch.Tensor
     gstate: torch.Tensor
+    close_row: Optional[torch.Tensor] = None
+    closes: Optional[torch.Tensor] = None
+    budget: Optional[torch.Tensor] = None
 
 
 def _guide_operands(g: GuideOperands, B: int, V: int):
@@ -1079,6 +1095,21 @@ def _guide_operands(g: GuideOperands, B: int, V: int):
     assert g.guides.shape[0] >= B and g.gstate.numel() >= B
     return (g.cls.data_ptr(), g.cls.shape[0], g.cls.shape[1], g.next.data_ptr(), g.next.numel(), g.state_row.data_ptr(), g.state_row.numel(),
             g.guides.data_ptr(), g.gstate.data_ptr())
+
+
+def _close_operands(g: GuideOperands, B: int, rows_form: bool):
+    assert g.close_row is not None, "a closing head takes close_row and closes together"
+    t = g.close_row
+    assert t.dtype == torch.int32 and t.is_cuda and t.dim() == 1 and t.is_contiguous() and t.numel() >= 1
+    assert g.closes.dtype == torch.int32 and g.closes.is_cuda and g.closes.dim() == 2 and g.closes.shape[1] == 4 and g.closes.is_contiguous()
+    assert g.closes.shape[0] >= B
+    out = (t.data_ptr(), t.numel(), g.closes.data_ptr())
+    if rows_form:
+        b = g.budget
+        assert b is not None, "the rows form of the closing head takes the rows' budgets"
+        assert b.dtype == torch.int32 and b.is_cuda and b.dim() == 1 and b.is_contiguous() and b.numel() >= B
+        out += (b.data_ptr(),)
+    return out
 
 
 def _sample_operands(logits: torch.Tensor, params: torch.Tensor):
@@ -1101,7 +1132,8 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, counter: Optional[to
     row's greedy flag and its repetition penalty; without a bitmap no row may have a penalty on.  masks (int32 [R, ld_words], a set bit = token
     banned) and rules (token_rules, int32 [>= B, 4]): the ruled head (fo1_sample_rows_ruled_bf16), the general head behind each row's bans.
     guide (GuideOperands, with masks and rules): the guided head (fo1_sample_rows_guided_bf16) — a guided row b picks in state guide.gstate[b]
-    and the state after the pick is written back."""
+    and the state after the pick is written back; with guide.closes the closing head (fo1_sample_rows_closing_bf16), where guide.budget[b] -
+    counter - 1 tokens may follow row b's pick."""
     head, tail = _sample_operands(logits, params)
     B = head[3]
     if out is None:
@@ -1111,6 +1143,13 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, counter: Optional[to
         assert counter.dtype == torch.int32 and counter.is_cuda and counter.numel() > (B - 1) * counter_stride
     if u is not None:
         assert u.dtype == torch.float32 and u.is_cuda and u.is_contiguous() and u.numel() == B
+    if guide is not None and guide.closes is not None:
+        ps, ldw = _seen_operand(seen, B, head[2])
+        rc = _L.load().fo1_sample_rows_closing_bf16(*head, _ptr(counter), int(counter_stride), _ptr(u), out.data_ptr(), *tail[:2], ps, ldw,
+                                                    *_rule_operands(masks, rules, B, head[2]), tail[2], *_guide_operands(guide, B, head[2]),
+                                                    *_close_operands(guide, B, True))
+        _L.check(rc, "fo1_sample_rows_closing_bf16")
+        return out
     if guide is not None:
         ps, ldw = _seen_operand(seen, B, head[2])
         rc = _L.load().fo1_sample_rows_guided_bf16(*head, _ptr(counter), int(counter_stride), _ptr(u), out.data_ptr(), *tail[:2], ps, ldw,
@@ -1155,7 +1194,7 @@ def decode_head_accept(logits: torch.Tensor, params: torch.Tensor, state: torch.
     honoured; the accepted token's bit is set in the row's `seen` bitmap (int32 [>= B, ld_words]; None only when no row has a penalty).
     per_sequence_sets: as decode_argmax_accept.  masks / rules (as sample_rows takes them): the ruled head (fo1_decode_head_ruled_accept), which
     reads both tables and writes neither.  guide (GuideOperands, with masks and rules): the guided head (fo1_decode_head_guided_accept), which
-    also advances guide.gstate, the only guide table it writes."""
+    also advances guide.gstate, the only guide table it writes; with guide.closes the closing head (fo1_decode_head_closing_accept)."""
     B = state.shape[0]
     assert state.dtype == plan.dtype == ids_out.dtype == done.dtype == torch.int32 and ids_out.is_contiguous() and plan.is_contiguous()
     assert state.is_contiguous() and logits.shape[0] == B
@@ -1165,6 +1204,13 @@ def decode_head_accept(logits: torch.Tensor, params: torch.Tensor, state: torch.
         assert stop_ids is not None and stop_ids.dim() == 2 and stop_ids.shape[1] == 17 and stop_ids.is_contiguous() and stop_ids.dtype == torch.int32
         n_stop = -1
     ps, ldw = _seen_operand(seen, B, head[2])
+    if guide is not None and guide.closes is not None:
+        rc = _L.load().fo1_decode_head_closing_accept(*head, state.data_ptr(), plan.data_ptr(), ids_out.data_ptr(), ids_out.shape[1],
+                                                      stop_ids.data_ptr() if n_stop else None, n_stop, done.data_ptr(), *tail[:2], ps, ldw,
+                                                      *_rule_operands(masks, rules, B, head[2]), tail[2], *_guide_operands(guide, B, head[2]),
+                                                      *_close_operands(guide, B, False))
+        _L.check(rc, "fo1_decode_head_closing_accept")
+        return
     if guide is not None:
         rc = _L.load().fo1_decode_head_guided_accept(*head, state.data_ptr(), plan.data_ptr(), ids_out.data_ptr(), ids_out.shape[1],
                                                      stop_ids.data_ptr() if n_stop else None, n_stop, done.data_ptr(), *tail[:2], ps, ldw,
