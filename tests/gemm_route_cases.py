@@ -463,6 +463,18 @@ def _levels(n: int) -> torch.Tensor:
 PLANT = 1.0          # amplitude of the planted columns (tests/test_gemm_route_cases.py: at 0 the fault half fails)
 
 
+def bias_pattern(N: int) -> torch.Tensor:
+    """A per-column ramp with a jump at every 16- and 32-column fragment boundary."""
+    n = torch.arange(N)
+    return (0.015625 * (n % 16) + 0.5 * ((n // 16) % 5) - 1.0 + 0.25 * ((n // 32) % 2)).bfloat16()
+
+
+def res_pattern(M: int, N: int) -> torch.Tensor:
+    """Differs between (m, n), (m, n +- 1) and (m +- 1, n)."""
+    m, n = torch.arange(M)[:, None], torch.arange(N)[None, :]
+    return ((((3 * m + 5 * n) % 7) - 3) * 0.25 + ((m + n) % 2) * 0.125).bfloat16()
+
+
 def build(c: Case) -> dict:
     r = case_route(c)
     g = torch.Generator().manual_seed(c.seed)
@@ -481,11 +493,9 @@ def build(c: Case) -> dict:
         W[:, checker] = (0.5 * (1 - 2 * (torch.arange(c.N) % 2))).bfloat16()
     d = dict(case=c, route=r, A=A, W=W, pos=pos, checker=checker, bias=None, res=None)
     if c.bias:
-        n = torch.arange(c.N)
-        d["bias"] = (0.015625 * (n % 16) + 0.5 * ((n // 16) % 5) - 1.0 + 0.25 * ((n // 32) % 2)).bfloat16()
+        d["bias"] = bias_pattern(c.N)
     if c.res:
-        m, n = torch.arange(c.M)[:, None], torch.arange(c.N)[None, :]
-        d["res"] = ((((3 * m + 5 * n) % 7) - 3) * 0.25 + ((m + n) % 2) * 0.125).bfloat16()
+        d["res"] = res_pattern(c.M, c.N)
     return d
 
 

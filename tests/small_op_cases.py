@@ -1051,3 +1051,30 @@ def measure() -> Dict[str, float]:
         if small.any():
             m["box_abs"] = max(m["box_abs"], err[small].max().item())
     return m
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the row norms for other case modules (tests/fp8_cases.py: fo1_rmsnorm_quant_e4m3 is RMSNorm + quantiser)
+# ---------------------------------------------------------------------------------------------------------------------------------------
+gen, seq_sum, xor_tree = _gen, _seq_sum, _xor_tree
+
+
+def rownorm_case(name: str, op: str, x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None, **p) -> Case:
+    """A rownorm case over the caller's own rows x [M, D] (bf16), weight and bias; rownorm_reference / _bound / _emulate then serve it."""
+    M, D = x.shape
+    c = Case("rownorm", name, op=op, D=D, M=M, **p)
+    _INPUTS[name] = dict(x=x, w=w, b=torch.zeros(D, dtype=BF) if b is None else b)
+    return c
+
+
+def rownorm_reference(c: Case) -> torch.Tensor:
+    return _rownorm_ref(c)
+
+
+def rownorm_bound(c: Case, quarter: bool = False) -> torch.Tensor:
+    return _rownorm_bound(c, quarter)
+
+
+def rownorm_emulate(c: Case, fault: Optional[str] = None):
+    """-> (bf16-valued output, rstd) of the kernel's arithmetic."""
+    return _rownorm_emul(c, fault)

@@ -2569,7 +2569,8 @@ int fo1_gemm_bf16_wtiled(const void* A, int lda, const void* W_tiled, const void
 // fp8 linear (BASELINE configs[4], "fp8 MFMA"): C[M,N] = epilogue((Aq Wq^T) * scale_a[m] * scale_w[n]) with OCP e4m3 operands, fp32
 // accumulation on v_mfma_scale_f32_32x32x64_f8f6f4 (unit block scales), bf16 output; epilogues as fo1_gemm_bf16 (act 0..3).
 // Aq [M, K] / Wq [N, K] bytes with lda / ldw in elements (= bytes); K % 128 == 0.  The reference has no fp8 path: the bar is the
-// oracle's dequantised fp32 product (tests/test_fp8_gpu.py) and the tolerance table against the bf16 engine in DESIGN.md.
+// oracle's dequantised float64 product, element by element (tests/fp8_cases.py, tests/test_fp8_ops_gpu.py: bit for bit where the fp32
+// accumulation is exact, otherwise the per-element bound stated there), and the tolerance table against the bf16 engine in DESIGN.md.
 int fo1_gemm_fp8(const void* Aq, int lda, const float* scale_a, const void* Wq, int ldw, const float* scale_w, const void* bias,
                  const void* residual, int ldr, void* C, int ldc, int M, int N, int K, int act, void* stream) {
     using namespace fo1;
