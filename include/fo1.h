@@ -628,6 +628,60 @@ int fo1_decode_head_closing_accept(const void* logits, long long ld_logits, int 
                                    const int32_t* state_row, long long n_state_row, const fo1_token_guide_t* guides /* device [B] */,
                                    int32_t* gstate /* device [B], read and written */, const int32_t* close_row, long long n_close_row,
                                    const fo1_guide_close_t* closes /* device [B] */);
+/* Soft steering: a per-row additive logit bias and frequency / presence penalties.  Row b's steer names a row of the
+ * bias table (bf16 [bias_rows][ld_bias >= n_vocab]; entry b_i, a zero entry (0 or -0) = no bias; a bias_row outside [0, bias_rows) = no bias at
+ * all) and holds two penalties f, q against the row's counts (uint16 [rows >= B][ld_counts >= n_vocab, even]; n_i = how often the sequence has
+ * generated token i).  The count penalty of a row is on iff f and q are both finite and not both zero.  For a finite logit l_i, in this order:
+ *   1. ban        as the _ruled / _guided / _closing entries: a banned token is a non-finite entry, which no later step touches;
+ *   2. bias       if b_i != 0:  x = bf16_rne(fp32(l_i) + fp32(b_i))                                  (one fp32 add, one rounding)
+ *   3. penalty    the repetition penalty on x for the tokens of `seen`, as the _seen_ entry;
+ *   4. counts     if n_i > 0 and the penalty is on:  t = f * n_i;  t = t + q;  x = bf16_rne(x - t)   (three fp32 operations, each rounded: no
+ *                 fused multiply-add)
+ * and a result that is not finite counts as a non-finite entry.  The pick — greedy flag, top-k, top-p, the draw, "nothing left gives id 0" —
+ * is made on x.  Each table has a gate bitmap beside it in the seen bitmap's layout ([rows][gate_ld_words] uint32, a multiple of 4 words
+ * >= ceil(n_vocab / 32); bit i of a row set = entry i of the table's row may be non-zero): the head reads an entry only behind a set bit, so
+ * an entry whose bit is clear counts as zero — the caller keeps bias_gate in step with bias; fo1_count_mark and the accept form keep
+ * count_gate in step with counts.
+ *   fo1_sample_rows_steered_bf16     fo1_sample_rows_closing_bf16 + steers; reads the tables, writes none
+ *   fo1_decode_head_steered_accept   fo1_decode_head_closing_accept + steers; after the pick the accepted token's count of row b goes up by one
+ *                                    (saturating at 65535) and its gate bit is set, when counts are given; a finished row touches nothing
+ * steers == NULL: the call is the _closing entry's.  With steers the rule, guide and closing tables are optional, each level needing the one
+ * before it (rules + masks; + guides; + closes).  bias == NULL (with bias_gate == NULL): no row has a bias; counts == NULL (with count_gate ==
+ * NULL) is allowed only when no row has the count penalty on (such a row is picked without it).  One launch whatever the data, no host
+ * read, capturable, B <= 256; the same row and steer give the same id in any row of any batch. */
+typedef struct fo1_token_steer {      /* 16 bytes */
+    int32_t bias_row;               /* row of the bias table; outside [0, bias_rows): no bias */
+    float frequency_penalty;        /* f: subtracted once per earlier occurrence */
+    float presence_penalty;         /* q: subtracted once if the token occurred at all */
+    int32_t reserved;
+} fo1_token_steer_t;
+int fo1_sample_rows_steered_bf16(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params,
+                                 const int32_t* counter /* NULL = 0 */, int counter_stride, const float* u /* device [B]; NULL = Philox */,
+                                 int32_t* out /* [B] */, void* workspace, size_t workspace_bytes, const uint32_t* seen, long long ld_words,
+                                 const uint32_t* masks, int mask_rows, long long mask_ld_words, const fo1_token_rule_t* rules /* device [B] */,
+                                 void* stream, const uint16_t* cls, int cls_rows, long long ld_cls, const int32_t* next, long long n_next,
+                                 const int32_t* state_row, long long n_state_row, const fo1_token_guide_t* guides /* device [B] */,
+                                 int32_t* gstate /* device [B], read and written */, const int32_t* close_row, long long n_close_row,
+                                 const fo1_guide_close_t* closes /* device [B] */, const int32_t* budget /* device [B] */,
+                                 const void* bias /* bf16 */, const uint32_t* bias_gate, int bias_rows, long long ld_bias,
+                                 const uint16_t* counts, const uint32_t* count_gate, long long ld_counts, long long gate_ld_words,
+                                 const fo1_token_steer_t* steers /* device [B] */);
+int fo1_decode_head_steered_accept(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params,
+                                   int32_t* state, int32_t* plan, int32_t* ids_out, int ids_ld, const int32_t* stop_ids, int n_stop,
+                                   int32_t* done, void* workspace, size_t workspace_bytes, uint32_t* seen, long long ld_words,
+                                   const uint32_t* masks, int mask_rows, long long mask_ld_words, const fo1_token_rule_t* rules /* device [B] */,
+                                   void* stream, const uint16_t* cls, int cls_rows, long long ld_cls, const int32_t* next, long long n_next,
+                                   const int32_t* state_row, long long n_state_row, const fo1_token_guide_t* guides /* device [B] */,
+                                   int32_t* gstate /* device [B], read and written */, const int32_t* close_row, long long n_close_row,
+                                   const fo1_guide_close_t* closes /* device [B] */, const void* bias /* bf16 */, const uint32_t* bias_gate,
+                                   int bias_rows, long long ld_bias, uint16_t* counts /* read and written */,
+                                   uint32_t* count_gate /* read and written */, long long ld_counts, long long gate_ld_words,
+                                   const fo1_token_steer_t* steers /* device [B] */);
+/* counts[rows[i]][ids[i]] += 1 and the matching bit of count_gate set, for i < n (device int32 each; duplicates add up).  Ids outside
+ * [0, n_vocab) and negative rows are skipped; the caller vouches for rows[i] < the tables' rows and zeroes a row (both tables) to restart it.
+ * The analogue of fo1_seen_mark: it counts a sequence's first token. */
+int fo1_count_mark(uint16_t* counts, long long ld_counts, uint32_t* count_gate, long long gate_ld_words, int n_vocab, const int32_t* rows,
+                   const int32_t* ids, int n, void* stream);
 /* Log-probabilities of generated tokens.  For a bf16 logits row l[0..V) with F = { i : l_i finite }:
  *   m = max_F l,  S = sum_{i in F} exp(l_i - m) (fp32, a fixed order),  lp_i = (l_i - m) - log S as fp32 for i in F,  lp_i = -inf otherwise
  * (the sampler's rule: a non-finite entry has weight 0); a row with empty F gives -inf everywhere.  This is the log-softmax of the RAW logits:

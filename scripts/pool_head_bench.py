@@ -19,7 +19,13 @@
              D = 1 and the budget's last pick alone reads a closing row — every timed step pays the closing form's two table reads and
              resolves to the state's plain row, the steady state of a closing sequence,
   guided_open   the same guide without accepting states through fo1_decode_head_guided_accept: what `closing` adds to,
-  sampled_closing / sampled_guided_open   the two on every sequence of `sampled`.
+  sampled_closing / sampled_guided_open   the two on every sequence of `sampled`,
+  biased     the steered general head fo1_decode_head_steered_accept, every sequence greedy with one shared logit bias of 300 entries (one row
+             of the bias table): what the bias adds to `greedy_general`,
+  sampled_biased   the same bias on every sequence of `sampled`,
+  counted    every sequence of `sampled` with frequency_penalty = presence_penalty = 0.2: the count rows are read (their gate bitmaps first)
+             and the accepted token counted every step,
+  greedy_counted   the same penalties on every sequence of `greedy_general`.
 The heads are timed alternately, `--rounds` times each in one process, so the spread of a figure is the spread between its rounds; the pool is
 drained and re-joined for every timing.  Prints one JSON object.
 
@@ -28,7 +34,9 @@ drained and re-joined for every timing.  Prints one JSON object.
 With `greedy` among the heads the output also holds each other head's increment over it (difference of the medians of this process), and
 for a ruled head its increment over the same head without a rule (banned, min_new: greedy_general; sampled_banned: sampled), for a guided
 head its increment over the ruled head with the same mask row (guided: banned; sampled_guided: sampled_banned; one_guided: one_banned), for
-a closing head its increment over the guided head with the same guide (closing: guided_open; sampled_closing: sampled_guided_open).
+a closing head its increment over the guided head with the same guide (closing: guided_open; sampled_closing: sampled_guided_open), for
+a steered head its increment over the same head without the steer (biased, greedy_counted: greedy_general; sampled_biased, counted: sampled)
+beside this process's penalised - sampled, the increment of the other per-token transformation behind a gate bitmap.
 
 --root DIR imports the package from another checkout (e.g. the parent commit, for the greedy figure of both on one box; only `greedy`
 exists there; a head the other checkout lacks cannot be named)."""
@@ -48,7 +56,8 @@ def main():
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=5)
     HEADS = ["greedy", "sampled", "penalised", "greedy_lp0", "greedy_lp8", "greedy_general", "banned", "sampled_banned", "min_new", "guided",
-             "sampled_guided", "one_banned", "one_guided", "closing", "guided_open", "sampled_closing", "sampled_guided_open"]
+             "sampled_guided", "one_banned", "one_guided", "closing", "guided_open", "sampled_closing", "sampled_guided_open",
+             "biased", "sampled_biased", "counted", "greedy_counted"]
     ap.add_argument("--heads", nargs="+", default=HEADS[:3], choices=HEADS)
     ap.add_argument("--root", default=None, help="import vlm_fo1_amd from this checkout instead of the script's own")
     args = ap.parse_args()
@@ -103,6 +112,12 @@ def main():
             sampling[name] = dict(greedy=True, guide=g3)
             sampling["sampled_" + name] = dict(sampling["sampled"], guide=g3)
 
+    bias = {t: (1.5 if i % 2 else -1.5) for i, t in enumerate(range(7, V, max(1, V // 300))[:300])}      # one vector for every sequence: one shared row
+    sampling.update(biased=dict(greedy=True, bias=bias), sampled_biased=dict(sampling["sampled"], bias=bias),
+                    counted=dict(sampling["sampled"], frequency_penalty=0.2, presence_penalty=0.2),
+                    greedy_counted=dict(greedy=True, frequency_penalty=0.2, presence_penalty=0.2))
+    unsteered = dict(biased="greedy_general", greedy_counted="greedy_general", sampled_biased="sampled", counted="sampled")
+
     def one(head):
         left, base = P, 0
         while left > 0:
@@ -152,6 +167,11 @@ def main():
     closing = {h: round(out["heads"][h]["median"] - out["heads"][u]["median"], 4) for h, u in unclosed.items() if h in times and u in times}
     if closing:
         out["increment_over_guided_ms"] = closing
+    steered = {h: round(out["heads"][h]["median"] - out["heads"][u]["median"], 4) for h, u in unsteered.items() if h in times and u in times}
+    if steered:
+        out["increment_over_unsteered_ms"] = steered
+        if "penalised" in times and "sampled" in times:
+            out["penalised_minus_sampled_ms"] = round(out["heads"]["penalised"]["median"] - out["heads"]["sampled"]["median"], 4)
     print(json.dumps(out))
 
 

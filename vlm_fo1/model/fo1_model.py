@@ -306,19 +306,83 @@ class FO1ForCausalLM:
                 plan[k] = tuple(sorted(set(int(t) for t in plan[k])))
         return plan or None
 
+    @staticmethod
+    def _steer_plan(kwargs: dict) -> Optional[dict]:
+        """generate()'s logit_bias / sequence_bias / frequency_penalty / presence_penalty -> None (all off, the default, whatever
+        generation_config.json holds) or the engine's steer keys (vlm_fo1_amd.llm.token_steer, which checks the ids against the vocabulary
+        and rounds the values to bf16): bias = {id: value} from logit_bias ({id: value}; an id may be an integer or its decimal string, as
+        OpenAI-shaped callers send it) and sequence_bias (HF's forms {(id,): value} or [[[id], value], ...]; an entry longer than one token is
+        a NotImplementedError naming it), the two summed per id; an id whose sum is 0 has no bias.  frequency_penalty / presence_penalty: any
+        finite fp32 value, 0 or None = off.  ValueError: a value that is a bool, not a number or not finite."""
+        import math
+
+        def number(v, what):
+            if isinstance(v, bool):
+                raise ValueError(f"{what}: a finite number (got {v!r})")
+            try:
+                f = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"{what}: a finite number (got {v!r})") from None
+            if not math.isfinite(f) or not math.isfinite(float(torch.tensor(f, dtype=torch.float32))):
+                raise ValueError(f"{what}: a finite number (got {v!r}); to forbid a token use suppress_tokens, to force a set allowed_token_ids")
+            return f
+
+        def token(t, what):
+            if isinstance(t, str) and t.strip().lstrip("-").isdigit():
+                t = int(t)
+            if isinstance(t, torch.Tensor) and t.numel() == 1 and not t.is_floating_point():
+                t = int(t.item())
+            if isinstance(t, (bool, float)) or not hasattr(t, "__index__"):
+                raise ValueError(f"{what}: token ids are integers (got {t!r})")
+            return int(t)
+
+        bias: Dict[int, float] = {}
+        lb = kwargs.get("logit_bias")
+        if lb is not None:
+            if not hasattr(lb, "items"):
+                raise ValueError(f"logit_bias: a dict {{token id: value}} (got {type(lb).__name__})")
+            for t, v in lb.items():
+                t = token(t, "logit_bias")
+                bias[t] = bias.get(t, 0.0) + number(v, f"logit_bias[{t}]")
+        sb = kwargs.get("sequence_bias")
+        if sb is not None:
+            if isinstance(sb, (str, bytes)) or not (hasattr(sb, "items") or hasattr(sb, "__iter__")):
+                raise ValueError(f"sequence_bias: {{(id,): value}} or [[[id], value], ...] (got {sb!r})")
+            entries = list(sb.items()) if hasattr(sb, "items") else [tuple(e) for e in sb]
+            for e in entries:
+                if len(e) != 2:
+                    raise ValueError(f"sequence_bias: an entry is (token sequence, value) (got {e!r})")
+                seq, v = e
+                seq = seq.reshape(-1).tolist() if isinstance(seq, torch.Tensor) else (list(seq) if hasattr(seq, "__iter__") and not isinstance(seq, (str, bytes)) else [seq])
+                if len(seq) != 1:
+                    raise NotImplementedError(f"sequence_bias: only single-token entries are biased on the device (got {seq!r})")
+                t = token(seq[0], "sequence_bias")
+                bias[t] = bias.get(t, 0.0) + number(v, f"sequence_bias[{t}]")
+        plan = {}
+        bias = {t: number(v, f"the summed bias of token {t}") for t, v in sorted(bias.items()) if v != 0}
+        if bias:
+            plan["bias"] = bias
+        for name in ("frequency_penalty", "presence_penalty"):
+            v = kwargs.get(name)
+            if v is not None and number(v, name) != 0:
+                plan[name] = number(v, name)
+        return plan or None
+
     @classmethod
     def _decode_plan(cls, kwargs: dict, generation_config: Optional[dict] = None, eos_ids=()) -> Optional[dict]:
-        """_sampling_plan, _penalty_plan and _rule_plan as the one dict the engine takes per request: None = plain greedy; a sampled request's
-        dict gains repetition_penalty and the token-rule keys; a greedy request with a penalty or a rule is dict(greedy=True, ...).  guide (a
-        vlm_fo1_amd.guide.TokenGuide, or None = off; anything else is a ValueError) rides in the dict as the engine's `guide` key."""
+        """_sampling_plan, _penalty_plan, _rule_plan and _steer_plan as the one dict the engine takes per request: None = plain greedy; a
+        sampled request's dict gains repetition_penalty, the token-rule keys and the steer keys; a greedy request with a penalty, a rule or a
+        steer is dict(greedy=True, ...).  guide (a vlm_fo1_amd.guide.TokenGuide, or None = off; anything else is a ValueError) rides in the
+        dict as the engine's `guide` key."""
         sampling, pen, rule = cls._sampling_plan(kwargs, generation_config), cls._penalty_plan(kwargs), cls._rule_plan(kwargs, eos_ids)
-        guide = cls._guide_plan(kwargs)
-        if pen is None and rule is None and guide is None:
+        guide, steer = cls._guide_plan(kwargs), cls._steer_plan(kwargs)
+        if pen is None and rule is None and guide is None and steer is None:
             return sampling
         plan = dict(greedy=True) if sampling is None else dict(sampling)
         if pen is not None:
             plan["repetition_penalty"] = pen
         plan.update(rule or {})
+        plan.update(steer or {})
         if guide is not None:
             plan["guide"] = guide
         return plan
@@ -398,7 +462,7 @@ class FO1ForCausalLM:
             sp = self._sampling_plan(dict(kw, seed=0), gen)
             rule = self._rule_plan(kw, eos)
             return ((None if sp is None else (sp["temperature"], sp["top_p"], sp["top_k"])), self._penalty_plan(kw), rule and tuple(sorted(rule.items())),
-                    self._guide_plan(kw))
+                    self._guide_plan(kw), self._steer_plan(kw))
         v0 = values(k0)
         mixed = False
         for kw in requests_kwargs[1:]:       # one budget and one stop rule per packed batch: refuse a mixed batch rather than apply the first's
@@ -412,7 +476,7 @@ class FO1ForCausalLM:
                     continue
                 if v != v0:      # without the pool one BatchDecoder group decodes the batch with one sampling
                     raise ValueError("generate_many: every request of a batch must share do_sample, temperature, top_p and top_k "
-                                     "(and repetition_penalty, the token-rule keywords and the guide) unless the decode pool is enabled")
+                                     "(and repetition_penalty, the token-rule keywords, the guide and the steering keywords) unless the decode pool is enabled")
                 raise ValueError("generate_many: every request of a sampled batch must share seed (request i draws on stream i of the one seed)")
         sampling = [self._decode_plan(kw, gen, eos) for kw in requests_kwargs] if mixed else self._decode_plan(k0, gen, eos)
         reqs = [self._request(kw.get("inputs"), kw.get("images"), kw.get("images_aux"), kw.get("image_grid_thws"), kw.get("bbox_list"))
@@ -533,7 +597,7 @@ class FO1ForCausalLM:
                  temperature=0.0, max_new_tokens=512, streamer=None, top_p=1.0, use_cache=True, stopping_criteria=None,
                  pad_token_id=None, top_k=None, seed=None, repetition_penalty=None, _stream=0, output_logprobs=False, top_logprobs=0,
                  suppress_tokens=None, begin_suppress_tokens=None, bad_words_ids=None, min_new_tokens=None, allowed_token_ids=None, guide=None,
-                 **unused):
+                 logit_bias=None, sequence_bias=None, frequency_penalty=None, presence_penalty=None, **unused):
         """Decoding of one prompt: greedy, or with do_sample=True temperature / top-k / top-p sampling on the device (_sampling_plan).
         Returns [1, L_in + new] like HF generate (the reference slices `output_ids[0, inputs.shape[1]:]`, inference.py:47-48).  Without a
         streamer and with id-set stop criteria the whole loop runs on the device (BatchDecoder, no per-token host read); otherwise tokens
@@ -554,7 +618,11 @@ class FO1ForCausalLM:
         guide: None (off) or a vlm_fo1_amd.guide.TokenGuide — region_guide(tokenizer, n_regions) for the FO1 answer language, guide.ban_sequences
         for multi-token banned sequences: the banned set of every pick follows the guide's automaton state, which the head advances on the
         device; decoded as a constrained generation is.  max_new_tokens may still cut an answer short inside a structure unless the guide has
-        accepting states (region_guide(..., close=True)): then the head closes the structure before the budget runs out."""
+        accepting states (region_guide(..., close=True)): then the head closes the structure before the budget runs out.
+        logit_bias={id: value} / sequence_bias (HF's forms, single-token entries; a longer one is a NotImplementedError): added to the token's
+        logit in front of the repetition penalty, the two keywords summed per id; frequency_penalty / presence_penalty: the OpenAI count
+        penalties over the generated tokens, subtracted after it (_steer_plan).  All default to off, whatever
+        generation_config.json holds; a steered generation decodes as a penalised one does, max_new_tokens beyond IDS_CAP is a ValueError."""
         lpn = self._logprob_plan(dict(output_logprobs=output_logprobs, top_logprobs=top_logprobs))
         if lpn is not None and not self._fits_device_loop(max_new_tokens):
             from vlm_fo1_amd.llm import BatchDecoder
@@ -562,7 +630,8 @@ class FO1ForCausalLM:
         sampling = self._decode_plan(dict(do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k, seed=seed,
                                           repetition_penalty=repetition_penalty, suppress_tokens=suppress_tokens,
                                           begin_suppress_tokens=begin_suppress_tokens, bad_words_ids=bad_words_ids, min_new_tokens=min_new_tokens,
-                                          allowed_token_ids=allowed_token_ids, guide=guide), getattr(self.config, "_gen", None),
+                                          allowed_token_ids=allowed_token_ids, guide=guide, logit_bias=logit_bias, sequence_bias=sequence_bias,
+                                          frequency_penalty=frequency_penalty, presence_penalty=presence_penalty), getattr(self.config, "_gen", None),
                                      self.config.eos_ids())
         req = self._request(inputs, images, images_aux, image_grid_thws, bbox_list)
         dev = self.device

@@ -47,6 +47,16 @@
 // With r = budget - c - 1 tokens still to follow this pick, a guided row with 0 <= r < depth takes close_row[close_off + s * depth + r] as its
 // state's mask row instead of state_row[row_off + s]: two more scalar table reads where the guide is resolved, nothing else.  An index outside
 // close_row keeps the plain row.
+//
+// The steered head (STEER instantiations: fo1_sample_rows_steered_bf16, fo1_decode_head_steered_accept) reads one fo1_token_steer_t per row
+// { bias_row, frequency_penalty f, presence_penalty q } and resolves it, once per workgroup, to a row of the bias table (bf16, a zero entry =
+// no bias; bias_row outside the table: none) and, when f and q are both finite and not both zero, the row's generated-token counts (uint16).
+// Each table has a gate bitmap beside it in the seen bitmap's layout — a set bit = the entry may be non-zero — so a pass pays one byte per 8
+// tokens and loads an entry only behind a set bit.  For a finite logit l, in this order (sp_load8p, after the ban):
+//   bias (b != 0):    x = bf16_rne(fp32(l) + fp32(b));           then the repetition penalty on x, as above;
+//   counts (n > 0):   t = f * n, t = t + q, x = bf16_rne(x - t)  — three separately rounded fp32 operations, no fused multiply-add.
+// A result that is not finite has no key, and no later step touches it.  In the accept form thread 0 adds 1 to the accepted token's count
+// (saturating) and sets its gate bit where it sets the seen bit.
 #include "decode_common.h"
 
 namespace fo1 {
@@ -90,12 +100,47 @@ struct SpGuide {
     int cmax;
 };
 
-// sp_load8; RULE: banned tokens come back as a NaN (no key); PEN: seen tokens come back as their penalised logit, so every pass keys the same
+// what the steer needs of a row: its bias row with the gate bitmap (bgate == NULL: no bias) and its count row with the gate bitmap and the
+// two penalties (cgate == NULL: the count penalty is off).  Gates are bytes, as SpPen::seen
+struct SpSteer {
+    const uint16_t* bias;
+    const uint8_t* bgate;
+    const uint16_t* cnt;
+    const uint8_t* cgate;
+    float f, q;
+    bool bvec, cvec;      // the bias row / the count row is 16-byte aligned (sp_load8's vector path)
+};
+
+// the biased logit: bf16_rne(fp32(l) + fp32(b)); a non-finite entry and a zero bias (0 or -0) leave the entry alone
+__device__ __forceinline__ uint32_t sp_bias(uint32_t e, uint32_t b) {
+    if ((e & 0x7f80u) == 0x7f80u || (b & 0x7fffu) == 0u) return e;
+    return (uint32_t)f32_to_bf16(__fadd_rn(__uint_as_float(e << 16), __uint_as_float(b << 16)));
+}
+
+// the count-penalised logit of a token generated n > 0 times: bf16_rne(x - (f * n + q)), every operation rounded on its own.  hipcc contracts
+// a * b + c into a fused multiply-add by default, also through __fmul_rn / __fadd_rn (plain operators in this toolchain): the pragma takes
+// the licence away from the operations of this block, and the product is rounded before the sum sees it
+__device__ __forceinline__ uint32_t sp_count(uint32_t e, float f, float q, uint32_t n) {
+#pragma clang fp contract(off)
+    if ((e & 0x7f80u) == 0x7f80u || n == 0u) return e;
+    float t = f * (float)n;
+    t = t + q;
+    return (uint32_t)f32_to_bf16(__uint_as_float(e << 16) - t);
+}
+
+// sp_load8; RULE: banned tokens come back as a NaN (no key); STEER: biased tokens come back as their biased logit, tokens generated before as
+// their count-penalised one; PEN: seen tokens come back as their penalised logit, so every pass keys the same
 // 16-bit values
-template <bool PEN, bool RULE>
-__device__ __forceinline__ void sp_load8p(const uint16_t* __restrict__ row, const SpPen& pen, const SpRule& rule, int i0, int V, bool vec,
-                                          uint32_t (&e)[8]) {
+template <bool PEN, bool RULE, bool STEER = false>
+__device__ __forceinline__ void sp_load8p(const uint16_t* __restrict__ row, const SpPen& pen, const SpRule& rule, const SpSteer& steer, int i0,
+                                          int V, bool vec, uint32_t (&e)[8]) {
     uint32_t ban = 0u;
+    [[maybe_unused]] uint32_t bbits = 0u, cbits = 0u;
+    if constexpr (STEER) {     // the gate bytes, in front of the logits' load as the mask bytes are: one latency, not three in a row
+        const int i = min(i0, V - 1) >> 3;      // (byte < ceil(V / 8) <= 4 gate_ld_words: inside the gate row)
+        if (steer.bgate) bbits = steer.bgate[i];
+        if (steer.cgate) cbits = steer.cgate[i];
+    }
     if constexpr (RULE) {      // in front of the logits' load: the loads are in flight together
         if (rule.live) {
             const int i = min(i0, V - 1) >> 3;      // (byte < ceil(V / 8) <= 4 mask_ld_words: inside the mask row; past the row's end the entries are NaN already)
@@ -110,6 +155,15 @@ __device__ __forceinline__ void sp_load8p(const uint16_t* __restrict__ row, cons
                 if ((ban >> j) & 1u) e[j] = 0x7fc0u;
         }
     }
+    if constexpr (STEER) {
+        if (bbits) {      // some entry of this group may be non-zero: the group's 8 entries in one load (past the row's end the logits are NaN already)
+            uint32_t bv[8];
+            sp_load8(steer.bias, i0, V, steer.bvec, bv);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if ((bbits >> j) & 1u) e[j] = sp_bias(e[j], bv[j]);      // (an entry behind a clear bit counts as zero)
+        }
+    }
     if constexpr (PEN) {
         if (pen.seen) {
             const uint32_t bits = i0 < V ? pen.seen[i0 >> 3] : 0u;
@@ -120,14 +174,24 @@ __device__ __forceinline__ void sp_load8p(const uint16_t* __restrict__ row, cons
             }
         }
     }
+    if constexpr (STEER) {
+        if (cbits) {
+            uint32_t cv[8];
+            sp_load8(steer.cnt, i0, V, steer.cvec, cv);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if ((cbits >> j) & 1u) e[j] = sp_count(e[j], steer.f, steer.q, cv[j]);
+        }
+    }
 }
 
 // every key of the row, 8 tokens per thread and step (any order: the callers count or take a maximum)
-template <bool PEN, bool RULE, class F>
-__device__ __forceinline__ void sp_for_row(const uint16_t* __restrict__ row, const SpPen& pen, const SpRule& rule, int V, bool vec, F f) {
+template <bool PEN, bool RULE, bool STEER, class F>
+__device__ __forceinline__ void sp_for_row(const uint16_t* __restrict__ row, const SpPen& pen, const SpRule& rule, const SpSteer& steer, int V,
+                                           bool vec, F f) {
     for (int i0 = threadIdx.x * 8; i0 < V; i0 += SP_NT * 8) {
         uint32_t e[8];
-        sp_load8p<PEN, RULE>(row, pen, rule, i0, V, vec, e);
+        sp_load8p<PEN, RULE, STEER>(row, pen, rule, steer, i0, V, vec, e);
 #pragma unroll
         for (int j = 0; j < 8; ++j) f(sp_key(e[j]));
     }
@@ -177,6 +241,9 @@ struct SampleArgs {
     const uint16_t* cls; int cls_rows; long long ld_cls; const int* next; long long n_next;            // guided head: token classes, transitions,
     const int* state_row; long long n_state_row; const fo1_token_guide_t* guides; int* gstate;         // state -> mask row, the rows' guides and states
     const int* close_row; long long n_close_row; const fo1_guide_close_t* closes; const int* budget;   // closing head: (state, tokens left) -> mask row, the rows' closing rules, rows form: their budgets
+    const uint16_t* bias; const uint32_t* bias_gate; int bias_rows; long long ld_bias;                 // steered head: the bias table and its gate bitmaps,
+    uint16_t* counts; uint32_t* count_gate; long long ld_counts; long long gate_ld_words;              // the rows' counts [rows][ld_counts] and their gate bitmaps,
+    const fo1_token_steer_t* steers;                                                                   // the rows' steers
 };
 
 // Key scan of the half whose counters sit in `hist` (keys key0 .. key0 + 32767), top key down.  carry_c / carry_m: tokens and mass of the
@@ -221,7 +288,7 @@ __device__ __forceinline__ void sp_key_scan(const uint32_t* hist, int key0, int 
     __syncthreads();
 }
 
-template <bool ACCEPT, bool PEN, bool RULE = false, bool GUIDE = false, bool CLOSE = false>
+template <bool ACCEPT, bool PEN, bool RULE = false, bool GUIDE = false, bool CLOSE = false, bool STEER = false>
 __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
     extern __shared__ __align__(16) unsigned char sp_smem[];
     uint32_t* hist = reinterpret_cast<uint32_t*>(sp_smem);
@@ -257,6 +324,23 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
             pen.p = rp;
         }
     }
+    SpSteer steer{nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, false, false};
+    if constexpr (STEER) {      // the row's bias row and count row (uniform per row); a bias_row outside the table: no bias
+        const fo1_token_steer_t S = a.steers[b];
+        if (a.bias && a.bias_gate && S.bias_row >= 0 && S.bias_row < a.bias_rows) {
+            steer.bias = a.bias + (long long)S.bias_row * a.ld_bias;
+            steer.bgate = reinterpret_cast<const uint8_t*>(a.bias_gate + (long long)S.bias_row * a.gate_ld_words);
+            steer.bvec = ((uintptr_t)steer.bias & 15) == 0;
+        }
+        const float f = S.frequency_penalty, q = S.presence_penalty;
+        if (a.counts && a.count_gate && fabsf(f) < INFINITY && fabsf(q) < INFINITY && (f != 0.f || q != 0.f)) {
+            steer.cnt = a.counts + (long long)b * a.ld_counts;
+            steer.cgate = reinterpret_cast<const uint8_t*>(a.count_gate + (long long)b * a.gate_ld_words);
+            steer.cvec = ((uintptr_t)steer.cnt & 15) == 0;
+            steer.f = f;
+            steer.q = q;
+        }
+    }
     SpRule rule{{nullptr, nullptr, nullptr}, false};
     if constexpr (GUIDE) {
         if (tid == 0) s_gd.cmax = 0;
@@ -272,11 +356,13 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
                 const long long ri = (long long)G.row_off + gs;
                 row0 = gs >= 0 && ri < a.n_state_row ? a.state_row[ri] : -1;
                 if constexpr (CLOSE) {      // fewer than `depth` tokens may follow this pick: the row of (state, tokens left) instead
-                    const fo1_guide_close_t K = a.closes[b];
-                    const int left = (ACCEPT ? min(st[5], a.ids_ld) : a.budget[b]) - c - 1;
-                    if (K.depth > 0 && K.close_off >= 0 && gs >= 0 && left >= 0 && left < K.depth) {
-                        const long long ci = (long long)K.close_off + (long long)gs * K.depth + left;
-                        if (ci < a.n_close_row) row0 = a.close_row[ci];
+                    if (!STEER || a.closes) {      // (the steered head also takes a batch without closing rules)
+                        const fo1_guide_close_t K = a.closes[b];
+                        const int left = (ACCEPT ? min(st[5], a.ids_ld) : a.budget[b]) - c - 1;
+                        if (K.depth > 0 && K.close_off >= 0 && gs >= 0 && left >= 0 && left < K.depth) {
+                            const long long ci = (long long)K.close_off + (long long)gs * K.depth + left;
+                            if (ci < a.n_close_row) row0 = a.close_row[ci];
+                        }
                     }
                 }
                 // what thread 0 needs after the pick waits in LDS, not in registers across the passes: the token's class row, the state's
@@ -309,12 +395,12 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
     __syncthreads();
     int kmax = -1;
     if (cut)
-        sp_for_row<PEN, RULE>(row, pen, rule, V, vec, [&](int k) {
+        sp_for_row<PEN, RULE, STEER>(row, pen, rule, steer, V, vec, [&](int k) {
             kmax = max(kmax, k);
             if (k >= 0x8000) atomicAdd(&hist[sp_slot(k & 0x7fff)], 1u);
         });
     else
-        sp_for_row<PEN, RULE>(row, pen, rule, V, vec, [&](int k) { kmax = max(kmax, k); });
+        sp_for_row<PEN, RULE, STEER>(row, pen, rule, steer, V, vec, [&](int k) { kmax = max(kmax, k); });
     kmax = sp_wave_max(kmax);
     if (lane == 0) s_wi[wave] = kmax;
     __syncthreads();
@@ -326,7 +412,7 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
             int first = 0x7fffffff;
             for (int i0 = tid * 8; i0 < V; i0 += SP_NT * 8) {
                 uint32_t e[8];
-                sp_load8p<PEN, RULE>(row, pen, rule, i0, V, vec, e);
+                sp_load8p<PEN, RULE, STEER>(row, pen, rule, steer, i0, V, vec, e);
 #pragma unroll
                 for (int j = 7; j >= 0; --j)
                     if (sp_key(e[j]) == kmax) first = min(first, i0 + j);
@@ -349,7 +435,7 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
             if (s_kcut_k < 0) {      // no top-k cut-off yet: the negative half (uniform: shared value read after the scan's barrier)
                 for (int i = tid; i < SP_HALF; i += SP_NT) hist[i] = 0;
                 __syncthreads();
-                sp_for_row<PEN, RULE>(row, pen, rule, V, vec, [&](int k) {
+                sp_for_row<PEN, RULE, STEER>(row, pen, rule, steer, V, vec, [&](int k) {
                     if (k >= 0 && k < 0x8000) atomicAdd(&hist[sp_slot(k)], 1u);
                 });
                 __syncthreads();
@@ -378,7 +464,7 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
                     if (!resident) {
                         if (tid < SP_KPT) mini[tid] = 0;
                         __syncthreads();
-                        sp_for_row<PEN, RULE>(row, pen, rule, V, vec, [&](int k) {
+                        sp_for_row<PEN, RULE, STEER>(row, pen, rule, steer, V, vec, [&](int k) {
                             if (k >= key_lo && k < key_lo + SP_KPT) atomicAdd(&mini[k - key_lo], 1u);
                         });
                         __syncthreads();
@@ -416,7 +502,7 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
         for (int s0 = r0; s0 < r0 + region && s0 < V; s0 += SP_SLICE) {
             uint32_t e[8];
             const int i0 = s0 + lane * 8;
-            sp_load8p<PEN, RULE>(row, pen, rule, i0, V, vec, e);
+            sp_load8p<PEN, RULE, STEER>(row, pen, rule, steer, i0, V, vec, e);
             float s = 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -450,7 +536,7 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
             for (int s0 = r0; s0 < r0 + region && s0 < V && pick < 0; s0 += SP_SLICE) {
                 uint32_t e[8];
                 const int i0 = s0 + lane * 8;
-                sp_load8p<PEN, RULE>(row, pen, rule, i0, V, vec, e);
+                sp_load8p<PEN, RULE, STEER>(row, pen, rule, steer, i0, V, vec, e);
                 float wj[8], s = 0.f;
                 int lm = -1;
 #pragma unroll
@@ -507,6 +593,14 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
             if constexpr (PEN) {      // the accepted token joins the row's seen set (tok < V: an index of the row)
                 if (a.seen) atomicOr(a.seen + (long long)b * a.ld_words + (tok >> 5), 1u << (tok & 31));
             }
+            if constexpr (STEER) {    // ... and its count goes up by one (this workgroup is the row's only writer; tok < V <= ld_counts)
+                if (a.counts && a.count_gate) {
+                    uint16_t* cn = a.counts + (long long)b * a.ld_counts + tok;
+                    const uint16_t n = *cn;
+                    if (n != 0xffffu) *cn = (uint16_t)(n + 1);
+                    atomicOr(a.count_gate + (long long)b * a.gate_ld_words + (tok >> 5), 1u << (tok & 31));
+                }
+            }
         } else {
             a.out[b] = tok;
         }
@@ -518,14 +612,15 @@ __global__ __launch_bounds__(SP_NT) void sample_rows_kernel(SampleArgs a) {
 
 constexpr size_t SP_WORKSPACE = 256;      // the one-workgroup-per-row kernel keeps everything in LDS; the argument stays for a split form
 
-template <bool ACCEPT, bool PEN, bool RULE = false, bool GUIDE = false, bool CLOSE = false>
+template <bool ACCEPT, bool PEN, bool RULE = false, bool GUIDE = false, bool CLOSE = false, bool STEER = false>
 static int launch_sample(const SampleArgs& a, int B, hipStream_t st) {
-    FO1_DYNAMIC_LDS_ONCE(SP_SMEM, sample_rows_kernel<ACCEPT, PEN, RULE, GUIDE, CLOSE>);
-    FO1_LAUNCH(CLOSE ? (ACCEPT ? "head_closing_accept" : "sample_rows_closing")
+    FO1_DYNAMIC_LDS_ONCE(SP_SMEM, sample_rows_kernel<ACCEPT, PEN, RULE, GUIDE, CLOSE, STEER>);
+    FO1_LAUNCH(STEER ? (ACCEPT ? "head_steered_accept" : "sample_rows_steered")
+               : CLOSE ? (ACCEPT ? "head_closing_accept" : "sample_rows_closing")
                : GUIDE ? (ACCEPT ? "head_guided_accept" : "sample_rows_guided")
                : RULE ? (ACCEPT ? "head_ruled_accept" : "sample_rows_ruled")
                       : PEN ? (ACCEPT ? "head_accept" : "sample_rows_seen") : (ACCEPT ? "sample_accept" : "sample_rows"),
-               (double)B * a.V * 2.0, (sample_rows_kernel<ACCEPT, PEN, RULE, GUIDE, CLOSE>), dim3(B), dim3(SP_NT), SP_SMEM, st, a);
+               (double)B * a.V * 2.0, (sample_rows_kernel<ACCEPT, PEN, RULE, GUIDE, CLOSE, STEER>), dim3(B), dim3(SP_NT), SP_SMEM, st, a);
     return FO1_OK;
 }
 
@@ -567,6 +662,31 @@ static int check_guides(const char* who, const void* masks, const void* rules, c
 static int check_closes(const char* who, const void* close_row, long long n_close_row, const void* closes) {
     FO1_CHECK_ARG(close_row && n_close_row > 0, "%s: closing rules with close_row=%p n_close_row=%lld (a table of >= 1 entries)", who, close_row, n_close_row);
     FO1_CHECK_ARG((((uintptr_t)close_row | (uintptr_t)closes) & 3) == 0, "%s: misaligned closing table", who);
+    return FO1_OK;
+}
+
+// (row, id) pairs -> + 1 in the count table and the bit of the gate bitmap; ids outside [0, V) and negative rows are skipped.  Two counts share
+// a 32-bit word (rows start on a word: ld_counts is even), so duplicates add up through the word's atomic; a count stays far below 65 536
+// (at most IDS_CAP marks reach a row between two clears), so the low half never carries into the high one
+__global__ __launch_bounds__(256) void count_mark_kernel(uint32_t* __restrict__ counts, long long ld_count_words, uint32_t* __restrict__ gate,
+                                                              long long gate_ld_words, int V, const int* __restrict__ rows, const int* __restrict__ ids,
+                                                              int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int r = rows[i], t = ids[i];
+    if (r < 0 || t < 0 || t >= V) return;
+    atomicAdd(counts + (long long)r * ld_count_words + (t >> 1), 1u << (16 * (t & 1)));
+    atomicOr(gate + (long long)r * gate_ld_words + (t >> 5), 1u << (t & 31));
+}
+
+static int check_steers(const char* who, const void* bias, const void* bias_gate, int bias_rows, long long ld_bias, const void* counts,
+                        const void* count_gate, long long ld_counts, long long gate_ld_words, int V) {
+    FO1_CHECK_ARG(!bias == !bias_gate && !counts == !count_gate, "%s: a bias table and a count table come with their gate bitmaps", who);
+    FO1_CHECK_ARG(!(bias || counts) || (gate_ld_words % 4 == 0 && gate_ld_words >= ((long long)V + 31) / 32),
+                  "%s: gate_ld_words=%lld (a multiple of 4, >= ceil(n_vocab / 32) = %d)", who, gate_ld_words, (V + 31) / 32);
+    FO1_CHECK_ARG(!bias || (bias_rows > 0 && ld_bias >= V), "%s: bias_rows=%d ld_bias=%lld (>= 1 rows of >= n_vocab = %d entries)", who, bias_rows, ld_bias, V);
+    FO1_CHECK_ARG(!counts || (ld_counts >= V && ld_counts % 2 == 0), "%s: ld_counts=%lld (even, >= n_vocab = %d)", who, ld_counts, V);
+    FO1_CHECK_ARG(((uintptr_t)bias & 1) == 0 && (((uintptr_t)bias_gate | (uintptr_t)counts | (uintptr_t)count_gate) & 3) == 0, "%s: misaligned steer table", who);
     return FO1_OK;
 }
 
@@ -796,6 +916,105 @@ int fo1_decode_head_closing_accept(const void* logits, long long ld_logits, int 
     a.n_state_row = n_state_row; a.guides = guides; a.gstate = (int*)gstate;
     a.close_row = (const int*)close_row; a.n_close_row = n_close_row; a.closes = closes;
     return launch_sample<true, true, true, true, true>(a, B, (hipStream_t)stream);
+}
+
+// fo1_sample_rows_closing_bf16 with the rows' steers honoured (the head of this file; include/fo1.h): an additive bias row and the frequency /
+// presence penalties against the rows' counts.  steers == NULL: fo1_sample_rows_closing_bf16.  With steers, the rule / guide / closing tables
+// are optional, each level needing the one before it: no rules, rules, rules + guides, rules + guides + closing rules.
+int fo1_sample_rows_steered_bf16(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params, const int32_t* counter,
+                                 int counter_stride, const float* u, int32_t* out, void* workspace, size_t workspace_bytes, const uint32_t* seen,
+                                 long long ld_words, const uint32_t* masks, int mask_rows, long long mask_ld_words, const fo1_token_rule_t* rules,
+                                 void* stream, const uint16_t* cls, int cls_rows, long long ld_cls, const int32_t* next, long long n_next,
+                                 const int32_t* state_row, long long n_state_row, const fo1_token_guide_t* guides, int32_t* gstate,
+                                 const int32_t* close_row, long long n_close_row, const fo1_guide_close_t* closes, const int32_t* budget,
+                                 const void* bias, const uint32_t* bias_gate, int bias_rows, long long ld_bias, const uint16_t* counts,
+                                 const uint32_t* count_gate, long long ld_counts, long long gate_ld_words, const fo1_token_steer_t* steers) {
+    using namespace fo1;
+    if (!steers)
+        return fo1_sample_rows_closing_bf16(logits, ld_logits, n_vocab, B, params, counter, counter_stride, u, out, workspace, workspace_bytes, seen, ld_words,
+                                            masks, mask_rows, mask_ld_words, rules, stream, cls, cls_rows, ld_cls, next, n_next, state_row, n_state_row,
+                                            guides, gstate, close_row, n_close_row, closes, budget);
+    const char* who = "sample_rows_steered";
+    if (int rc = check_sample(who, logits, ld_logits, n_vocab, B, params, workspace, workspace_bytes)) return rc;
+    if (int rc = check_seen(who, seen, ld_words, n_vocab)) return rc;
+    if (int rc = check_masks(who, masks, mask_rows, mask_ld_words, n_vocab)) return rc;
+    if (int rc = check_steers(who, bias, bias_gate, bias_rows, ld_bias, counts, count_gate, ld_counts, gate_ld_words, n_vocab)) return rc;
+    FO1_CHECK_ARG(out != nullptr && ((uintptr_t)steers & 3) == 0, "sample_rows_steered: NULL out or misaligned steers");
+    FO1_CHECK_ARG(!closes || guides, "sample_rows_steered: closing rules need the rows' guides");
+    SampleArgs a{};
+    a.logits = (const uint16_t*)logits; a.ld = ld_logits; a.V = n_vocab; a.params = params; a.counter = (const int*)counter;
+    a.counter_stride = counter_stride; a.u = u; a.out = (int*)out; a.seen = const_cast<uint32_t*>(seen); a.ld_words = ld_words;
+    a.bias = (const uint16_t*)bias; a.bias_gate = bias_gate; a.bias_rows = bias_rows; a.ld_bias = ld_bias; a.counts = const_cast<uint16_t*>(counts);
+    a.count_gate = const_cast<uint32_t*>(count_gate); a.ld_counts = ld_counts; a.gate_ld_words = gate_ld_words; a.steers = steers;
+    if (!guides && (!masks || !rules)) return launch_sample<false, true, false, false, false, true>(a, B, (hipStream_t)stream);
+    a.masks = masks; a.mask_rows = mask_rows; a.mask_ld_words = mask_ld_words; a.rules = rules;
+    if (!guides) return launch_sample<false, true, true, false, false, true>(a, B, (hipStream_t)stream);
+    if (int rc = check_guides(who, masks, rules, cls, cls_rows, ld_cls, next, n_next, state_row, n_state_row, gstate, n_vocab)) return rc;
+    a.cls = cls; a.cls_rows = cls_rows; a.ld_cls = ld_cls; a.next = (const int*)next; a.n_next = n_next; a.state_row = (const int*)state_row;
+    a.n_state_row = n_state_row; a.guides = guides; a.gstate = (int*)gstate;
+    if (closes) {
+        if (int rc = check_closes(who, close_row, n_close_row, closes)) return rc;
+        FO1_CHECK_ARG(budget && ((uintptr_t)budget & 3) == 0, "sample_rows_steered: closing rules need the rows' budgets (device int32 [B])");
+        a.close_row = (const int*)close_row; a.n_close_row = n_close_row; a.closes = closes; a.budget = (const int*)budget;
+    }
+    return launch_sample<false, true, true, true, true, true>(a, B, (hipStream_t)stream);
+}
+
+// fo1_decode_head_closing_accept with the rows' steers honoured: the step reads the bias table, its gate and the steers and writes none of
+// them; it adds 1 to the accepted token's count of row b and sets its gate bit (when counts are given) — a finished row touches nothing.
+// steers == NULL: fo1_decode_head_closing_accept.
+int fo1_decode_head_steered_accept(const void* logits, long long ld_logits, int n_vocab, int B, const fo1_sample_params_t* params, int32_t* state,
+                                   int32_t* plan, int32_t* ids_out, int ids_ld, const int32_t* stop_ids, int n_stop, int32_t* done, void* workspace,
+                                   size_t workspace_bytes, uint32_t* seen, long long ld_words, const uint32_t* masks, int mask_rows,
+                                   long long mask_ld_words, const fo1_token_rule_t* rules, void* stream, const uint16_t* cls, int cls_rows,
+                                   long long ld_cls, const int32_t* next, long long n_next, const int32_t* state_row, long long n_state_row,
+                                   const fo1_token_guide_t* guides, int32_t* gstate, const int32_t* close_row, long long n_close_row,
+                                   const fo1_guide_close_t* closes, const void* bias, const uint32_t* bias_gate, int bias_rows, long long ld_bias,
+                                   uint16_t* counts, uint32_t* count_gate, long long ld_counts, long long gate_ld_words,
+                                   const fo1_token_steer_t* steers) {
+    using namespace fo1;
+    if (!steers)
+        return fo1_decode_head_closing_accept(logits, ld_logits, n_vocab, B, params, state, plan, ids_out, ids_ld, stop_ids, n_stop, done, workspace,
+                                              workspace_bytes, seen, ld_words, masks, mask_rows, mask_ld_words, rules, stream, cls, cls_rows, ld_cls, next,
+                                              n_next, state_row, n_state_row, guides, gstate, close_row, n_close_row, closes);
+    const char* who = "decode_head_steered_accept";
+    if (int rc = check_sample(who, logits, ld_logits, n_vocab, B, params, workspace, workspace_bytes)) return rc;
+    if (int rc = check_seen(who, seen, ld_words, n_vocab)) return rc;
+    if (int rc = check_masks(who, masks, mask_rows, mask_ld_words, n_vocab)) return rc;
+    if (int rc = check_steers(who, bias, bias_gate, bias_rows, ld_bias, counts, count_gate, ld_counts, gate_ld_words, n_vocab)) return rc;
+    FO1_CHECK_ARG(state && plan && ids_out && done && ids_ld > 0 && n_stop >= -1 && (n_stop == 0 || stop_ids), "decode_head_steered_accept: bad arguments");
+    FO1_CHECK_ARG(((uintptr_t)steers & 3) == 0, "decode_head_steered_accept: misaligned steers");
+    FO1_CHECK_ARG(!closes || guides, "decode_head_steered_accept: closing rules need the rows' guides");
+    SampleArgs a{};
+    a.logits = (const uint16_t*)logits; a.ld = ld_logits; a.V = n_vocab; a.params = params;
+    a.state = (int*)state; a.plan = (int*)plan; a.ids_out = (int*)ids_out; a.ids_ld = ids_ld; a.stop_ids = (const int*)stop_ids; a.n_stop = n_stop;
+    a.done = (int*)done; a.seen = seen; a.ld_words = ld_words;
+    a.bias = (const uint16_t*)bias; a.bias_gate = bias_gate; a.bias_rows = bias_rows; a.ld_bias = ld_bias; a.counts = counts;
+    a.count_gate = count_gate; a.ld_counts = ld_counts; a.gate_ld_words = gate_ld_words; a.steers = steers;
+    if (!guides && (!masks || !rules)) return launch_sample<true, true, false, false, false, true>(a, B, (hipStream_t)stream);
+    a.masks = masks; a.mask_rows = mask_rows; a.mask_ld_words = mask_ld_words; a.rules = rules;
+    if (!guides) return launch_sample<true, true, true, false, false, true>(a, B, (hipStream_t)stream);
+    if (int rc = check_guides(who, masks, rules, cls, cls_rows, ld_cls, next, n_next, state_row, n_state_row, gstate, n_vocab)) return rc;
+    a.cls = cls; a.cls_rows = cls_rows; a.ld_cls = ld_cls; a.next = (const int*)next; a.n_next = n_next; a.state_row = (const int*)state_row;
+    a.n_state_row = n_state_row; a.guides = guides; a.gstate = (int*)gstate;
+    if (closes) {
+        if (int rc = check_closes(who, close_row, n_close_row, closes)) return rc;
+        a.close_row = (const int*)close_row; a.n_close_row = n_close_row; a.closes = closes;
+    }
+    return launch_sample<true, true, true, true, true, true>(a, B, (hipStream_t)stream);
+}
+
+// Adds 1 to counts[rows[i]][ids[i]] and sets the matching gate bit for i < n (device int32 each; duplicates add up).  Ids outside [0, n_vocab)
+// and negative rows are skipped; the caller vouches for rows[i] < the tables' rows.
+int fo1_count_mark(uint16_t* counts, long long ld_counts, uint32_t* count_gate, long long gate_ld_words, int n_vocab, const int32_t* rows,
+                   const int32_t* ids, int n, void* stream) {
+    using namespace fo1;
+    FO1_CHECK_ARG(counts && count_gate && n >= 0 && n_vocab >= 1 && (n == 0 || (rows && ids)), "count_mark: bad arguments");
+    if (int rc = check_steers("count_mark", nullptr, nullptr, 0, 0, counts, count_gate, ld_counts, gate_ld_words, n_vocab)) return rc;
+    if (n == 0) return FO1_OK;
+    FO1_LAUNCH("count_mark", (double)n * 16.0, count_mark_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+               reinterpret_cast<uint32_t*>(counts), ld_counts / 2, count_gate, gate_ld_words, n_vocab, (const int*)rows, (const int*)ids, n);
+    return FO1_OK;
 }
 
 // Sets bit ids[i] of row rows[i] of the seen bitmap for i < n (device int32 each; duplicates are fine).  Ids outside [0, n_vocab) and negative

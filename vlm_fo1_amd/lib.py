@@ -298,6 +298,18 @@ SIGNATURES = {
                                                c_void_p, c_void_p, c_size_t, c_void_p, c_longlong, c_void_p, c_int, c_longlong, c_void_p, c_void_p,
                                                c_void_p, c_int, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p,
                                                c_void_p, c_longlong, c_void_p]),
+    # the _closing entries' lists + (bias, bias_gate, bias_rows, ld_bias, counts, count_gate, ld_counts, gate_ld_words, steers)
+    "fo1_sample_rows_steered_bf16": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
+                                             c_longlong, c_void_p, c_int, c_longlong, c_void_p, c_void_p,
+                                             c_void_p, c_int, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p,
+                                             c_void_p, c_longlong, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_int, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong, c_void_p]),
+    "fo1_decode_head_steered_accept": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                               c_void_p, c_void_p, c_size_t, c_void_p, c_longlong, c_void_p, c_int, c_longlong, c_void_p, c_void_p,
+                                               c_void_p, c_int, c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p,
+                                               c_void_p, c_longlong, c_void_p,
+                                               c_void_p, c_void_p, c_int, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong, c_void_p]),
+    "fo1_count_mark": (c_int, [c_void_p, c_longlong, c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "fo1_logprob_rows_bf16": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
     "fo1_decode_logprob_record": (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p]),

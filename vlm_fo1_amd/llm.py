@@ -700,7 +700,8 @@ def sampling_table(sampling, B: int):
     too: dict(greedy=True, ban=[...]) is a constrained greedy sequence; so is a dict with a guide (guide=TokenGuide: sampling_guides)."""
     per = _per_sequence(sampling, B)
     rows = [ops.sampling_row(sp, b) for b, sp in enumerate(per)]
-    kinds = ["plain" if sp is None else ("general" if (r[5] or ops.penalty_on(r[6]) or has_rule(sp) or has_guide(sp)) else "sampled") for sp, r in zip(per, rows)]
+    kinds = ["plain" if sp is None else ("general" if (r[5] or ops.penalty_on(r[6]) or has_rule(sp) or has_guide(sp) or has_steer(sp)) else "sampled")
+             for sp, r in zip(per, rows)]
     return rows, kinds
 
 
@@ -729,6 +730,168 @@ def has_rule(sp: Optional[dict]) -> bool:
 
 def has_guide(sp: Optional[dict]) -> bool:
     return sp is not None and sp.get("guide") is not None
+
+
+STEER_KEYS = ("bias", "frequency_penalty", "presence_penalty")      # the soft-steering keys of a sequence's sampling dict (token_steer)
+
+
+def _penalty_value(v, what: str) -> float:
+    """A frequency / presence penalty as the fp32 value the device reads: None = 0 = off; ValueError for a bool, a non-number or a value that
+    is not finite as fp32."""
+    if v is None:
+        return 0.0
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{what}: a finite number (got {v!r})")
+    with np.errstate(over="ignore"):
+        f = float(np.float32(v))
+    if not math.isfinite(f):
+        raise ValueError(f"{what}: a finite fp32 number (got {v!r})")
+    return f
+
+
+def has_steer(sp: Optional[dict]) -> bool:
+    """Does the dict ask for a bias or a count penalty?  An empty or all-zero bias and penalties of 0 / None are "off": such a dict is planned
+    exactly as one without the keys."""
+    if sp is None:
+        return False
+    b = sp.get("bias")
+    if b is not None and not hasattr(b, "items"):
+        return True      # (token_steer raises on it)
+    if b and any(isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or v != 0 for v in b.values()):
+        return True
+    return any(sp.get(k) is not None and (isinstance(sp.get(k), bool) or sp.get(k) != 0) for k in STEER_KEYS[1:])
+
+
+class TokenSteer(NamedTuple):
+    """A sequence's normalised steer (include/fo1.h, fo1_token_steer_t): `bias` is its row of the bias table — ops.count_words(V) bf16 bit
+    patterns as bytes, each value rounded once to bf16, zero elsewhere — or None; f and q are the frequency and presence penalties as fp32."""
+    bias: Optional[bytes]
+    f: float
+    q: float
+
+    @property
+    def counting(self) -> bool:
+        return ops.count_penalty_on(self.f, self.q)
+
+
+def bf16_bits(x) -> np.ndarray:
+    """float32 values -> bf16 bit patterns, round to nearest even (NaN stays NaN)."""
+    x = np.asarray(x, dtype=np.float32)
+    u = x.view(np.uint32).astype(np.uint64)
+    r = ((u + 0x7fff + ((u >> 16) & 1)) >> 16).astype(np.uint32)
+    return np.where(np.isnan(x), 0x7fc0, r).astype(np.uint16)
+
+
+def token_steer(spec: Optional[dict], V: int) -> Optional[TokenSteer]:
+    """The soft-steering keys of a sequence's sampling dict -> its TokenSteer, or None for a dict without one (has_steer):
+      bias={id: value}        added to the token's logit before the repetition penalty: x = bf16(fp32(l) + fp32(bf16(value)));
+      frequency_penalty=f     f times the number of times the sequence has generated the token is subtracted, after the penalty;
+      presence_penalty=q      q is subtracted once the sequence has generated the token at all.
+    ValueError: an id that is not an integer or lies outside [0, V), a value that is not a number or not finite once rounded to bf16 (to
+    forbid a token use `ban`, to force one `allow`), a penalty that is a bool or not finite as fp32."""
+    if not has_steer(spec):
+        return None
+    V = int(V)
+    b = spec.get("bias")
+    row = None
+    if b is not None:
+        if not hasattr(b, "items"):
+            raise ValueError(f"bias: a dict {{token id: value}} (got {type(b).__name__})")
+        ids = _token_ids(list(b.keys()), V, "bias")
+        vals = []
+        for t, v in zip(ids, b.values()):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError(f"bias: the value of token {t} is a number (got {v!r})")
+            with np.errstate(over="ignore"):
+                vals.append(np.float32(v))
+        bits = bf16_bits(np.array(vals, dtype=np.float32))
+        bad = [t for t, h in zip(ids, bits) if (int(h) & 0x7f80) == 0x7f80]
+        if bad:
+            raise ValueError(f"bias: the value of token {bad[0]} is not finite as bf16 ({b[list(b.keys())[ids.index(bad[0])]]!r}); "
+                             f"to forbid a token use `ban`, to force a set of tokens `allow`")
+        if any(int(h) & 0x7fff for h in bits):
+            full = np.zeros(ops.count_words(V), dtype=np.uint16)
+            full[ids] = bits
+            row = full.tobytes()
+    f = _penalty_value(spec.get("frequency_penalty"), "frequency_penalty")
+    q = _penalty_value(spec.get("presence_penalty"), "presence_penalty")
+    if row is None and not ops.count_penalty_on(f, q):
+        return None
+    return TokenSteer(row, f, q)
+
+
+def sampling_steers(sampling, B: int, V: int) -> List[Optional[TokenSteer]]:
+    """sampling_table's argument -> the TokenSteer (or None) of every sequence."""
+    return [token_steer(sp, V) for sp in _per_sequence(sampling, B)]
+
+
+class BiasTable:
+    """Device side of the logit biases of a decoder's rows: the bias table bf16 [rows, count_words(V)], its gate bitmap int32 [rows,
+    seen_words(V)] (a set bit = a non-zero entry) and a host map from a bias row's bytes to its table row with a user count.  Equal biases
+    share a row; a row with users is never rewritten (a captured step reads the table, it never writes it).  Allocated by the first biased
+    sequence, as the mask table is by the first constrained one.  dev=None keeps the bookkeeping alone (no tables)."""
+
+    def __init__(self, rows: int, n_vocab: int, dev):
+        self.rows, self.V = rows, int(n_vocab)
+        self.table = self.gate = None
+        if dev is not None:
+            with torch.inference_mode(False):
+                self.table = torch.zeros(rows, ops.count_words(n_vocab), dtype=torch.bfloat16, device=dev)
+                self.gate = torch.zeros(rows, ops.seen_words(n_vocab), dtype=torch.int32, device=dev)
+        self._row: Dict[bytes, int] = {}
+        self.users = [0] * rows
+        self._keep: list = []
+
+    def room(self, biases: Sequence[bytes]) -> bool:
+        """Is there a row for every one of these bias rows (its own, or one without users)?"""
+        new = {m for m in biases if m not in self._row}
+        taken = {self._row[m] for m in biases if m in self._row}
+        return len(new) <= sum(1 for r in range(self.rows) if self.users[r] == 0 and r not in taken)
+
+    def gate_of(self, bias: bytes) -> np.ndarray:
+        """The gate bitmap of a bias row: uint32 [seen_words(V)], bit i set iff entry i is not zero (-0 counts as zero)."""
+        nz = (np.frombuffer(bias, dtype=np.uint16)[:self.V] & 0x7fff) != 0
+        out = np.zeros(ops.seen_words(self.V) * 4, dtype=np.uint8)
+        pk = np.packbits(nz, bitorder="little")
+        out[:pk.size] = pk
+        return out.view(np.uint32)
+
+    def acquire(self, bias: bytes) -> int:
+        """The row holding `bias`, one user more; a new bias is uploaded (current stream) into a row without users."""
+        if len(bias) != ops.count_words(self.V) * 2:
+            raise ValueError(f"BiasTable: a bias row has {ops.count_words(self.V) * 2} bytes (got {len(bias)})")
+        row = self._row.get(bias)
+        if row is None:
+            held = set(self._row.values())
+            free = [r for r in range(self.rows) if self.users[r] == 0 and r not in held] or [r for r in range(self.rows) if self.users[r] == 0]
+            if not free:
+                raise RuntimeError(f"BiasTable: {self.rows} different logit-bias vectors are live; wait for sequences to finish")
+            row = free[0]
+            for k in [k for k, v in self._row.items() if v == row]:
+                del self._row[k]
+            if self.table is not None:
+                host = torch.frombuffer(bytearray(bias), dtype=torch.int16).view(1, -1)
+                gate = torch.from_numpy(self.gate_of(bias).view(np.int32).copy()).view(1, -1)
+                self.table.view(torch.int16)[row:row + 1].copy_(host, non_blocking=True)
+                self.gate[row:row + 1].copy_(gate, non_blocking=True)
+                self._keep += [host, gate]
+                if len(self._keep) > 4 * self.rows:
+                    del self._keep[:len(self._keep) - 4 * self.rows]
+            self._row[bias] = row
+        self.users[row] += 1
+        return row
+
+    def release(self, row: int) -> None:
+        if row >= 0:
+            assert self.users[row] > 0
+            self.users[row] -= 1
+
+
+def new_counts(rows: int, n_vocab: int, dev):
+    """(counts int16 [rows, count_words(V)] holding the uint16 counts, count_gate int32 [rows, seen_words(V)]), zeroed."""
+    with torch.inference_mode(False):
+        return (torch.zeros(rows, ops.count_words(n_vocab), dtype=torch.int16, device=dev),
+                torch.zeros(rows, ops.seen_words(n_vocab), dtype=torch.int32, device=dev))
 
 
 class TokenRule(NamedTuple):
@@ -1301,6 +1464,11 @@ class BatchDecoder:
         self._guide_keys: list = []          # guide-table entries the current start() holds
         self.closes = None         # budget-aware guides: the per-row fo1_guide_close_t table, allocated by the first start() with a closing guide
         self.closing = False       # some row of the current start() has a closing rule: the guided head runs in its closing form
+        self.btab = None           # soft steering: the bias table (BiasTable) and the per-row fo1_token_steer_t table, allocated by the first
+        self.steers = None         # start() with a steer; the count table and its gate by the first start() with a count penalty
+        self.counts = self.count_gate = None
+        self.steered = False       # some row of the current start() has a steer: the general head runs in its steered form
+        self._bias_rows: List[int] = []      # bias rows the current start() holds
         self.lp_want: List[int] = []       # per sequence of the current start(): -1 = no record, else its top-n
         self.n_stop = 0
         self.dk = self.dvt = None
@@ -1341,6 +1509,9 @@ class BatchDecoder:
         function of the sequence's automaton state, which the head advances on the device; its table rows are held until the next start() too.
         A guide with accepting states closes before max_new_tokens runs out (guide.closing_bitmaps): the head reads the tokens left from the
         row's decode state; a start state further from an accepting one than the budget is a ValueError.
+        A dict's steer keys (bias, frequency_penalty, presence_penalty: token_steer) bias that sequence's logits on the device and penalise
+        the tokens it has generated, the first token included, by their counts (the head keeps them); the bias rows are held until the next
+        start().
         logprobs (logprob_wants): None, one int or a list with None / int per sequence = the top-n of the log-probability record kept for that
         sequence (logprobs()); orthogonal to `sampling`: the record launch follows whichever head the step ends in.  first_logprobs: the first
         tokens' records, ops.logprob_rows on the prefill's logits with the largest requested n (FO1Engine._first_logprobs)."""
@@ -1376,12 +1547,14 @@ class BatchDecoder:
         srows, kinds = sampling_table(sampling, B)
         trules = sampling_rules(sampling, B, llm.cfg.vocab_size)
         gplans = sampling_guides(sampling, B, llm.cfg.vocab_size, trules, prompt_ids, budget=max_new)
+        tsteers = sampling_steers(sampling, B, llm.cfg.vocab_size)
         self.sampled = any(k != "plain" for k in kinds)
         self.general = self.sampled and any(k != "sampled" for k in kinds)
         penalised = any(ops.penalty_on(r[6]) for r in srows)
         if penalised and (prompt_ids is None or len(prompt_ids) != B):
             raise ValueError("BatchDecoder: a repetition penalty needs prompt_ids, one list per sequence")
         self._start_rules(unguided_rules(trules, gplans), gplans, first_tokens)
+        self._start_steers(tsteers)
         if self.sampled:
             sp = ops.sample_params(srows)
             self.sparams[:B].copy_(sp, non_blocking=True)
@@ -1403,6 +1576,12 @@ class BatchDecoder:
                 rt = torch.arange(B, dtype=torch.int32)
                 self._keep.append(rt)
                 ops.seen_mark(self.seen, llm.cfg.vocab_size, rt.to(first.device, non_blocking=True), first)
+            if self.steered and any(t is not None and t.counting for t in tsteers):      # the counts: zero, then the first tokens
+                self.counts[:B].zero_()
+                self.count_gate[:B].zero_()
+                ct = torch.arange(B, dtype=torch.int32)
+                self._keep.append(ct)
+                ops.count_mark(self.counts, self.count_gate, llm.cfg.vocab_size, ct.to(first.device, non_blocking=True), first)
 
     GUIDE_MASKS = 64         # mask rows kept for the guides' state bitmaps, beside the 3 per sequence of the rules
 
@@ -1436,6 +1615,41 @@ class BatchDecoder:
         self._keep.append(rt)
         if self.guided:
             self._start_guides(gplans, first_tokens)
+
+    def _start_steers(self, tsteers):
+        """The previous run's bias rows go back; this run's steers take theirs (one row per sequence at most: there is always room).  The
+        count table is allocated by the first run with a count penalty; start() zeroes its rows and counts the first tokens."""
+        if self.btab is not None:
+            for r in self._bias_rows:
+                self.btab.release(r)
+        self._bias_rows = []
+        self.steered = any(t is not None for t in tsteers)
+        if not self.steered:
+            return
+        V, dev = self.llm.cfg.vocab_size, self.llm.dev
+        if self.btab is None:
+            self.btab = BiasTable(self.MAX_BATCH, V, dev)
+            with torch.inference_mode(False):
+                self.steers = ops.token_steers([None] * self.MAX_BATCH, dev)
+        if self.counts is None and any(t is not None and t.counting for t in tsteers):
+            self.counts, self.count_gate = new_counts(self.MAX_BATCH, V, dev)
+        table = []
+        for t in tsteers:
+            if t is None:
+                table.append(None)
+                continue
+            row = -1 if t.bias is None else self.btab.acquire(t.bias)
+            if row >= 0:
+                self._bias_rows.append(row)
+            table.append((row, t.f, t.q))
+        st = ops.token_steers(table)
+        self.steers[:len(table)].copy_(st, non_blocking=True)
+        self._keep.append(st)
+
+    def _steer_args(self) -> dict:
+        if not self.steered:
+            return {}
+        return dict(steer=ops.SteerOperands(self.steers[:self.B], self.btab.table, self.btab.gate, self.counts, self.count_gate))
 
     def _start_guides(self, gplans, first_tokens):
         if self.gtab is None:
@@ -1513,7 +1727,7 @@ class BatchDecoder:
             logits = ops.gemv_batch(x, llm.lm_head, norm_weight=llm.norm, norm_eps=c.rms_norm_eps)
             if self.general:
                 ops.decode_head_accept(logits, self.sparams[:B], st, self.plan[:B], self.ids[:B], self.stop[:self.n_stop], self.done, seen=self.seen,
-                                       **self._rule_args())
+                                       **self._rule_args(), **self._steer_args())
             elif self.sampled:
                 ops.decode_sample_accept(logits, self.sparams[:B], st, self.plan[:B], self.ids[:B], self.stop[:self.n_stop], self.done)
             else:
@@ -1548,6 +1762,10 @@ class BatchDecoder:
                 seen += (self.gstate,)
             if self.closing:  # (the closing form reads two more tables and writes neither: nothing more to roll back)
                 key += ("closing", self.gtab.close_row.data_ptr(), self.closes.data_ptr())
+            if self.steered:  # (the steered form reads the bias table and the steers and counts the accepted tokens: the counts join the rollback)
+                key += ("steered", self.btab.table.data_ptr(), self.steers.data_ptr(), self.counts.data_ptr() if self.counts is not None else 0)
+                if self.counts is not None:
+                    seen += (self.counts, self.count_gate)
         if self.recording:   # (and one more: the record launch bakes the buffers' identity in, and the warm-up step writes them)
             key += ("logprobs", self.lpb.lp.data_ptr())
             seen += self.lpb.written()
@@ -1638,6 +1856,7 @@ class DecodePool:
     MAX_STOP = 16
     MAX_SETS = 32            # distinct stop-id sets live in the pool at once
     MAX_MASKS = 64           # distinct token masks (rows of the mask table) live in the pool at once
+    MAX_BIAS = 16            # distinct logit-bias vectors (rows of the bias table) live in the pool at once
     KV_BUCKET = 256          # the attention launch geometry follows the longest live context rounded up to this many keys
 
     def __init__(self, llm: QwenLLM, slots: int = 128, slot_rows: int = 1024):
@@ -1675,6 +1894,13 @@ class DecodePool:
         self.close_dev = [False] * P                   # closing sequence joins; does the slot's row on the device hold depth > 0 (as `kind`)
         self.slot_close = [False] * P                  # a live slot's guide has a closing rule
         self.n_closing = 0                             # live slots with a closing rule: > 0 runs the guided head in its closing form
+        self.btab = None                               # soft steering: the bias table (BiasTable) and the per-slot fo1_token_steer_t table, allocated
+        self.steers = None                             # when the first steered sequence joins; the count table and its gate when the first
+        self.counts = self.count_gate = None           # sequence with a count penalty does
+        self.steer_dev = [False] * P                   # does the slot's steer row on the device hold a steer (tracked as `kind` is)
+        self.slot_bias = [-1] * P                      # the bias row a live slot holds
+        self.slot_steer = [False] * P                  # a live slot has a steer
+        self.n_steered = 0                             # live slots with a steer: > 0 runs the general head in its steered form
         self.lpb = None                                # log-probability records (LogprobBuffers), allocated when the first requesting sequence joins
         self.lp_want = [-1] * P                        # a live slot's request: -1 = no record, else its top-n
         self.lp_dev = [-1] * P                         # what each slot's `want` word on the device holds (tracked as `kind` is)
@@ -1744,6 +1970,10 @@ class DecodePool:
         A guide with accepting states closes before max_new_tokens runs out (guide.closing_bitmaps): its (state, tokens left) bitmaps take
         mask rows too, the head reads the tokens left from the slot's decode state, and a start state further from an accepting one than
         the budget is a ValueError.  While no such sequence is live the step is the guided (or ruled, or general, or greedy) one.
+        A dict's steer keys (bias, frequency_penalty, presence_penalty: token_steer) bias that sequence's logits and penalise the tokens it
+        has generated by their counts: equal bias vectors share a row of the bias table, at most MAX_BIAS distinct ones are live at once
+        (can_take), and the row is released when the sequence is harvested; the slot's count row is zeroed here and the first token counted.
+        While no steered sequence is live the step is the one it was.
         logprobs / first_logprobs: as BatchDecoder.start takes them; while any live slot asks for a record the record launch follows the head
         (step()), and harvest(records=True) hands the finished slots' records out.  A pool no requesting sequence ever joined holds no
         record buffer and issues exactly the launches and copies it always has."""
@@ -1756,10 +1986,11 @@ class DecodePool:
         max_new = token_budget(max_new_tokens, self.IDS_CAP, "DecodePool")
         gplans = sampling_guides(sampling, B, self.llm.cfg.vocab_size, trules, prompt_ids, budget=max_new)
         trules = unguided_rules(trules, gplans)
+        tsteers = sampling_steers(sampling, B, self.llm.cfg.vocab_size)
         penalised = [ops.penalty_on(r[6]) for r in srows]
         if any(penalised) and (prompt_ids is None or len(prompt_ids) != B):
             raise ValueError("DecodePool: a repetition penalty needs prompt_ids, one list per sequence")
-        full = self._table_without_room(trules, gplans)
+        full = self._table_without_room(trules, gplans, tsteers)
         if full is not None:
             raise RuntimeError(f"DecodePool: {full}; wait for sequences to finish")
         set_row = self._stop_set_row(tuple(stop_id_list(stop_ids, self.MAX_STOP, "DecodePool")))
@@ -1774,6 +2005,7 @@ class DecodePool:
             self._join_sampling(slots, srows, kinds, penalised, first_tokens, prompt_ids)
             self._join_rules(slots, trules)
             self._join_guides(slots, gplans, first_tokens)
+            self._join_steers(slots, tsteers, first_tokens)
             self._join_logprobs(slots, wants, first_logprobs)
         except BaseException:
             # nothing of this submission is live: its slots go back (their device state may be half written — the next occupant's
@@ -1789,6 +2021,7 @@ class DecodePool:
             for s in slots:
                 self._release_masks(s)
                 self._release_guide(s)
+                self._release_bias(s)
             raise
         for k, s in enumerate(slots):
             # a tag identifies ONE occupancy of a slot: harvest() compares it by identity against an older snapshot, so the default must
@@ -1803,6 +2036,8 @@ class DecodePool:
             self.n_guided += gplans[k] is not None
             self.slot_close[s] = gplans[k] is not None and gplans[k].depth > 0
             self.n_closing += self.slot_close[s]
+            self.slot_steer[s] = tsteers[k] is not None
+            self.n_steered += self.slot_steer[s]
             self.lp_want[s] = wants[k]
             self.n_logprob += wants[k] >= 0
         return slots
@@ -1819,9 +2054,12 @@ class DecodePool:
         for k in write:
             self.lp_dev[slots[k]] = wants[k]
 
-    def _table_without_room(self, trules, gplans=()) -> Optional[str]:
-        """None when there is a mask row for every banned set of the rules and every state bitmap of the guides and room in the guide tables;
-        else which table is full."""
+    def _table_without_room(self, trules, gplans=(), tsteers=()) -> Optional[str]:
+        """None when there is a mask row for every banned set of the rules and every state bitmap of the guides, room in the guide tables and
+        a bias row for every bias vector of the steers; else which table is full."""
+        biases = [t.bias for t in tsteers if t is not None and t.bias is not None]
+        if biases and not (self.btab.room(biases) if self.btab is not None else len(set(biases)) <= self.MAX_BIAS):
+            return f"{self.MAX_BIAS} different logit-bias vectors are live"
         maps = [m for t in trules if t is not None for m in t.bitmaps()]
         if any(g is not None for g in gplans):      # (nothing allocated yet: the same answers from the bookkeeping alone)
             gtab = self.gtab if self.gtab is not None else GuideTables(self.llm.cfg.vocab_size, None, None)
@@ -1832,8 +2070,51 @@ class DecodePool:
             return None
         return f"{self.MAX_MASKS} different token masks are live"
 
-    def _mask_room(self, trules, gplans=()) -> bool:
-        return self._table_without_room(trules, gplans) is None
+    def _mask_room(self, trules, gplans=(), tsteers=()) -> bool:
+        return self._table_without_room(trules, gplans, tsteers) is None
+
+    def _join_steers(self, slots, tsteers, first_tokens):
+        """The steer rows, bias rows and count rows of a submission's slots.  Nothing is enqueued for a sequence without a steer whose slot
+        holds none: a slot a steered sequence has left gets the "none" row back when an unsteered one reuses it."""
+        write = [k for k, s in enumerate(slots) if tsteers[k] is not None or self.steer_dev[s]]
+        if not write:
+            return
+        V, dev = self.llm.cfg.vocab_size, self.llm.dev
+        if self.btab is None:      # (graphs captured before are unreachable for a steered step: its key holds the tables' identity)
+            self.btab = BiasTable(self.MAX_BIAS, V, dev)
+            with torch.inference_mode(False):
+                self.steers = ops.token_steers([None] * self.P, dev)
+        counting = [k for k in write if tsteers[k] is not None and tsteers[k].counting]
+        if counting and self.counts is None:
+            self.counts, self.count_gate = new_counts(self.P, V, dev)
+        table = []
+        for k in write:
+            t = tsteers[k]
+            if t is None:
+                table.append(None)
+                continue
+            row = -1 if t.bias is None else self.btab.acquire(t.bias)
+            self.slot_bias[slots[k]] = row
+            table.append((row, t.f, t.q))
+        st = ops.token_steers(table)
+        self._keep.append(st)
+        for j, k in enumerate(write):
+            self.steers[slots[k]:slots[k] + 1].copy_(st[j:j + 1], non_blocking=True)
+            self.steer_dev[slots[k]] = tsteers[k] is not None
+        if counting:      # a counting slot's row starts from zero, then its first token
+            for k in counting:
+                self.counts[slots[k]].zero_()
+                self.count_gate[slots[k]].zero_()
+            first = first_tokens.to(torch.int32).contiguous()
+            rt = torch.tensor([slots[k] if k in counting else -1 for k in range(len(slots))], dtype=torch.int32)      # (row -1: skipped)
+            self._keep.append(rt)
+            with ops.workspace_scope(self._ws_owner):
+                ops.count_mark(self.counts, self.count_gate, V, rt.to(first.device, non_blocking=True), first)
+
+    def _release_bias(self, slot: int) -> None:
+        if self.slot_bias[slot] >= 0:
+            self.btab.release(self.slot_bias[slot])
+            self.slot_bias[slot] = -1
 
     def _ensure_masks(self):
         if self.masks is None:      # (graphs captured before are unreachable for a ruled step: its key holds the tables' identity)
@@ -1938,7 +2219,8 @@ class DecodePool:
 
     def can_take(self, stop_ids: Sequence[int], sampling=None, B: int = 0) -> bool:
         """Is there a table row for this stop-id set (its own, or one no live slot uses) — and, for a submission of B sequences with
-        `sampling`, a mask-table row for every banned set of its token rules?  (A malformed rule answers True: join() raises it.)"""
+        `sampling`, a mask-table row for every banned set of its token rules and a bias-table row for every bias vector of its steers?  (A
+        malformed rule or steer answers True: join() raises it.)"""
         key = tuple(sorted(set(int(t) for t in stop_ids)))
         if not (key in self._sets or any(u == 0 for u in self._set_users)):
             return False
@@ -1952,6 +2234,9 @@ class DecodePool:
                 if g is not None and not isinstance(g, TokenGuide):
                     raise ValueError("guide: not a TokenGuide")
                 gplans.append(None if g is None else guide_plan(g, always, g.start))
+            tsteers = sampling_steers(sampling, B, self.llm.cfg.vocab_size)
+            if self._table_without_room((), (), tsteers) is not None and self.btab is not None and any(self.btab.users):
+                return False
             return self._mask_room(unguided_rules(trules, gplans), gplans) or self.masks is None or not any(self.masks.users)
         except ValueError:
             return True
@@ -2044,6 +2329,8 @@ class DecodePool:
                 key += ("guided", self.masks.table.data_ptr(), self.rules.data_ptr(), *self.gtab.pointers(), self.guides.data_ptr(), self.gstate.data_ptr())
             if self.n_closing > 0:    # (the closing form reads two more tables and writes neither: nothing more joins the rollback)
                 key += ("closing", self.gtab.close_row.data_ptr(), self.closes.data_ptr())
+            if self.n_steered > 0:    # (the steered form reads the bias table and the steers and counts the accepted tokens: the counts join the rollback)
+                key += ("steered", self.btab.table.data_ptr(), self.steers.data_ptr(), self.counts.data_ptr() if self.counts is not None else 0)
         if self.n_logprob > 0:
             key += ("logprobs", self.lpb.lp.data_ptr())
         return key
@@ -2092,6 +2379,8 @@ class DecodePool:
                 rule = dict(masks=self.masks.table, rules=self.rules) if self.n_ruled > 0 or self.n_guided > 0 else {}
                 if self.n_guided > 0:
                     rule["guide"] = self.gtab.operands(self.guides, self.gstate, self.closes if self.n_closing > 0 else None)
+                if self.n_steered > 0:
+                    rule["steer"] = ops.SteerOperands(self.steers, self.btab.table, self.btab.gate, self.counts, self.count_gate)
                 ops.decode_head_accept(logits, self.sparams, st, self.plan, self.ids, self.stop, self.done, seen=self.seen, per_sequence_sets=True, **rule)
             else:
                 ops.decode_argmax_accept(logits, None, st, self.plan, self.ids, self.stop, self.done, per_sequence_sets=True)
@@ -2120,6 +2409,8 @@ class DecodePool:
                 roll += (self.seen,)
             if general and self.n_guided > 0:      # or the first replay would start from the warm-up step's states, not the ones join() set
                 roll += (self.gstate,)
+            if general and self.n_steered > 0 and self.counts is not None:      # the warm-up step counted its picks
+                roll += (self.counts, self.count_gate)
             if record:
                 roll += self.lpb.written()
             ent = self._graphs.get(key)
@@ -2183,6 +2474,9 @@ class DecodePool:
                 self._release_guide(s)
                 self.n_closing -= self.slot_close[s]
                 self.slot_close[s] = False
+                self.n_steered -= self.slot_steer[s]
+                self.slot_steer[s] = False
+                self._release_bias(s)
         return out
 
     def drain(self, use_graph: bool = True, poll: int = 8, records: bool = False) -> List[tuple]:

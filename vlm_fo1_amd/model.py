@@ -537,9 +537,11 @@ class FO1Engine:
         state for a ban_sequences guide), and the device word holding the state after it is put into the request's dict as `guide_state`, which
         BatchDecoder.start / DecodePool.join copy into their own state array — no host read.  A guide with accepting states
         (guide.closing_bitmaps) goes to the closing form with budget = max_new_tokens for every row: the first pick already closes under it
-        (max_new_tokens = 1 leaves only a token after which the answer is closed); such a guide without max_new_tokens is a ValueError."""
-        from .llm import (BatchDecoder, GuideTables, PassTables, TokenMasks, new_seen, sampling_guides, sampling_rules, sampling_table,
-                          unguided_rules)
+        (max_new_tokens = 1 leaves only a token after which the answer is closed); such a guide without max_new_tokens is a ValueError.
+        A request's steer (llm.token_steer) goes to the steered form on top of those: its bias through a scratch bias table; nothing has been
+        generated yet, so the count penalties have nothing to subtract and the launch takes no count table."""
+        from .llm import (BatchDecoder, BiasTable, GuideTables, PassTables, TokenMasks, new_seen, sampling_guides, sampling_rules,
+                          sampling_steers, sampling_table, unguided_rules)
         n = len(requests)
         rows, kinds = sampling_table(per, n)
         trules = sampling_rules(per, n, self.cfg.llm.vocab_size)
@@ -547,6 +549,7 @@ class FO1Engine:
         gplans = sampling_guides(per, n, self.cfg.llm.vocab_size, trules, [r["ids"] for r in requests], budget=budget)
         trules = unguided_rules(trules, gplans)
         guided = any(g is not None for g in gplans)
+        tsteers = sampling_steers(per, n, self.cfg.llm.vocab_size)
         if all(k == "plain" for k in kinds):
             return self._last_next_tokens[:n]
         with ops.workspace_scope(self._ws_owner):
@@ -559,35 +562,53 @@ class FO1Engine:
                     self._seen_scratch = new_seen(max(n, self.PREFILL_MAX), self.cfg.llm.vocab_size, self.dev)
                 seen = self._seen_scratch
                 self._seen_keep = ops.mark_prompts(seen, self.cfg.llm.vocab_size, list(range(n)), [r["ids"] for r in requests])
-            rule = {}
-            if guided or any(t is not None for t in trules):
-                tm = getattr(self, "_mask_scratch", None)
-                if tm is None or tm.rows < 3 * n + self.GUIDE_MASKS:
-                    tm = self._mask_scratch = TokenMasks(3 * max(n, self.PREFILL_MAX) + self.GUIDE_MASKS, self.cfg.llm.vocab_size, self.dev)
-                    self._guide_scratch = None
-                gt = getattr(self, "_guide_scratch", None)
-                if guided and gt is None:
-                    gt = self._guide_scratch = GuideTables(self.cfg.llm.vocab_size, self.dev, tm)
-                # every row of the pass, the rules' and the guides', is held until the launch is enqueued (the next pass's uploads are
-                # ordered behind it: same stream): a row given back earlier could be rewritten by a later acquire of this same pass
-                held = PassTables(tm, gt, trules, gplans)
-                try:
-                    rule = dict(masks=tm.table, rules=ops.token_rules(held.rules, self.dev))
-                    if guided:
-                        gstate = torch.tensor([0 if g is None else g.s0 for g in gplans], dtype=torch.int32).to(self.dev)
-                        close = {}
-                        if held.closes is not None:
-                            close = dict(closes=ops.guide_closes(held.closes, self.dev),
-                                         budget=torch.full((n,), budget, dtype=torch.int32).to(self.dev))
-                        rule["guide"] = gt.operands(ops.token_guides(held.guides, self.dev), gstate, **close)
-                    out = ops.sample_rows(self._last_logits[:n], table, seen=seen, general=True, **rule)
-                finally:
-                    held.release()
-                for k, g in enumerate(gplans):      # (the state words stay with the requests)
-                    if g is not None:
-                        per[k]["guide_state"] = gstate[k:k + 1]
-                return out
-            return ops.sample_rows(self._last_logits[:n], table, seen=seen, general=True)
+            steer, bias_rows = {}, []
+            if any(t is not None for t in tsteers):
+                bt = getattr(self, "_bias_scratch", None)
+                if bt is None or bt.rows < n:
+                    bt = self._bias_scratch = BiasTable(max(n, self.PREFILL_MAX), self.cfg.llm.vocab_size, self.dev)
+                # (the rows are held until the launch is enqueued, as the mask rows below are)
+                bias_rows = [-1 if t is None or t.bias is None else bt.acquire(t.bias) for t in tsteers]
+                table_s = ops.token_steers([None if t is None else (r, t.f, t.q) for t, r in zip(tsteers, bias_rows)], self.dev)
+                steer = dict(steer=ops.SteerOperands(table_s, bt.table, bt.gate))
+            try:
+                return self._first_general(per, n, table, seen, trules, gplans, guided, budget, steer)
+            finally:
+                for r in bias_rows:
+                    self._bias_scratch.release(r)
+
+    def _first_general(self, per, n, table, seen, trules, gplans, guided, budget, steer):
+        """_first_tokens' launch of the general head in its ruled / guided / closing / steered form."""
+        from .llm import GuideTables, PassTables, TokenMasks
+        rule = {}
+        if guided or any(t is not None for t in trules):
+            tm = getattr(self, "_mask_scratch", None)
+            if tm is None or tm.rows < 3 * n + self.GUIDE_MASKS:
+                tm = self._mask_scratch = TokenMasks(3 * max(n, self.PREFILL_MAX) + self.GUIDE_MASKS, self.cfg.llm.vocab_size, self.dev)
+                self._guide_scratch = None
+            gt = getattr(self, "_guide_scratch", None)
+            if guided and gt is None:
+                gt = self._guide_scratch = GuideTables(self.cfg.llm.vocab_size, self.dev, tm)
+            # every row of the pass, the rules' and the guides', is held until the launch is enqueued (the next pass's uploads are
+            # ordered behind it: same stream): a row given back earlier could be rewritten by a later acquire of this same pass
+            held = PassTables(tm, gt, trules, gplans)
+            try:
+                rule = dict(masks=tm.table, rules=ops.token_rules(held.rules, self.dev))
+                if guided:
+                    gstate = torch.tensor([0 if g is None else g.s0 for g in gplans], dtype=torch.int32).to(self.dev)
+                    close = {}
+                    if held.closes is not None:
+                        close = dict(closes=ops.guide_closes(held.closes, self.dev),
+                                     budget=torch.full((n,), budget, dtype=torch.int32).to(self.dev))
+                    rule["guide"] = gt.operands(ops.token_guides(held.guides, self.dev), gstate, **close)
+                out = ops.sample_rows(self._last_logits[:n], table, seen=seen, general=True, **rule, **steer)
+            finally:
+                held.release()
+            for k, g in enumerate(gplans):      # (the state words stay with the requests)
+                if g is not None:
+                    per[k]["guide_state"] = gstate[k:k + 1]
+            return out
+        return ops.sample_rows(self._last_logits[:n], table, seen=seen, general=True, **steer)
 
     @staticmethod
     def _logprob_part(logprobs, a: int, b: int):

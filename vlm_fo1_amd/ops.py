@@ -1112,6 +1112,102 @@ def _close_operands(g: GuideOperands, B: int, rows_form: bool):
     return out
 
 
+NO_STEER = (-1, 0.0, 0.0)      # fo1_token_steer_t of a row without a steer: no bias row, both penalties off
+
+
+def token_steers(rows: Sequence, device=None) -> torch.Tensor:
+    """The fo1_token_steer_t table (int32 [B, 4] holding int32, fp32, fp32, int32) from rows of (bias_row, frequency_penalty,
+    presence_penalty) — a row of the bias table (-1 = none) and the two count penalties (include/fo1.h) — or None for a row without a steer.
+    On `device` when given, else a host tensor."""
+    import struct
+    rows = [NO_STEER if r is None else r for r in rows]
+    raw = b"".join(struct.pack("<iffi", int(r[0]), float(r[1] or 0.0), float(r[2] or 0.0), 0) for r in rows)
+    tab = torch.frombuffer(bytearray(raw), dtype=torch.int32).view(-1, 4)
+    return tab if device is None else tab.to(device)
+
+
+def count_penalty_on(f, q) -> bool:
+    """The device's rule: a row's count penalty is on iff both penalties are finite (as fp32) and not both zero."""
+    import math
+    f, q = (float(torch.tensor(float(x or 0.0), dtype=torch.float32)) for x in (f, q))      # (a value beyond fp32's range is inf there)
+    return math.isfinite(f) and math.isfinite(q) and (f != 0.0 or q != 0.0)
+
+
+def gate_of(table: torch.Tensor, n_vocab: int) -> torch.Tensor:
+    """The gate bitmap (int32 [rows, seen_words(n_vocab)], the seen bitmap's layout) of a bias table (bf16) or a count table (int16 holding
+    uint16) [rows, >= n_vocab]: bit i of a row set iff entry i < n_vocab of the table's row is not zero (-0 counts as zero)."""
+    V = int(n_vocab)
+    bits = table[:, :V].contiguous().view(torch.int16)
+    nz = (bits & 0x7fff) != 0 if table.dtype == torch.bfloat16 else bits != 0
+    pad = torch.zeros(nz.shape[0], seen_words(V) * 32, dtype=torch.int64, device=table.device)
+    pad[:, :V] = nz
+    w = (pad.view(nz.shape[0], -1, 32) << torch.arange(32, device=table.device)).sum(-1)      # < 2^32, the sign bit folded below
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32).contiguous()
+
+
+class SteerOperands(NamedTuple):
+    """What a steered head takes (include/fo1.h): steers (token_steers, int32 [>= B, 4]); bias bf16 [bias rows, ld_bias >= V] with bias_gate
+    (gate_of) int32 [bias rows, ld_words], or None for both; counts int16 [>= B, ld_counts >= V, even] holding the uint16 counts with
+    count_gate int32 [>= B, ld_words], or None for both (then no row may have a count penalty on).  The accept form adds 1 to the accepted
+    token's count and sets its gate bit."""
+    steers: torch.Tensor
+    bias: Optional[torch.Tensor] = None
+    bias_gate: Optional[torch.Tensor] = None
+    counts: Optional[torch.Tensor] = None
+    count_gate: Optional[torch.Tensor] = None
+
+
+def _steer_operands(s: SteerOperands, B: int, V: int):
+    st = s.steers
+    assert st.dtype == torch.int32 and st.is_cuda and st.dim() == 2 and st.shape[1] == 4 and st.is_contiguous() and st.shape[0] >= B
+    ldg = 0
+    pb = pg = pc = pcg = None
+    rows_b = ld_b = ld_c = 0
+    if s.bias is not None:
+        b, g = s.bias, s.bias_gate
+        assert g is not None, "a bias table comes with its gate bitmap (gate_of)"
+        assert b.dtype == torch.bfloat16 and b.is_cuda and b.dim() == 2 and b.is_contiguous() and b.shape[0] >= 1 and b.shape[1] >= V
+        assert g.dtype == torch.int32 and g.is_cuda and g.dim() == 2 and g.is_contiguous() and g.shape[0] >= b.shape[0]
+        assert g.shape[1] % 4 == 0 and g.shape[1] * 32 >= V
+        pb, pg, rows_b, ld_b, ldg = b.data_ptr(), g.data_ptr(), b.shape[0], b.shape[1], g.shape[1]
+    if s.counts is not None:
+        c, g = s.counts, s.count_gate
+        assert g is not None, "a count table comes with its gate bitmap"
+        assert c.dtype == torch.int16 and c.is_cuda and c.dim() == 2 and c.is_contiguous() and c.shape[0] >= B and c.shape[1] >= V and c.shape[1] % 2 == 0
+        assert g.dtype == torch.int32 and g.is_cuda and g.dim() == 2 and g.is_contiguous() and g.shape[0] >= B
+        assert g.shape[1] % 4 == 0 and g.shape[1] * 32 >= V and (ldg in (0, g.shape[1])), "the two gate bitmaps share one row length"
+        pc, pcg, ld_c, ldg = c.data_ptr(), g.data_ptr(), c.shape[1], g.shape[1]
+    return pb, pg, rows_b, ld_b, pc, pcg, ld_c, ldg, st.data_ptr()
+
+
+def count_mark(counts: torch.Tensor, count_gate: torch.Tensor, n_vocab: int, rows: torch.Tensor, ids: torch.Tensor) -> None:
+    """counts[rows[i], ids[i]] += 1 (int16 [R, ld_counts] holding uint16) and the matching bit of count_gate (int32 [R, ld_words]) set, duplicates
+    included (fo1_count_mark); ids outside [0, n_vocab) and negative rows are skipped."""
+    assert counts.dtype == torch.int16 and counts.is_cuda and counts.dim() == 2 and counts.is_contiguous()
+    assert count_gate.dtype == torch.int32 and count_gate.is_cuda and count_gate.dim() == 2 and count_gate.is_contiguous()
+    assert count_gate.shape[0] >= counts.shape[0]
+    assert rows.dtype == ids.dtype == torch.int32 and rows.is_cuda and ids.is_cuda and rows.is_contiguous() and ids.is_contiguous() and rows.numel() == ids.numel()
+    rc = _L.load().fo1_count_mark(counts.data_ptr(), counts.shape[1], count_gate.data_ptr(), count_gate.shape[1], int(n_vocab), _ptr(rows), _ptr(ids),
+                                  rows.numel(), _stream())
+    _L.check(rc, "fo1_count_mark")
+
+
+def count_words(n_vocab: int) -> int:
+    """Entries per row of a count table: n_vocab rounded up to a multiple of 8."""
+    return -(-int(n_vocab) // 8) * 8
+
+
+def _all_levels(masks, rules, guide, B: int, V: int, rows_form: bool):
+    """The rule, guide and closing operands of a steered call, NULL for every level the caller left out."""
+    ro = _rule_operands(masks, rules, B, V) if (masks is not None or rules is not None or guide is not None) else (None, 0, 0, None)
+    go = _guide_operands(guide, B, V) if guide is not None else (None, 0, 0, None, 0, None, 0, None, None)
+    if guide is not None and guide.closes is not None:
+        co = _close_operands(guide, B, rows_form)
+    else:
+        co = (None, 0, None) + ((None,) if rows_form else ())
+    return ro, go, co
+
+
 def _sample_operands(logits: torch.Tensor, params: torch.Tensor):
     _chk(logits, "logits")
     pl, ld, B, V = _rows(logits, "logits")
@@ -1125,7 +1221,7 @@ def _sample_operands(logits: torch.Tensor, params: torch.Tensor):
 def sample_rows(logits: torch.Tensor, params: torch.Tensor, counter: Optional[torch.Tensor] = None, counter_stride: int = 1,
                 u: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, seen: Optional[torch.Tensor] = None,
                 general: bool = False, masks: Optional[torch.Tensor] = None, rules: Optional[torch.Tensor] = None,
-                guide: Optional[GuideOperands] = None) -> torch.Tensor:
+                guide: Optional[GuideOperands] = None, steer: Optional[SteerOperands] = None) -> torch.Tensor:
     """int32 [B]: one sampled id per row of logits [B, V] bf16 (fo1_sample_rows_bf16): temperature / top-k / top-p per row from `params`
     (sample_params), draw = Philox(counter, stream; seed) with counter = counter[b * counter_stride] (device int32; None = 0), or the explicit
     u [B] fp32.  seen (int32 [>= B, ld_words] bitmap) or general=True: the general head (fo1_sample_rows_seen_bf16), which also honours a
@@ -1133,7 +1229,8 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, counter: Optional[to
     banned) and rules (token_rules, int32 [>= B, 4]): the ruled head (fo1_sample_rows_ruled_bf16), the general head behind each row's bans.
     guide (GuideOperands, with masks and rules): the guided head (fo1_sample_rows_guided_bf16) — a guided row b picks in state guide.gstate[b]
     and the state after the pick is written back; with guide.closes the closing head (fo1_sample_rows_closing_bf16), where guide.budget[b] -
-    counter - 1 tokens may follow row b's pick."""
+    counter - 1 tokens may follow row b's pick.  steer (SteerOperands): the steered head (fo1_sample_rows_steered_bf16) — each row's additive
+    bias and count penalties on top of whichever of the forms above the other arguments select."""
     head, tail = _sample_operands(logits, params)
     B = head[3]
     if out is None:
@@ -1143,6 +1240,13 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, counter: Optional[to
         assert counter.dtype == torch.int32 and counter.is_cuda and counter.numel() > (B - 1) * counter_stride
     if u is not None:
         assert u.dtype == torch.float32 and u.is_cuda and u.is_contiguous() and u.numel() == B
+    if steer is not None:
+        ps, ldw = _seen_operand(seen, B, head[2])
+        ro, go, co = _all_levels(masks, rules, guide, B, head[2], True)
+        rc = _L.load().fo1_sample_rows_steered_bf16(*head, _ptr(counter), int(counter_stride), _ptr(u), out.data_ptr(), *tail[:2], ps, ldw, *ro, tail[2],
+                                                    *go, *co, *_steer_operands(steer, B, head[2]))
+        _L.check(rc, "fo1_sample_rows_steered_bf16")
+        return out
     if guide is not None and guide.closes is not None:
         ps, ldw = _seen_operand(seen, B, head[2])
         rc = _L.load().fo1_sample_rows_closing_bf16(*head, _ptr(counter), int(counter_stride), _ptr(u), out.data_ptr(), *tail[:2], ps, ldw,
@@ -1189,12 +1293,14 @@ def decode_sample_accept(logits: torch.Tensor, params: torch.Tensor, state: torc
 def decode_head_accept(logits: torch.Tensor, params: torch.Tensor, state: torch.Tensor, plan: torch.Tensor, ids_out: torch.Tensor,
                        stop_ids: Optional[torch.Tensor], done: torch.Tensor, seen: Optional[torch.Tensor] = None,
                        per_sequence_sets: bool = False, masks: Optional[torch.Tensor] = None, rules: Optional[torch.Tensor] = None,
-                       guide: Optional[GuideOperands] = None) -> None:
+                       guide: Optional[GuideOperands] = None, steer: Optional[SteerOperands] = None) -> None:
     """The general head of a decode step (fo1_decode_head_accept): decode_sample_accept with each row's greedy flag and repetition penalty
     honoured; the accepted token's bit is set in the row's `seen` bitmap (int32 [>= B, ld_words]; None only when no row has a penalty).
     per_sequence_sets: as decode_argmax_accept.  masks / rules (as sample_rows takes them): the ruled head (fo1_decode_head_ruled_accept), which
     reads both tables and writes neither.  guide (GuideOperands, with masks and rules): the guided head (fo1_decode_head_guided_accept), which
-    also advances guide.gstate, the only guide table it writes; with guide.closes the closing head (fo1_decode_head_closing_accept)."""
+    also advances guide.gstate, the only guide table it writes; with guide.closes the closing head (fo1_decode_head_closing_accept).
+    steer (SteerOperands): the steered head (fo1_decode_head_steered_accept) on top of whichever form the other arguments select; it counts
+    the accepted token in steer.counts / steer.count_gate."""
     B = state.shape[0]
     assert state.dtype == plan.dtype == ids_out.dtype == done.dtype == torch.int32 and ids_out.is_contiguous() and plan.is_contiguous()
     assert state.is_contiguous() and logits.shape[0] == B
@@ -1204,6 +1310,13 @@ def decode_head_accept(logits: torch.Tensor, params: torch.Tensor, state: torch.
         assert stop_ids is not None and stop_ids.dim() == 2 and stop_ids.shape[1] == 17 and stop_ids.is_contiguous() and stop_ids.dtype == torch.int32
         n_stop = -1
     ps, ldw = _seen_operand(seen, B, head[2])
+    if steer is not None:
+        ro, go, co = _all_levels(masks, rules, guide, B, head[2], False)
+        rc = _L.load().fo1_decode_head_steered_accept(*head, state.data_ptr(), plan.data_ptr(), ids_out.data_ptr(), ids_out.shape[1],
+                                                      stop_ids.data_ptr() if n_stop else None, n_stop, done.data_ptr(), *tail[:2], ps, ldw, *ro, tail[2],
+                                                      *go, *co, *_steer_operands(steer, B, head[2]))
+        _L.check(rc, "fo1_decode_head_steered_accept")
+        return
     if guide is not None and guide.closes is not None:
         rc = _L.load().fo1_decode_head_closing_accept(*head, state.data_ptr(), plan.data_ptr(), ids_out.data_ptr(), ids_out.shape[1],
                                                       stop_ids.data_ptr() if n_stop else None, n_stop, done.data_ptr(), *tail[:2], ps, ldw,
