@@ -4,7 +4,9 @@ Host side (as in the reference, where all of this runs on the CPU): PIL decode +
 (transforms/transform.py:6-36 + RandomResize([800], max_size=1333), inference_wrapper.py:128-134), box conversion, score sort, score
 threshold and NMS.  Device side: rescale / normalise (uint8 upload + table, as the main path's preprocessing) and the whole model.
 `torchvision.ops.nms` (inference_wrapper.py:9,217) is restated here in numpy (greedy, boxes with IoU > threshold suppressed, the
-published CPU algorithm); torchvision is not installed on either box, so that restatement is unpinned."""
+published CPU algorithm); torchvision is not installed on either box, so that restatement is unpinned.
+propose() / propose_device() give filter(inference(...)) with the box conversion, sort, threshold and NMS on the device instead
+(vlm_fo1_amd/csrc/upn_post.hip); the reference API above is unchanged."""
 import copy
 import os
 from typing import Dict, List, Union
@@ -36,6 +38,20 @@ def nms(boxes: np.ndarray, scores: np.ndarray, iou_threshold: float) -> np.ndarr
         iou = inter / (areas[i] + areas - inter)
         suppressed |= iou > iou_threshold
     return np.asarray(keep, dtype=np.int64)
+
+
+def kept_lists(results) -> Dict:
+    """Device post-process results (one vlm_fo1_amd.ops.UPNPost per image, equal cap) -> filter()'s dict: ONE device-to-host copy of the
+    images' blocks, then int boxes as lists and the scores rounded to 2 decimals on the host, over the kept entries only."""
+    from vlm_fo1_amd import ops
+    cap = results[0].keep_idx.shape[1]
+    blocks = results[0].block if len(results) == 1 else torch.cat([r.block for r in results])
+    host = ops.upn_post_views(blocks.cpu(), cap)
+    out = {"original_xyxy_boxes": [], "scores": []}
+    for i, n in enumerate(host.n_keep.tolist()):
+        out["original_xyxy_boxes"].append(host.boxes_i32[i, :n].tolist())
+        out["scores"].append([round(float(s), 2) for s in host.scores[i, :n].numpy()])
+    return out
 
 
 def resize_size(w: int, h: int, size: int = 800, max_size: int = 1333):
@@ -88,6 +104,31 @@ class UPNWrapper:
             boxes.append(out["pred_boxes"].clone())
             logits.append(out["pred_logits"][:, None].clone())
         return dict(pred_boxes=torch.stack(boxes), pred_logits=torch.stack(logits))
+
+    # ---- the same result with the post-process on the device -------------------------------------------------------------------------
+    def propose_device(self, image: List[Union[str, Image.Image]], min_score: float, nms_value: float = 0.8, max_boxes: int = None,
+                       prompt_type: str = "fine_grained_prompt"):
+        """inference() + filter() without the host in between, for callers that keep going on the GPU: per image the detector
+        and one launch that decodes, sorts, thresholds and runs NMS on the device (UPNEngine.propose).  -> a list with one
+        vlm_fo1_amd.ops.UPNPost per image: device tensors n_keep [1], keep_idx [1, cap] (query indices), boxes_f32 / boxes_i32
+        [1, cap, 4] (original pixels, x0 y0 x1 y1), scores [1, cap] (fp32, unrounded), in keep order = descending score; entries past
+        n_keep are unwritten.  cap = max_boxes, or the number of queries."""
+        if not isinstance(image, list):
+            image = [image]
+        input_images, image_sizes = self.construct_input(image)
+        return [self.model.propose(img, hw, min_score, nms_value, max_boxes, prompt_type, use_graph=self.use_graph)
+                for img, hw in zip(input_images, image_sizes)]
+
+    def propose(self, image: List[Union[str, Image.Image]], min_score: float, nms_value: float = 0.8, max_boxes: int = None,
+                prompt_type: str = "fine_grained_prompt"):
+        """filter(inference(image, prompt_type), min_score, nms_value) with the box conversion, the score sort, the threshold and the NMS
+        on the device: -> {"original_xyxy_boxes": [per image: list of [x0, y0, x1, y1] ints], "scores": [per image: list of 2-decimal
+        floats]}, cut to the first max_boxes per image when given (the reference's caller slices [:100]).  One small device-to-host
+        copy returns all images' kept entries; the 2-decimal rounding runs on the host over them.
+        Two differences from the host path, both deliberate: equal scores keep the lower query index first (argsort leaves ties
+        unspecified), and an image with nothing above min_score yields an empty list for that image while the remaining images are
+        still processed — filter()'s early return at the first empty image, which drops every later image, is not copied."""
+        return kept_lists(self.propose_device(image, min_score, nms_value, max_boxes, prompt_type))
 
     def construct_input(self, image: List[Union[str, Image.Image]]):
         input_images, image_sizes = [], []

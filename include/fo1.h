@@ -951,6 +951,42 @@ int fo1_topk_desc_f32(const float* scores, int stride, int n, int k, int32_t* id
                       size_t workspace_bytes, void* stream);
 int fo1_gather_rows_f32(const float* table, int ld_table, const int32_t* idx, float* out, int ld_out, int n, int D, void* stream);
 
+/* ------------------------------------------------------------------------
+ * UPN post-process on the device: what UPNWrapper.postprocess + filter do on the host (detect_tools/upn/inference_wrapper.py:138-237),
+ * one workgroup per image, no host read.  The definition (restated in numpy by tests/upn_post_cases.py), all in IEEE fp32
+ * with one rounding per operation and no fused multiply-add:
+ *   decode      x0 = cx - w/2, y0 = cy - h/2, x1 = x0 + w, y1 = y0 + h;  X0 = x0*W, Y0 = y0*H, X1 = x1*W, Y1 = y1*H;
+ *               score = 1 / (1 + exp(-logit))
+ *   order       score descending, equal scores: lower query index first (as fo1_topk_desc_f32)
+ *   candidates  the prefix of that order with score >= min_score
+ *   NMS         greedy over the candidates in order: area = (X1-X0)*(Y1-Y0),
+ *               inter = max(min(X1_i,X1_j) - max(X0_i,X0_j), 0) * max(min(Y1_i,Y1_j) - max(Y0_i,Y0_j), 0),
+ *               iou = inter / ((area_i + area_j) - inter); a candidate is dropped iff a candidate KEPT before it has
+ *               iou > iou_threshold (a NaN iou drops nothing); iou_threshold <= 0 (or NaN): no NMS
+ *   output      in keep order, the first min(max_keep, cap) kept: query index, fp32 box, int32 box (truncated toward zero; unspecified
+ *               for a non-finite coordinate), fp32 score; n_keep = their number.  Entries past n_keep are left untouched.
+ * boxes fp32 [Q][ld_boxes] (cx, cy, w, h), logits fp32 [Q][ld_logits] (element 0 of each row), 1 <= Q <= 1024.  `params` is read on
+ * the DEVICE (one resized tensor shape serves many original sizes, and a captured launch must see the new ones).
+ * fo1_upn_post_batch_f32 is the same for n_images images in one launch (grid = images): image b reads boxes + b*img_boxes,
+ * logits + b*img_logits (strides in floats), params[b], and writes each of the five outputs at its pointer + b*out_stride (in 4-byte
+ * words: an image's outputs form one record).  The sort keys, the boxes and the 1024 x 1024 suppression bit matrix live in LDS, so
+ * fo1_upn_post_workspace_bytes is 0 today and `workspace` may then be NULL; the pair stays in the signature for a form that needs scratch.
+ * ---------------------------------------------------------------------- */
+typedef struct fo1_upn_post_params_t {
+    float W, H;              /* original image size */
+    float min_score;
+    float iou_threshold;
+    int32_t max_keep;        /* >= 1 */
+} fo1_upn_post_params_t;
+size_t fo1_upn_post_workspace_bytes(int Q);
+int fo1_upn_post_f32(const float* boxes, int ld_boxes, const float* logits, int ld_logits, int Q, const fo1_upn_post_params_t* params,
+                     int32_t* n_keep, int32_t* keep_idx, float* boxes_f32, int32_t* boxes_i32, float* scores, int cap, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int fo1_upn_post_batch_f32(const float* boxes, int ld_boxes, long long img_boxes, const float* logits, int ld_logits, long long img_logits,
+                           int Q, int n_images, const fo1_upn_post_params_t* params, int32_t* n_keep, int32_t* keep_idx, float* boxes_f32,
+                           int32_t* boxes_i32, float* scores, int cap, long long out_stride, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

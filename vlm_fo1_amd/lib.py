@@ -162,6 +162,11 @@ SIGNATURES = {
     "fo1_topk_workspace_bytes": (c_size_t, [c_int]),
     "fo1_topk_desc_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fo1_gather_rows_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "fo1_upn_post_workspace_bytes": (c_size_t, [c_int]),
+    "fo1_upn_post_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
+                                 c_void_p]),
+    "fo1_upn_post_batch_f32": (c_int, [c_void_p, c_int, c_longlong, c_void_p, c_int, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_int, c_longlong, c_void_p, c_size_t, c_void_p]),
     "fo1_msda_fused_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                     c_void_p, c_void_p]),
     "fo1_add_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),

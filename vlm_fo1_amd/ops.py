@@ -1937,6 +1937,65 @@ def gather_rows_f32(table: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ---- UPN post-process (upn_post.hip) -----------------------------------------------------------------------------------------------
+class UPNPost(NamedTuple):
+    """Views into ONE int32 device block [images, 1 + 10 * cap] (`block`: one device-to-host copy returns everything): per image
+    n_keep | keep_idx [cap] | boxes_f32 [cap, 4] | boxes_i32 [cap, 4] | scores [cap]; entries past n_keep are unwritten."""
+    block: torch.Tensor
+    n_keep: torch.Tensor       # int32 [images]
+    keep_idx: torch.Tensor     # int32 [images, cap]
+    boxes_f32: torch.Tensor    # fp32 [images, cap, 4]
+    boxes_i32: torch.Tensor    # int32 [images, cap, 4]
+    scores: torch.Tensor       # fp32 [images, cap]
+
+
+def upn_post_views(block: torch.Tensor, cap: int) -> UPNPost:
+    """The UPNPost views of an int32 block [images, 1 + 10 * cap], on the device or after its copy to the host."""
+    n = block.shape[0]
+    return UPNPost(block, block[:, 0], block[:, 1:1 + cap], block[:, 1 + cap:1 + 5 * cap].view(torch.float32).view(n, cap, 4),
+                   block[:, 1 + 5 * cap:1 + 9 * cap].view(n, cap, 4), block[:, 1 + 9 * cap:1 + 10 * cap].view(torch.float32))
+
+
+def upn_post_params(sizes_hw, min_score: float, iou_threshold: float, max_keep: int, device) -> torch.Tensor:
+    """fo1_upn_post_params_t per image as an int32 device tensor [images, 5]: (W, H, min_score, iou_threshold) as fp32 bits, max_keep."""
+    import numpy as np
+    p = np.zeros((len(sizes_hw), 5), dtype=np.int32)
+    f = p.view(np.float32)
+    for i, (H, W) in enumerate(sizes_hw):
+        f[i, :4] = (W, H, min_score, iou_threshold)
+        p[i, 4] = max_keep
+    return torch.from_numpy(p).to(device)
+
+
+def upn_post(boxes: torch.Tensor, logits: torch.Tensor, params: torch.Tensor, cap: Optional[int] = None, out: Optional[torch.Tensor] = None) -> UPNPost:
+    """postprocess + filter of the UPN wrapper on the device (fo1_upn_post_batch_f32; the definition: include/fo1.h): boxes fp32
+    [Q, >= 4] or [images, Q, >= 4] (cx, cy, w, h), logits fp32 [Q] / [images, Q] (any element stride, e.g. a column of the class
+    GEMM's output), params = upn_post_params(...).  One launch, grid = images; `cap` (default Q) bounds the kept entries per image."""
+    if boxes.dim() == 2:
+        boxes, logits = boxes[None], logits[None]
+    if not (boxes.is_cuda and boxes.dtype == torch.float32 and boxes.dim() == 3 and boxes.shape[2] >= 4 and boxes.stride(2) == 1):
+        raise TypeError("upn_post: boxes must be an fp32 GPU tensor [images, Q, >= 4] with unit column stride")
+    n, Q = boxes.shape[0], boxes.shape[1]
+    if not (logits.is_cuda and logits.dtype == torch.float32 and tuple(logits.shape) == (n, Q)):
+        raise TypeError("upn_post: logits must be an fp32 GPU tensor [images, Q]")
+    if not (params.is_cuda and params.dtype == torch.int32 and tuple(params.shape) == (n, 5) and params.is_contiguous()):
+        raise TypeError("upn_post: params must be upn_post_params(...) for the same images")
+    cap = Q if cap is None else cap
+    if out is None:
+        out = torch.empty(n, 1 + 10 * cap, dtype=torch.int32, device=boxes.device)
+    elif not (out.is_cuda and out.dtype == torch.int32 and tuple(out.shape) == (n, 1 + 10 * cap) and out.is_contiguous()):
+        raise TypeError("upn_post: out must be a contiguous int32 GPU tensor [images, 1 + 10 * cap]")
+    r = upn_post_views(out, cap)
+    lib = _L.load()
+    need = lib.fo1_upn_post_workspace_bytes(Q)
+    ws = _workspace("upn_post", boxes.device, need) if need else None
+    _L.check(lib.fo1_upn_post_batch_f32(boxes.data_ptr(), boxes.stride(1) if Q > 1 else 4, boxes.stride(0) if n > 1 else 0, logits.data_ptr(), logits.stride(1) if Q > 1 else 1,
+                                        logits.stride(0) if n > 1 else 0, Q, n, params.data_ptr(), r.n_keep.data_ptr(), r.keep_idx.data_ptr(),
+                                        r.boxes_f32.data_ptr(), r.boxes_i32.data_ptr(), r.scores.data_ptr(), cap, out.stride(0), _ptr(ws),
+                                        ws.numel() if ws is not None else 0, _stream()), "fo1_upn_post_batch_f32")
+    return r
+
+
 # ---- Swin backbone pieces (swin_ops.hip, attention.hip) ------------------------------------------------------------------------
 def attention_window_bias(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, items: torch.Tensor, n_heads: int, head_dim: int, scale: float,
                           bias: torch.Tensor, ws: int, shift: int, nwy: int, nwx: int, flops: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -480,6 +480,19 @@ class UPNEngine:
         ops.replay_graph(g)
         return out
 
+    def propose(self, img: torch.Tensor, size_hw, min_score: float, iou_threshold: float = 0.8, max_keep: Optional[int] = None,
+                prompt_type: str = "fine_grained_prompt", use_graph: bool = True) -> "ops.UPNPost":
+        """The detector and its post-process without a host step in between: forward_graph (or forward) and then ONE eager launch on
+        the same stream (ops.upn_post: decode to the original size_hw = (H, W), score sort, score >= min_score, greedy NMS at
+        iou_threshold, at most max_keep kept).  The captured graph is not touched.  -> device tensors (ops.UPNPost, one image)."""
+        out = self.forward_graph(img, prompt_type) if use_graph else self.forward(img, prompt_type)
+        nq = out["pred_logits"].shape[0]
+        max_keep = nq if max_keep is None else int(max_keep)
+        if max_keep < 1:
+            raise ValueError("propose: max_keep must be >= 1")
+        params = ops.upn_post_params([size_hw], min_score, iou_threshold, max_keep, out["pred_boxes"].device)
+        return ops.upn_post(out["pred_boxes"], out["pred_logits"], params, cap=min(max_keep, nq))
+
     def forward(self, img: torch.Tensor, prompt_type: str = "fine_grained_prompt") -> dict:
         if prompt_type not in ("fine_grained_prompt", "coarse_grained_prompt"):
             raise ValueError("prompt_type must be 'fine_grained_prompt' or 'coarse_grained_prompt' (inference_wrapper.py:51-52)")
